@@ -14,8 +14,10 @@ contiguous ranges and the only collective on the path is the per-iteration all-r
 of still-active problems.  `--scaling weak` (default): per-GPU batch fixed (4096 each);
 `--scaling strong --global-batch 4096`: the north star's fixed 4096-problem batch split over the ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel =
-the structured interior-point solve) and `cpu_baseline` (oracle PTR loop timed on the host).
+Prints ONE JSON line on rank 0: the headline figure (`value`, `ms_per_step`, ...) and nothing else is measured.  `--full`
+adds `roofline` (dominant kernel = the structured interior-point solve), `cpu_baseline` (oracle PTR loop timed on the
+host) and every other record, written to `bench_records.json`.  `--dump-outputs DIR` writes the last timed step's results
+(`dump_outputs`); the Monte-Carlo inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -109,7 +111,8 @@ def _get(d, *path):
 
 def compact_line(out, records_file=None):
     """The ONE stdout line of the contract: headline fields, `roofline`, `cpu_baseline`, one number per parity
-    record -- nothing else.  Everything `main()` gathers goes to `bench_records.json` (`records_file`); the line is kept under
+    record -- nothing else; the headline fields alone for a record without `roofline` (a run without `--full`).
+    Everything `main()` gathers goes to `bench_records.json` (`records_file`); the line is kept under
     LINE_BYTES_MAX bytes and is strict JSON (no NaN / Infinity), tests/test_bench_line.py checks both on a canned record."""
     r = out.get("roofline") or {}
     k1 = out.get("roofline_discretize") or {}
@@ -122,6 +125,10 @@ def compact_line(out, records_file=None):
     line["config"] = {k: cfg.get(k) for k in ("workload", "global_batch", "streams_per_gpu", "lookahead", "parallelism") if k in cfg}
     if cfg.get("collective_note"):
         line["config"]["collective_note"] = str(cfg["collective_note"])[:160]
+    if "roofline" not in out:         # a plain run measured the headline only (the rest: `--full`)
+        line["failed_instances"] = out.get("failed_instances")
+        line["scp_iterations_executed_per_step"] = out.get("scp_iterations_executed_per_step")
+        return json.dumps(line, allow_nan=False, separators=(",", ":"))
     line["roofline"] = {
         "bound": r.get("bound"), "achieved": _num(r.get("achieved")), "peak": _num(r.get("peak")), "unit": r.get("unit"),
         "frac": _num(r.get("frac")), "traffic": _num(r.get("traffic")), "kernel": r.get("kernel"),
@@ -211,6 +218,43 @@ def write_records(out, names=("bench_records.json",)):
             except OSError:
                 pass
     return written
+
+
+DUMP_BYTES_MAX = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, sol, hist, offset=0, prefix="", budget=DUMP_BYTES_MAX):
+    """`--dump-outputs DIR`: what a caller of the timed path receives from its last step (`PTR.group_collect`: the batch's
+    solutions and per-iteration history, history as [problem, iteration]) as float64 `DIR/<prefix><name>.npy`, so that two builds
+    can be compared output for output.  Every written number is finite: where an array holds NaN or +-inf (the relative
+    improvement of the first iteration is NaN, as in the reference; the cost of a failed problem is inf), those entries are
+    written as 0 and `<name>_nonfinite.npy` codes them (0 finite, 1 NaN, 2 +inf, 3 -inf).  When the whole batch exceeds `budget`
+    bytes, a fixed sample of its problems (seed 0) is written; `instance.npy` holds the Monte-Carlo index of every written row.
+    Returns the bytes written."""
+    B = len(sol.status)
+    per_problem = {"xd": sol.xd, "ud": sol.ud, "p": sol.p, "defect": sol.defect, "cost": sol.cost, "J": sol.J, "J_aug": sol.J_aug,
+                   "feas": sol.feas, "solved": np.array([s == "SCP_SOLVED" for s in sol.status]), "iterations": sol.iterations}
+    per_problem.update({"hist_" + f: getattr(hist, f).T for f in type(hist).__dataclass_fields__})
+    per_problem["instance"] = offset + np.arange(B)
+    arrays = {}
+    for k, v in per_problem.items():
+        a = np.array(v, dtype=np.float64)
+        bad = ~np.isfinite(a)
+        if bad.any():
+            arrays[k + "_nonfinite"] = np.where(np.isnan(a), 1.0, np.where(a == np.inf, 2.0, np.where(a == -np.inf, 3.0, 0.0)))
+            a[bad] = 0.0
+        arrays[k] = a
+    row_bytes = 8 * sum(a.size // B for a in arrays.values())
+    npy_header = 128                            # (bytes: the header numpy writes for these shapes)
+    keep = min(B, max(0, budget - npy_header * (len(arrays) + 1) - 8 * sol.td.size) // row_bytes)
+    rows = np.arange(B) if keep == B else np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for k, a in [("td", np.asarray(sol.td, dtype=np.float64))] + [(k, a[rows]) for k, a in arrays.items()]:
+        path = os.path.join(dirname, prefix + k + ".npy")
+        np.save(path, np.ascontiguousarray(a))
+        total += os.path.getsize(path)
+    return total
 
 
 def cpu_baseline(model, N, Nsub, iters, budget_s=20.0):
@@ -1107,7 +1151,13 @@ def main():
                          "leaves the device; what a Julia host binds), torch = torch.distributed from Python (dist.make_lagged_all_reduce)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--global-batch", type=int, default=4096, help="total problems over all GPUs (--scaling strong)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: roofline and per-kernel figures, the PCIe-inclusive rate, the "
+                    "to_convergence and strong-scaling records, agreement with the oracle, the CPU baseline and the generic-path records "
+                    "(all written to bench_records.json; the --no-* options leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -1218,6 +1268,32 @@ def main():
     if dist is not None:
         dist.all_reduce(tot)
     executed, n_failed, B_total = (int(v) for v in tot.tolist())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sol, hist, offset, "rank%d_" % rank if world > 1 else "", DUMP_BYTES_MAX // world)
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "SCP iterations/sec (batched PTR, N=%d nodes)" % N,
+            "value": executed * args.steps / dt, "unit": "SCP iterations/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "%s PTR N=%d Nsub=%d iter_max=%d, Monte-Carlo batch %s" % (
+                           model, N, Nsub, iters, ("%d/GPU" % B) if args.scaling == "weak" else ("%d global (%d on rank 0)" % (B_total, B))),
+                       "global_batch": B_total, "streams_per_gpu": pbm.streams, "lookahead": lookahead, "solver_opts": sopts,
+                       "parallelism": "batch-shard x%d, 1 convergence all-reduce (8 bytes) / %d PTR iteration(s)" % (world, lookahead),
+                       "collective": ("none (one GPU)" if world == 1 else
+                                      ("scp_ptr_run_sharded: RCCL inside libscp_mi355x.so, device-resident count (C ABI)" if comm is not None
+                                       else "torch.distributed all_reduce from Python, lagged by one window")),
+                       "collective_note": comm_note},
+            "scp_iterations_executed_per_step": executed, "failed_instances": n_failed,
+        }
+    if not args.full:       # a plain run: the headline figure only
+        pbm.close()
+        if rank == 0:
+            print(compact_line(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # The same solve through the HOST-BUFFER boundary (never `value`): per-problem data host -> HBM, guesses on the device, the
     # PTR iterations, then trajectories / defects / history HBM -> host and the host-side result objects.
@@ -1254,7 +1330,6 @@ def main():
         one.close()
         solo = [s_sec[i] / max(s_cnt[i], 1) for i in range(4)]
     if rank == 0:
-        scp_iters = executed * args.steps
         # ---- roofline of the dominant kernel (K3, structured IPM): algorithmic bytes = stage-form subproblem
         #      data read once + scaled solution written once, per problem per launch ----
         info = pbm.info
@@ -1324,20 +1399,7 @@ def main():
         except (OSError, KeyError, ValueError):
             pass
         ms_ = lambda v: None if v != v else 1e3 * v
-        out = {
-            "metric": "SCP iterations/sec (batched PTR, N=%d nodes)" % N,
-            "value": scp_iters / dt, "unit": "SCP iterations/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "%s PTR N=%d Nsub=%d iter_max=%d, Monte-Carlo batch %s" % (
-                           model, N, Nsub, iters, ("%d/GPU" % B) if args.scaling == "weak" else ("%d global (%d on rank 0)" % (B_total, B))),
-                       "global_batch": B_total, "streams_per_gpu": pbm.streams, "lookahead": lookahead, "solver_opts": sopts,
-                       "parallelism": "batch-shard x%d, 1 convergence all-reduce (8 bytes) / %d PTR iteration(s)" % (world, lookahead),
-                       "collective": ("none (one GPU)" if world == 1 else
-                                      ("scp_ptr_run_sharded: RCCL inside libscp_mi355x.so, device-resident count (C ABI)" if comm is not None
-                                       else "torch.distributed all_reduce from Python, lagged by one window")),
-                       "collective_note": comm_note},
-            "scp_iterations_executed_per_step": executed, "failed_instances": n_failed,
+        out.update({
             "roofline": roof,
             "roofline_discretize": k1,
             "kernel_seconds": {"discretize": ksec[0], "assemble": ksec[1], "ipm": ksec[2], "extract_update": ksec[3],
@@ -1354,7 +1416,7 @@ def main():
                          if sol.feas.any() else None,
                          "ipm_max_pres": float(hist.pres.max()), "ipm_max_dres": float(hist.dres.max()),
                          "ipm_max_gap": float(hist.gap.max())},
-        }
+        })
         out["roofline"]["frac_survey_8d"] = survey_8d.get("frac") if isinstance(survey_8d, dict) else None
         # the same per-solver-iteration pricing for FULL launches only (every wave slot busy for the whole launch: the first two launches of a
         # run on one handle).  The average over all launches above includes the late launches of a converged run, which the warm start

@@ -4,6 +4,7 @@
 # K3 + K1v (headline step), K5 (full chip, one workgroup per problem, the free-flyer geometry), K1 (reference form), K3 phase clocks, and
 # BASELINE.json configs[2] run to iter_max.  Environment: SKIP_TESTS / SKIP_BENCH / SKIP_PROF / ONLY_HEAD = 1 to leave parts out.
 TAG=${1:-r06_final}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
@@ -13,7 +14,7 @@ if [ -z "$SKIP_TESTS" ]; then
 tail -4 $OUT/pytest.log
 fi
 if [ -z "$SKIP_BENCH" ]; then
-( time python bench.py ${BENCH_ARGS:---steps 20 --warmup 5} ) > $OUT/bench.json 2> $OUT/bench.err
+( time python bench.py --full ${BENCH_ARGS:---steps 20 --warmup 5} ) > $OUT/bench.json 2> $OUT/bench.err
 tail -c 3000 $OUT/bench.json; echo; tail -3 $OUT/bench.err
 cp bench_records.json $OUT/bench_records.json 2>/dev/null
 fi
@@ -36,7 +37,7 @@ passes() {   # passes <prefix> <grep -A lines> -- <command>: kernel trace + FETC
   rm -rf $OUT/${pre}kt $OUT/${pre}pmc_FETCH_SIZE $OUT/${pre}pmc_WRITE_SIZE $OUT/${pre}pmc_sq
 }
 # ---- headline workload (K3, K1v, K2, K4) ----
-passes "" 30 -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-generic --no-solo --no-convergence
+passes "" 30 -- python "$REPO/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline --no-generic --no-solo --no-convergence
 # ---- K3 phase clocks (make prof) ----
 if [ -f $GRAFT_REPO_ROOT/scptoolbox.jl_amd/csrc/libscp_mi355x_prof.so ]; then
   ( cd $GRAFT_REPO_ROOT; for IT in 1 10; do SCP_MI355X_LIB=$GRAFT_REPO_ROOT/scptoolbox.jl_amd/csrc/libscp_mi355x_prof.so python tools/ipm_phase_profile.py rocket_landing 4096 $IT; done ) > $OUT/k3_phase_profile.txt 2>&1

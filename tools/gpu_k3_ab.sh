@@ -18,6 +18,6 @@ if [ -z "$SKIP_TESTS" ]; then
 tail -6 $OUT/pytest.log
 fi
 if [ -z "$SKIP_BENCH" ]; then
-( time python bench.py ${BENCH_ARGS:---steps 2 --warmup 1 --no-generic --no-cpu-baseline} ) > $OUT/bench.json 2> $OUT/bench.err
+( time python bench.py --full ${BENCH_ARGS:---steps 2 --warmup 1 --no-generic --no-cpu-baseline} ) > $OUT/bench.json 2> $OUT/bench.err
 tail -c 1500 $OUT/bench.json; echo; tail -4 $OUT/bench.err
 fi
