@@ -9,9 +9,16 @@
 //                      bit-identical subproblem data
 //   solve_subproblem!  the structured primal-dual interior-point method of oracle/ipm_struct.py / csrc/ipm2_*.hpp
 //                      (Mehrotra predictor-corrector, NT scaling, quasi-definite block sweep + arrow column, static
-//                      regularisation + one refinement step) in scalar C++ with small dense blocks
+//                      regularisation + one refinement step) in scalar C++ with small dense blocks, warm-started from
+//                      snapshots of the previous solve and repeated on failure exactly as the device does
+//                      (CpuIpm::solve below = the `attempt` loop of csrc/ipm2_run.hpp)
 //   outer loop         src/solvers/ptr.jl:448-532 (fixed iteration count, reference update) per problem
 // One problem per OpenMP task (`omp parallel for` over the batch), single-threaded inside a problem like the reference.
+// This file is the scalar TWIN of the device solver K3: it states only what the device does, every K3 change is mirrored
+// here, and tests/test_cpu_port_cpu.py pins its results.  It has no run-time settings and reads
+// nothing from the environment.  The warm-start research of rounds 4 to 6 was done in this file (other warm-start schemes,
+// Mehrotra's starting point, Gondzio correctors, ...; findings in DESIGN.md); that code is in the git history, last in
+// commit 615bb3b.
 // Build: hipcc -x hip (host pass only; no kernel is instantiated), see oracle/Makefile.
 #include <hip/hip_runtime.h>
 #include <omp.h>
@@ -19,8 +26,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -36,34 +41,28 @@ extern "C" int oracle_discretize(int model_id, const double* par, int N, int Nsu
 namespace {
 using namespace scp;
 
+// The settings of the solver: the values the device runs with (scptoolbox.jl_amd/ptr.py, include/scp_mi355x.h).  They are constants:
+// the twin solves with one algorithm and has no switches.  (Experiments with other values and rules: git history, commit 615bb3b.)
 struct IpmOpts {
-    int max_iter = 100, nref = 1, stall = 3;
-    double feastol = 1e-8, abstol = 1e-8, reltol = 1e-8, reg = 1e-12, ref_gap = 1e-2;
-    // warm start of the IPM (environment SCP_CPU_WARM=mode, SCP_CPU_WARM_MU, SCP_CPU_WARM_FROM, ...): 0 cold (two-solve ECOS-style
-    // point), 4 = what the device does since round 4: two snapshots of the previous solve (the iterates where mu first fell
-    // below warm_save_mu_coarse / warm_save_mu), the fine one when the reference moved less than warm_dev, else the coarse one.
-    // Experiments kept for the record: 1 structured centred point about the reference, 2 previous FINAL iterate pushed into the
-    // interior (the device's round-2/3 scheme: ~32 iterations per warm solve against ~15), 3 fine snapshot only.
-    int warm = 5, warm_from = 1, warm_min_cold = 25, warm_max_iter = 45;
-    // warm == 5 (round 6, what the device does now): NL snapshot levels -- the iterates at which mu first fell below lvl_mu[l] -- and the
-    // next solve starts from the FINEST level l whose deviation bound covers the previous solution's deviation, prev_dev <= lvl_dev[l]
-    // (and whose snapshot exists; level 0 only where cold solves are slow, warm_min_cold).  A snapshot at mu = 1e-9 is the right start when
-    // the reference moved by 1e-8 and the wrong one when it moved by 1e-4: the new problem's residual at that point (~ the deviation)
-    // is then far above the distance to the boundary and the iteration crawls with steps of 0.01 (45 iterations, then the cold repeat).
+    static constexpr int max_iter = 100, nref = 1, stall = 3;
+    static constexpr double feastol = 1e-8, abstol = 1e-8, reltol = 1e-8;
+    static constexpr double ref_gap = 1e-2;     // directions are refined (nref steps) once relgap < ref_gap; robust attempt: from the start
+    static constexpr double reg = 1e-12;        // static regularisation at the start of a subproblem (device: reg_cur) ...
+    static constexpr int reg_escalate = 4;      // ... x10, at most this often per factorisation, when a factorisation breaks down
+    static constexpr double step_frac = 0.99;   // fraction of the step to the boundary
+    // Warm start: NL snapshot levels -- level l holds the iterate at which mu first fell below lvl_mu[l] -- and the next solve starts
+    // from the FINEST level l whose deviation bound covers the previous solution's deviation, prev_dev <= lvl_dev[l] (and whose snapshot
+    // exists; level 0 only where cold solves are slow, warm_min_cold).  A snapshot at mu = 1e-9 is the right start when the reference
+    // moved by 1e-8 and the wrong one when it moved by 1e-4: the new problem's residual at that point (~ the deviation) is then far above
+    // the distance to the boundary and the iteration crawls with steps of 0.01 (45 iterations, then the cold repeat).
     static constexpr int NL = 4;
-    double lvl_mu[NL] = {1e-1, 1e-5, 1e-8, 1e-10};
-    double lvl_dev[NL] = {1e300, 1e-1, 1e-3, 1e-6};
-    int lvl_cap[NL] = {45, 45, 45, 16};   // iteration limit of a warm attempt from level l (experiment: SCP_CPU_LVL_CAP)
-    int almost_lvl = NL - 2;              // finest level used after a solve that ended ALMOST_OPTIMAL (its last iterates are not well centred; SCP_CPU_ALMOST_LVL)
-    double lvl_floor = 1e-2;              // > 0: an iterate refreshes level l only if lvl_mu[l] * lvl_floor <= mu <= lvl_mu[l] (SCP_CPU_LVL_FLOOR)
-    int cross = 0;                        // 1: a level's snapshot is the iterate that CROSSES the level (mu_prev > level >= mu); a warm solve
-                                          // that starts below a level leaves that level's snapshot alone (SCP_CPU_CROSS=0: first iterate below)
-    int ref_on_stall = 0;         // experiment: refine once the merit has not improved for this many iterations
-    int ref_corrector_only = 0;   // experiment: no refinement of the predictor (affine) direction
-    double warm_mu = 1e-5, warm_dev = 1e-3, warm_save_mu = 1e-9, warm_save_mu_coarse = 1e-1;   // (fine level 1e-9 since round 6, like the device)
-    int reg_escalate = 4;
-    double stall_rel = 1.0;
-    double step_frac = 0.99, cgamma = 0.0;   // experiments: SCP_CPU_STEPFRAC, SCP_CPU_CGAMMA
+    static constexpr double lvl_mu[NL] = {1e-1, 1e-5, 1e-8, 1e-10};
+    static constexpr double lvl_dev[NL] = {1e300, 1e-1, 1e-3, 1e-6};
+    static constexpr int lvl_cap[NL] = {45, 45, 45, 16};   // iteration limit of a warm attempt from level l
+    static constexpr int almost_lvl = NL - 2;      // finest level used after a solve that ended ALMOST_OPTIMAL (its last iterates are not well centred)
+    static constexpr double lvl_floor = 1e-2;      // an iterate refreshes level l only if lvl_mu[l] * lvl_floor <= mu <= lvl_mu[l]
+    static constexpr int warm_min_cold = 25;       // level 0 is used only if the last cold solve of the problem took at least this many iterations
+    static constexpr int warm_from = 1;            // first PTR iteration that may start warm
 };
 struct IpmResult {
     int status = 2, iters = 0;   // 0 OPTIMAL, 1 ALMOST_OPTIMAL, 2 ITERATION_LIMIT, 3 NUMERICAL_ERROR
@@ -118,19 +117,15 @@ struct CpuIpm {
     // factor storage per node
     std::vector<double> Lz, Lnu, X, Y, Dt, Ft, cf, C0, Ycz, Ycnu, socW, spL;
     std::vector<double> fb, ft;
-    std::vector<double> xi_prev, lam_prev;   // final iterate of the previous solve (warm-start experiments)
-    std::vector<double> xi_snap, s_snap, lam_snap;   // warm == 3: the iterate at which mu first fell below warm_save_mu (a well-centred point)
-    bool snap_ok = false;
-    std::vector<double> xi_snapA, s_snapA, lam_snapA;   // warm == 4: coarse snapshot (mu <= warm_save_mu_coarse) for large reference deviations
-    bool snapA_ok = false; int snap_level = 1;   // level the next warm solve starts from: 0 coarse, 1 fine (warm == 5: 0 .. NL - 1)
-    std::vector<double> xi_sn[IpmOpts::NL], s_sn[IpmOpts::NL], lam_sn[IpmOpts::NL];   // warm == 5
+    // constants of the bound subproblem (setup): -h, c, diag(Q); norms of the stopping rule; degree of the cone
+    std::vector<double> hneg, cv, qd;
+    double nrm_h = 1, nrm_c = 1, deg = 0;
+    // iterate, residuals, directions (reset at the start of every run)
+    std::vector<double> xi, dxi, rx, exi, rxe, s, lam, rz, w, rtil, ds, dl, gd, r2, el, ge, sn, ln, nuv;
+    // warm start: the snapshot levels of IpmOpts, kept from one subproblem of this problem to the next
+    std::vector<double> xi_sn[IpmOpts::NL], s_sn[IpmOpts::NL], lam_sn[IpmOpts::NL];
     bool sn_ok[IpmOpts::NL] = {false, false, false, false};
-    bool sn_ok_prev[IpmOpts::NL] = {false, false, false, false};   // availability before the current solve
-    double sn_acc[IpmOpts::NL] = {0, 0, 0, 0};   // reference deviation accumulated since the level's snapshot was taken
-    bool sn_new[IpmOpts::NL] = {false, false, false, false};   // taken by the last solve
-    bool use_warm = false;
-    long gondzio_tried = 0, gondzio_kept = 0;
-    IpmOpts opt;
+    double reg = IpmOpts::reg;   // static regularisation of the current subproblem
 
     // ---- slab views ----
     const double* st(int k) const { return P + (long)k * SR; }
@@ -433,7 +428,7 @@ struct CpuIpm {
                 for (int c2 = 0; c2 < MNU; c2++) {
                     double acc = 0.0;
                     for (int j = 0; j < nz; j++) acc += Yk[j * MNU + c1] * Yk[j * MNU + c2];
-                    if (c1 == c2) acc += cfk[c1 * 2 + 1] + (nu_live(k, c1) ? opt.reg : 0.0);
+                    if (c1 == c2) acc += cfk[c1 * 2 + 1] + (nu_live(k, c1) ? reg : 0.0);
                     Sn[c1 * MNU + c2] = acc;
                 }
             if (!chol(Sn, MNU, MNU)) return false;
@@ -722,309 +717,249 @@ struct CpuIpm {
         return mm;
     }
 
-    // ---------------- main loop (oracle/ipm_struct.py::solve, csrc/ipm2_run.hpp) ----------------
-    IpmResult solve(std::vector<double>& best)
+    // ================ one interior-point run: the steps csrc/ipm2_run.hpp names, in its order ================
+    // constants of the bound subproblem, once for all attempts
+    void setup()
     {
-        std::vector<double> xi(XI, 0), dxi(XI, 0), rx(XI, 0), exi(XI, 0), rxe(XI, 0), cv(XI), qd(XI);
-        std::vector<double> s(ROWS, 0), lam(ROWS, 0), rz(ROWS, 0), w(ROWS, 1), rtil(ROWS, 0), ds(ROWS, 0), dl(ROWS, 0), gd(ROWS, 0), r2(ROWS, 0),
-            el(ROWS, 0), hneg(ROWS), ge(ROWS, 0), sn(ROWS), ln(ROWS);
-        std::vector<double> nuv((size_t)N * MNU, 0);
-        best.assign(XI, 0.0);
+        hneg.resize(ROWS); cv.resize(XI); qd.resize(XI);
         build_constants(hneg.data(), cv.data(), qd.data());
-        const double cost_const = P[o.scal + 1];
-        double nh = 0, nc = 0, deg = 0;
+        double nh = 0, nc = 0;
+        deg = 0;
         for (long i = 0; i < ROWS; i++) { nh += hneg[i] * hneg[i]; if (!is_dead(i) && !is_soc(i)) deg += 1.0; }
         for (long i = 0; i < XI; i++) nc += cv[i] * cv[i];
         deg += (double)N * nsoc;
-        const double nrm_h = std::max(1.0, std::sqrt(nh)), nrm_c = std::max(1.0, std::sqrt(nc));
-        IpmResult res, bestr;
-        double best_merit = 1e300; int best_it = 0;
-        double prog_merit = 1e300; int prog_it = 0;
-        double gap = 0, mu = 0, sigma = 0, relgap_it = 1e300;
-        int it;
-        int it0 = -1;
-        bool snap_taken = false;
-        double trace_alpha = 0.0;
-        bool snapA_taken = false;
-        bool sn_taken[IpmOpts::NL] = {false, false, false, false};
-        double mu_prev_it = 1e300;     // mu of the previous iterate of this solve (a cold solve comes from above every level)
-        if (use_warm && opt.warm == 5 && sn_ok[snap_level] && (long)xi_sn[snap_level].size() == XI) {
-            it0 = 0;
-            xi = xi_sn[snap_level]; s = s_sn[snap_level]; lam = lam_sn[snap_level];
-        } else
-        if (use_warm && opt.warm == 4 && snap_level == 0 && snapA_ok && (long)xi_snapA.size() == XI) {
-            it0 = 0;
-            xi = xi_snapA; s = s_snapA; lam = lam_snapA;
-        } else
-        if (use_warm && (opt.warm == 3 || (opt.warm == 4 && snap_level == 1)) && snap_ok && (long)xi_snap.size() == XI) {
-            // the well-centred intermediate iterate of the previous solve, as it is: the infeasible-start iteration absorbs the
-            // change of the problem data (residuals of the order of the reference deviation)
-            it0 = 0;
-            xi = xi_snap; s = s_snap; lam = lam_snap;
-        } else
-        if (use_warm && opt.warm == 1 && (long)xi_prev.size() != XI) xi_prev.assign(XI, 0.0);   // experiment: structured COLD start
-        if (use_warm && opt.warm != 3 && opt.warm != 4 && opt.warm != 5 && (long)xi_prev.size() == XI) {
-            it0 = 0;
-            const double m0 = opt.warm_mu;
-            // primal: the reference point (= previous solution) with its epigraph variables
-            xi = xi_prev;
-            for (int k = 0; k < N; k++) for (int j = 0; j < nz; j++) Z(xi.data(), k, j) = st(k)[S::O_ZREF + j];
-            for (int j = 0; j < np; j++) PV(xi.data(), j) = G()[S::Q_PREF + j];
-            if (opt.warm == 1) {
-                // structured point: epigraph variables chosen so that every pair / L_inf block is exactly centred at m0
-                std::vector<double> a0(ROWS, 0.0), zero(XI, 0.0);
-                std::vector<double> xm = xi;
-                for (int k = 0; k < N; k++) for (int i = 0; i < AS; i++) AUX(xm.data(), k, i) = 0.0;
-                for (int i = 0; i < AG; i++) GAUX(xm.data(), i) = 0.0;
-                G_apply(xm.data(), a0.data());
-                for (long i = 0; i < ROWS; i++) a0[i] += hneg[i];   // row activity incl. constants (first row of each pair: +a)
-                auto typeA = [&](double a, double om) { om = std::max(om, 1e-300); return (m0 + std::sqrt(m0 * m0 + om * om * a * a)) / om; };
-                for (int k = 0; k < N; k++) {
-                    for (int i = 0; i < nx; i++) AUX(xi.data(), k, S::A_Y + i) = k < N - 1 ? typeA(ROW(a0.data(), k, i), st(k)[S::O_OM + i]) : 0.0;
-                    for (int i = 0; i < ns; i++) {
-                        const double hw = st(k)[S::O_HW + i], ah = ROW(a0.data(), k, S::R_H0 + i), bq = hw * ah + 2 * m0;
-                        AUX(xi.data(), k, S::A_V + i) = (bq + std::sqrt(bq * bq - 4 * hw * m0 * ah)) / (2 * hw);
-                    }
-                    AUX(xi.data(), k, S::A_EX) = 2 * nx * m0 / st(k)[S::O_TTR]; AUX(xi.data(), k, S::A_EU) = 2 * nu * m0 / st(k)[S::O_TTR];
-                }
-                for (int i = 0; i < nic; i++) GAUX(xi.data(), S::GA_YIC + i) = typeA(GROW(a0.data(), S::G_IC0 + i), G()[S::Q_BW0 + i]);
-                for (int i = 0; i < ntc; i++) GAUX(xi.data(), S::GA_YTC + i) = typeA(GROW(a0.data(), S::G_TC0 + i), G()[S::Q_BWF + i]);
-                GAUX(xi.data(), S::GA_EP) = np > 0 ? 2 * np * m0 / P[o.scal + 0] : 0.0;
-            }
-            G_apply(xi.data(), gd.data());
-            for (long i = 0; i < ROWS; i++) s[i] = -(gd[i] + hneg[i]);
-            const double fl = std::sqrt(m0);
-            for (long i = 0; i < ROWS; i++) {
-                if (is_dead(i)) { s[i] = 1.0; lam[i] = 1.0; continue; }
-                if (is_soc(i)) continue;
-                if (opt.warm == 1) { s[i] = std::max(s[i], fl * 1e-3 + 0 * fl); s[i] = std::max(s[i], 1e-300); lam[i] = m0 / s[i]; }
-                else {
-                    double l = std::max(lam_prev[i], 1e-14);
-                    // slack pushed up to complementarity m0 with the old multiplier, but never beyond sqrt(m0): a row that was
-                    // inactive (multiplier ~ 0) keeps its own slack and gets the multiplier m0 / s instead -- pushing ITS slack to
-                    // m0 / l = 1e9 made the warm point wildly primal infeasible (relative residual 1e6) and 3 % of the warm solves
-                    // spend 45 iterations without a full step before the cold repeat
-                    double sv = std::max(s[i], std::min(m0 / l, fl));
-                    l = std::max(l, m0 / sv);
-                    s[i] = sv; lam[i] = l;
-                }
-            }
+        nrm_h = std::max(1.0, std::sqrt(nh)); nrm_c = std::max(1.0, std::sqrt(nc));
+    }
+    void reset_work()
+    {
+        for (auto* v : {&xi, &dxi, &rx, &exi, &rxe}) v->assign(XI, 0.0);
+        for (auto* v : {&s, &lam, &rz, &rtil, &ds, &dl, &gd, &r2, &el, &ge, &sn, &ln}) v->assign(ROWS, 0.0);
+        w.assign(ROWS, 1.0); nuv.assign((size_t)N * MNU, 0.0);
+    }
+
+    // ---- residuals and merit of the iterate (xi, s, lam): rx, rz, r~z = rz - s, the weights w = lam / s of the linear rows ----
+    struct Merit { double pcost, dcost, gap, pres, dres, relgap, merit; };
+    Merit residuals()
+    {
+        GT_apply(lam.data(), rx.data());
+        G_apply(xi.data(), gd.data());
+        double lrz = 0, nrz = 0, nrx = 0, pc = 0, gap = 0;
+        for (long i = 0; i < XI; i++) { const double r_ = rx[i] + qd[i] * xi[i] + cv[i]; rx[i] = r_; nrx += r_ * r_; pc += 0.5 * qd[i] * xi[i] * xi[i] + cv[i] * xi[i]; }
+        for (long i = 0; i < ROWS; i++) {
+            const bool lv = !is_dead(i);
+            const double val = lv ? gd[i] + s[i] + hneg[i] : 0.0;
+            rz[i] = val; rtil[i] = val - s[i];
+            w[i] = (lv && !is_soc(i)) ? lam[i] / s[i] : 1.0;
+            if (lv) { gap += s[i] * lam[i]; lrz += lam[i] * val; nrz += val * val; }
+        }
+        Merit m;
+        m.gap = gap; m.pcost = pc; m.dcost = m.pcost + lrz - gap;
+        m.pres = std::sqrt(nrz) / nrm_h; m.dres = std::sqrt(nrx) / nrm_c;
+        m.relgap = m.pcost < 0.0 ? gap / -m.pcost : (m.dcost > 0.0 ? gap / m.dcost : 1e300);
+        m.merit = std::max(std::max(m.pres / IpmOpts::feastol, m.dres / IpmOpts::feastol), std::min(gap / IpmOpts::abstol, m.relgap / IpmOpts::reltol));
+        return m;
+    }
+
+    // ---- snapshot refresh: level l takes the FIRST iterate of this run with lvl_mu[l] * lvl_floor <= mu <= lvl_mu[l].  A warm run
+    // (level >= 0) takes nothing at its starting point, only after a step on the NEW problem, and leaves the levels below its own alone.
+    void refresh_snapshots(int level, int it, double mu_it, bool* taken)
+    {
+        if (level >= 0 && it == 0) return;
+        for (int l = 0; l < IpmOpts::NL; l++)
+            if (!taken[l] && l >= level && mu_it <= IpmOpts::lvl_mu[l] && mu_it >= IpmOpts::lvl_mu[l] * IpmOpts::lvl_floor) { xi_sn[l] = xi; s_sn[l] = s; lam_sn[l] = lam; taken[l] = true; }
+    }
+
+    // ---- combined right-hand side of the corrector: r~z = rz - s + (sigma mu e - ds o dl) / lam, in the NT-scaled space for the cones ----
+    void combined_rhs(double sigma, double mu)
+    {
+        for (long i = 0; i < ROWS; i++) {
+            if (is_soc(i)) continue;
+            double val = rz[i] - s[i];
+            if (!is_dead(i)) val += (sigma * mu - ds[i] * dl[i]) / lam[i];
+            rtil[i] = val;
+        }
+        for (int k = 0; k < N; k++) for (int c = 0; c < nsoc; c++) {
+            const long b0 = (long)k * RS + S::R_SOC + 4 * c;
+            const double* Wv = &socW[((size_t)k * NSOC1 + c) * 36]; const double* Wi = Wv + 16; const double* lt = Wv + 32;
+            double u1[4], u2[4], dsv[4], uu[4];
+            for (int q = 0; q < 4; q++) { double a1 = 0, a2 = 0; for (int q2 = 0; q2 < 4; q2++) { a1 += Wi[q * 4 + q2] * ds[b0 + q2]; a2 += Wv[q * 4 + q2] * dl[b0 + q2]; } u1[q] = a1; u2[q] = a2; }
+            dsv[0] = sigma * mu - (lt[0] * lt[0] + lt[1] * lt[1] + lt[2] * lt[2] + lt[3] * lt[3]) - (u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2] + u1[3] * u2[3]);
+            for (int q = 1; q < 4; q++) dsv[q] = -2.0 * lt[0] * lt[q] - (u1[0] * u2[q] + u2[0] * u1[q]);
+            const double den = lt[0] * lt[0] - lt[1] * lt[1] - lt[2] * lt[2] - lt[3] * lt[3];
+            uu[0] = (lt[0] * dsv[0] - lt[1] * dsv[1] - lt[2] * dsv[2] - lt[3] * dsv[3]) / den;
+            for (int q = 1; q < 4; q++) uu[q] = (dsv[q] - uu[0] * lt[q]) / lt[0];
+            for (int q = 0; q < 4; q++) { double acc = 0; for (int q2 = 0; q2 < 4; q2++) acc += Wv[q * 4 + q2] * uu[q2]; rtil[b0 + q] = rz[b0 + q] + acc; }
+        }
+    }
+
+    // ---- Newton solve with refinement: (dxi, gd = G dxi, dl) for the right-hand sides (rtil, rx) on the current factorisation, then
+    // nref times the same solve for the residual of that direction, added to it ----
+    void newton_refined(int nref)
+    {
+        newton(w.data(), rtil.data(), rx.data(), dxi.data(), nuv.data());
+        finish(w.data(), rtil.data(), rx.data(), dxi.data(), nuv.data(), gd.data(), dl.data());
+        for (int rf = 1; rf <= nref; rf++) {
+            GT_apply(dl.data(), rxe.data());
+            for (long i = 0; i < XI; i++) rxe[i] = rxe[i] + qd[i] * dxi[i] + rx[i];
+            for (long i = 0; i < ROWS; i++) { if (is_soc(i)) continue; r2[i] = is_dead(i) ? 0.0 : rtil[i] + gd[i] - dl[i] / w[i]; }
             for (int k = 0; k < N; k++) for (int c = 0; c < nsoc; c++) {
                 const long b0 = (long)k * RS + S::R_SOC + 4 * c;
-                double ms = s[b0] - std::sqrt(s[b0 + 1] * s[b0 + 1] + s[b0 + 2] * s[b0 + 2] + s[b0 + 3] * s[b0 + 3]);
-                if (ms < fl) s[b0] += fl - ms;
-                if (opt.warm == 1) {
-                    const double det = s[b0] * s[b0] - s[b0 + 1] * s[b0 + 1] - s[b0 + 2] * s[b0 + 2] - s[b0 + 3] * s[b0 + 3];
-                    lam[b0] = m0 * s[b0] / det; for (int q = 1; q < 4; q++) lam[b0 + q] = -m0 * s[b0 + q] / det;
-                } else {
-                    for (int q = 0; q < 4; q++) lam[b0 + q] = lam_prev[b0 + q];
-                    double ml = lam[b0] - std::sqrt(lam[b0 + 1] * lam[b0 + 1] + lam[b0 + 2] * lam[b0 + 2] + lam[b0 + 3] * lam[b0 + 3]);
-                    if (ml < fl) lam[b0] += fl - ml;
-                }
+                const double* Wv = &socW[((size_t)k * NSOC1 + c) * 36];
+                double t1[4];
+                for (int q = 0; q < 4; q++) { double acc = 0; for (int q2 = 0; q2 < 4; q2++) acc += Wv[q * 4 + q2] * dl[b0 + q2]; t1[q] = acc; }
+                for (int rr = 0; rr < 4; rr++) { double acc = 0; for (int q = 0; q < 4; q++) acc += Wv[rr * 4 + q] * t1[q]; r2[b0 + rr] = rtil[b0 + rr] + gd[b0 + rr] - acc; }
+            }
+            newton(w.data(), r2.data(), rxe.data(), exi.data(), nuv.data());
+            finish(w.data(), r2.data(), rxe.data(), exi.data(), nuv.data(), ge.data(), el.data());
+            for (long i = 0; i < XI; i++) dxi[i] += exi[i];
+            for (long i = 0; i < ROWS; i++) { dl[i] += el[i]; gd[i] += ge[i]; }
+        }
+    }
+
+    // ---- initial point of a cold run (ECOS): two solves with weights 1 and cones W = I -- xi and s = -(G xi + h) from (r~z = -h,
+    // rx = 0), lam from (r~z = 0, rx = c) -- and s, lam shifted into the cone where they are outside ----
+    void initial_point()
+    {
+        for (long i = 0; i < ROWS; i++) { w[i] = 1.0; rtil[i] = hneg[i]; r2[i] = 0.0; }
+        for (long i = 0; i < XI; i++) { rx[i] = cv[i]; xi[i] = 0.0; rxe[i] = 0.0; }
+        for (int k = 0; k < N; k++) for (int c = 0; c < nsoc; c++) { double* Wm = &socW[((size_t)k * NSOC1 + c) * 36]; for (int q = 0; q < 16; q++) { Wm[q] = (q % 5 == 0) ? 1.0 : 0.0; Wm[16 + q] = Wm[q]; } for (int q = 0; q < 4; q++) Wm[32 + q] = 0.0; }
+    }
+    void initial_primal()
+    {
+        newton(w.data(), rtil.data(), rxe.data(), xi.data(), nuv.data());
+        finish(w.data(), rtil.data(), rxe.data(), xi.data(), nuv.data(), gd.data(), dl.data());
+        for (long i = 0; i < ROWS; i++) s[i] = -(gd[i] + hneg[i]);
+    }
+    void initial_dual()
+    {
+        newton(w.data(), r2.data(), rx.data(), dxi.data(), nuv.data());
+        finish(w.data(), r2.data(), rx.data(), dxi.data(), nuv.data(), ge.data(), el.data());
+        for (long i = 0; i < ROWS; i++) lam[i] = ge[i];
+        for (int r = 0; r < 2 * nx; r++) { ROW(lam.data(), N - 1, r) = 1.0; ROW(s.data(), N - 1, r) = 1.0; }
+        for (int pass = 0; pass < 2; pass++) {
+            double* v = pass == 0 ? s.data() : lam.data();
+            const double mm = min_margin(v);
+            if (mm <= 0.0) {
+                const double sh = 1.0 - mm;
+                for (long i = 0; i < ROWS; i++) { if (is_dead(i)) continue; if (!is_soc(i) || (((i % RS) - S::R_SOC) % 4 == 0)) v[i] += sh; }
             }
         }
-        for (it = it0; it <= opt.max_iter; it++) {
-            if (it < 0) {
-                for (long i = 0; i < ROWS; i++) { w[i] = 1.0; rtil[i] = hneg[i]; r2[i] = 0.0; }
-                for (long i = 0; i < XI; i++) { rx[i] = cv[i]; xi[i] = 0.0; rxe[i] = 0.0; }
-                for (int k = 0; k < N; k++) for (int c = 0; c < nsoc; c++) { double* Wm = &socW[((size_t)k * NSOC1 + c) * 36]; for (int q = 0; q < 16; q++) { Wm[q] = (q % 5 == 0) ? 1.0 : 0.0; Wm[16 + q] = Wm[q]; } for (int q = 0; q < 4; q++) Wm[32 + q] = 0.0; }
-            } else {
-                GT_apply(lam.data(), rx.data());
-                G_apply(xi.data(), gd.data());
-                double lrz = 0, nrz = 0, nrx = 0, pc = 0;
-                gap = 0;
-                for (long i = 0; i < XI; i++) { const double r_ = rx[i] + qd[i] * xi[i] + cv[i]; rx[i] = r_; nrx += r_ * r_; pc += 0.5 * qd[i] * xi[i] * xi[i] + cv[i] * xi[i]; }
-                for (long i = 0; i < ROWS; i++) {
-                    const bool lv = !is_dead(i);
-                    const double val = lv ? gd[i] + s[i] + hneg[i] : 0.0;
-                    rz[i] = val; rtil[i] = val - s[i];
-                    w[i] = (lv && !is_soc(i)) ? lam[i] / s[i] : 1.0;
-                    if (lv) { gap += s[i] * lam[i]; lrz += lam[i] * val; nrz += val * val; }
-                }
-                const bool snap_skip0 = it0 == 0 && it == 0;   // a warm solve refreshes its snapshots only after a step on the NEW problem
-                if (!snap_skip0)
-                if (opt.warm >= 3 && !snap_taken && gap / deg <= opt.warm_save_mu) { xi_snap = xi; s_snap = s; lam_snap = lam; snap_taken = true; }
-                if (!snap_skip0 && opt.warm == 5)
-                    for (int l = 0; l < IpmOpts::NL; l++)
-                        if (!sn_taken[l] && !(it0 == 0 && l < snap_level) && gap / deg <= opt.lvl_mu[l] && (!opt.cross || mu_prev_it > opt.lvl_mu[l]) && gap / deg >= opt.lvl_mu[l] * opt.lvl_floor) { xi_sn[l] = xi; s_sn[l] = s; lam_sn[l] = lam; sn_taken[l] = true; }
-                mu_prev_it = gap / deg;
-                if (!snap_skip0)
-                if (opt.warm == 4 && !snapA_taken && gap / deg <= opt.warm_save_mu_coarse) { xi_snapA = xi; s_snapA = s; lam_snapA = lam; snapA_taken = true; }
-                const double pcost = pc, dcost = pcost + lrz - gap;
-                const double pres = std::sqrt(nrz) / nrm_h, dres = std::sqrt(nrx) / nrm_c;
-                const double relgap = pcost < 0.0 ? gap / -pcost : (dcost > 0.0 ? gap / dcost : 1e300);
-                relgap_it = relgap;
-                const double merit = std::max(std::max(pres / opt.feastol, dres / opt.feastol), std::min(gap / opt.abstol, relgap / opt.reltol));
+    }
+
+    // ---- step: ds = -rz - G dxi and the largest step that keeps s + a ds and lam + a dl in the cone ----
+    double max_step()
+    {
+        double am_s = 1e300, am_l = 1e300;
+        for (long i = 0; i < ROWS; i++) {
+            const double d = -rz[i] - gd[i];
+            ds[i] = d;
+            if (is_dead(i) || is_soc(i)) continue;
+            if (d < 0.0) am_s = std::min(am_s, -s[i] / d);
+            if (dl[i] < 0.0) am_l = std::min(am_l, -lam[i] / dl[i]);
+        }
+        for (int k = 0; k < N; k++) for (int c = 0; c < nsoc; c++) { const long b0 = (long)k * RS + S::R_SOC + 4 * c; am_s = std::min(am_s, soc_step(&s[b0], &ds[b0])); am_l = std::min(am_l, soc_step(&lam[b0], &dl[b0])); }
+        return std::min(am_s, am_l);
+    }
+    // one step length for (xi, s, lam): step_frac of the way to the boundary, backed off while the new point is not strictly interior
+    void take_step(double am)
+    {
+        double alpha = std::min(1.0, IpmOpts::step_frac * am);
+        for (int bt = 0; bt < 60; bt++) {
+            for (long i = 0; i < ROWS; i++) { sn[i] = s[i] + alpha * ds[i]; ln[i] = lam[i] + alpha * dl[i]; }
+            for (int r = 0; r < 2 * nx; r++) { ROW(sn.data(), N - 1, r) = 1.0; ROW(ln.data(), N - 1, r) = 1.0; }
+            if (min_margin(sn.data()) > 0.0 && min_margin(ln.data()) > 0.0) break;
+            alpha *= 0.8;
+        }
+        s.swap(sn); lam.swap(ln);
+        for (long i = 0; i < XI; i++) xi[i] += alpha * dxi[i];
+    }
+
+    // ---- one run (oracle/ipm_struct.py::solve; the body of the device's attempt loop): from the snapshot of `level`, or cold (level < 0:
+    // iteration -1 builds the initial point through the same factor / solve path); robust: refinement on from the first iteration ----
+    IpmResult run(int level, bool robust, std::vector<double>& best)
+    {
+        const bool warm = level >= 0;
+        const double cost_const = P[o.scal + 1], ref_gap = robust ? 1e300 : IpmOpts::ref_gap;
+        reset_work();
+        best.assign(XI, 0.0);
+        IpmResult res, bestr;
+        double best_merit = 1e300; int best_it = 0;
+        double mu = 0, sigma = 0, relgap_it = 1e300;
+        bool taken[IpmOpts::NL] = {false, false, false, false};
+        // the well-centred intermediate iterate of the previous solve, as it is: the infeasible-start iteration absorbs the
+        // change of the problem data (residuals of the order of the reference deviation)
+        if (warm) { xi = xi_sn[level]; s = s_sn[level]; lam = lam_sn[level]; }
+        for (int it = warm ? 0 : -1; it <= IpmOpts::max_iter; it++) {
+            if (it < 0) initial_point();
+            else {
+                const Merit m = residuals();
+                refresh_snapshots(level, it, m.gap / deg, taken);
+                relgap_it = m.relgap;
                 res.iters = it;
-                if (std::isfinite(merit) && merit < best_merit) {
-                    // (progress for the stall rule: an improvement by at least the factor stall_rel -- experiment SCP_CPU_STALL_REL; 1 = any)
-                    if (merit < opt.stall_rel * prog_merit) { prog_merit = merit; prog_it = it; }
-                    best_merit = merit; best_it = it; best = xi;
-                    bestr.pcost = pcost + cost_const; bestr.dcost = dcost + cost_const; bestr.gap = gap; bestr.pres = pres; bestr.dres = dres; bestr.relgap = relgap;
+                if (std::isfinite(m.merit) && m.merit < best_merit) {
+                    best_merit = m.merit; best_it = it; best = xi;
+                    bestr.pcost = m.pcost + cost_const; bestr.dcost = m.dcost + cost_const; bestr.gap = m.gap; bestr.pres = m.pres; bestr.dres = m.dres; bestr.relgap = m.relgap;
                 }
-                if (std::getenv("SCP_CPU_TRACE")) std::fprintf(stderr, "  it %2d gap %.3e relgap %.2e pres %.2e dres %.2e mu %.2e sigma %.3f alpha %.4f\n", it, gap, relgap, pres, dres, gap / deg, sigma, trace_alpha);
-                if (!std::isfinite(merit)) { res.status = 3; break; }
-                if (merit <= 1.0) { res.status = 0; break; }
-                if (it == opt.max_iter) break;
-                if (it0 == 0 && it >= (opt.warm == 5 ? std::min(opt.warm_max_iter, opt.lvl_cap[snap_level]) : opt.warm_max_iter)) break;   // a warm start that has not converged by now is abandoned
-                if (best_merit <= 1e3 && it - (opt.stall_rel < 1.0 ? prog_it : best_it) >= opt.stall) break;
+                if (!std::isfinite(m.merit)) { res.status = 3; break; }
+                if (m.merit <= 1.0) { res.status = 0; break; }
+                if (it == IpmOpts::max_iter) break;
+                if (warm && it >= IpmOpts::lvl_cap[level]) break;   // a warm start that has not converged by now is abandoned
+                if (best_merit <= 1e3 && it - best_it >= IpmOpts::stall) break;
                 if (!nt_update(s.data(), lam.data())) { res.status = 3; break; }
-                mu = gap / deg;
+                mu = m.gap / deg;
             }
-            {   // experiment (SCP_CPU_REGESC): a factorisation that breaks down is repeated with 10x the static regularisation
-                bool fok = factor(w.data());
-                for (int tr = 0; !fok && tr < opt.reg_escalate; tr++) { opt.reg *= 10.0; fok = factor(w.data()); }
-                if (!fok) { res.status = 3; break; }
-            }
-            for (int phase = 0; phase < 2; phase++) {
-                if (it >= 0 && phase == 1) {
-                    for (long i = 0; i < ROWS; i++) {
-                        if (is_soc(i)) continue;
-                        double val = rz[i] - s[i];
-                        if (!is_dead(i)) val += (sigma * mu - ds[i] * dl[i]) / lam[i];
-                        rtil[i] = val;
-                    }
-                    for (int k = 0; k < N; k++) for (int c = 0; c < nsoc; c++) {
-                        const long b0 = (long)k * RS + S::R_SOC + 4 * c;
-                        const double* Wv = &socW[((size_t)k * NSOC1 + c) * 36]; const double* Wi = Wv + 16; const double* lt = Wv + 32;
-                        double u1[4], u2[4], dsv[4], uu[4];
-                        for (int q = 0; q < 4; q++) { double a1 = 0, a2 = 0; for (int q2 = 0; q2 < 4; q2++) { a1 += Wi[q * 4 + q2] * ds[b0 + q2]; a2 += Wv[q * 4 + q2] * dl[b0 + q2]; } u1[q] = a1; u2[q] = a2; }
-                        dsv[0] = sigma * mu - (lt[0] * lt[0] + lt[1] * lt[1] + lt[2] * lt[2] + lt[3] * lt[3]) - (u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2] + u1[3] * u2[3]);
-                        for (int q = 1; q < 4; q++) dsv[q] = -2.0 * lt[0] * lt[q] - (u1[0] * u2[q] + u2[0] * u1[q]);
-                        const double den = lt[0] * lt[0] - lt[1] * lt[1] - lt[2] * lt[2] - lt[3] * lt[3];
-                        uu[0] = (lt[0] * dsv[0] - lt[1] * dsv[1] - lt[2] * dsv[2] - lt[3] * dsv[3]) / den;
-                        for (int q = 1; q < 4; q++) uu[q] = (dsv[q] - uu[0] * lt[q]) / lt[0];
-                        for (int q = 0; q < 4; q++) { double acc = 0; for (int q2 = 0; q2 < 4; q2++) acc += Wv[q * 4 + q2] * uu[q2]; rtil[b0 + q] = rz[b0 + q] + acc; }
-                    }
-                }
-                int nref_eff = (it < 0 || !(relgap_it < opt.ref_gap)) ? 0 : opt.nref;
-                if (opt.ref_on_stall && it >= 0 && it - best_it >= opt.ref_on_stall) nref_eff = std::max(nref_eff, 1);   // experiment
-                if (opt.ref_corrector_only && phase == 0) nref_eff = 0;
-                for (int rf = 0; rf <= nref_eff; rf++) {
-                    double *rt_ = rtil.data(), *rx_ = rx.data(), *ox = dxi.data(), *og = gd.data(), *ol = dl.data();
-                    if (it < 0 && phase == 0) { rx_ = rxe.data(); ox = xi.data(); }
-                    if (it < 0 && phase == 1) { rt_ = r2.data(); og = ge.data(); ol = el.data(); }
-                    if (rf > 0) {
-                        GT_apply(dl.data(), rxe.data());
-                        for (long i = 0; i < XI; i++) rxe[i] = rxe[i] + qd[i] * dxi[i] + rx[i];
-                        for (long i = 0; i < ROWS; i++) { if (is_soc(i)) continue; r2[i] = is_dead(i) ? 0.0 : rtil[i] + gd[i] - dl[i] / w[i]; }
-                        for (int k = 0; k < N; k++) for (int c = 0; c < nsoc; c++) {
-                            const long b0 = (long)k * RS + S::R_SOC + 4 * c;
-                            const double* Wv = &socW[((size_t)k * NSOC1 + c) * 36];
-                            double t1[4];
-                            for (int q = 0; q < 4; q++) { double acc = 0; for (int q2 = 0; q2 < 4; q2++) acc += Wv[q * 4 + q2] * dl[b0 + q2]; t1[q] = acc; }
-                            for (int rr = 0; rr < 4; rr++) { double acc = 0; for (int q = 0; q < 4; q++) acc += Wv[rr * 4 + q] * t1[q]; r2[b0 + rr] = rtil[b0 + rr] + gd[b0 + rr] - acc; }
-                        }
-                        rt_ = r2.data(); rx_ = rxe.data(); ox = exi.data(); og = ge.data(); ol = el.data();
-                    }
-                    newton(w.data(), rt_, rx_, ox, nuv.data());
-                    finish(w.data(), rt_, rx_, ox, nuv.data(), og, ol);
-                    if (rf > 0) {
-                        for (long i = 0; i < XI; i++) dxi[i] += exi[i];
-                        for (long i = 0; i < ROWS; i++) { dl[i] += el[i]; gd[i] += ge[i]; }
-                    }
-                }
-                if (it < 0 && phase == 0) { for (long i = 0; i < ROWS; i++) s[i] = -(gd[i] + hneg[i]); }
-                else if (it < 0) {
-                    for (long i = 0; i < ROWS; i++) lam[i] = ge[i];
-                    for (int r = 0; r < 2 * nx; r++) { ROW(lam.data(), N - 1, r) = 1.0; ROW(s.data(), N - 1, r) = 1.0; }
-                    static const int init_mode = std::getenv("SCP_CPU_INIT") ? std::atoi(std::getenv("SCP_CPU_INIT")) : 0;
-                    auto add_e = [&](double* v, double sh) { for (long i = 0; i < ROWS; i++) { if (is_dead(i)) continue; if (!is_soc(i) || (((i % RS) - S::R_SOC) % 4 == 0)) v[i] += sh; } };
-                    if (init_mode == 0) {
-                    for (int pass = 0; pass < 2; pass++) {
-                        double* v = pass == 0 ? s.data() : lam.data();
-                        const double mm = min_margin(v);
-                        if (mm <= 0.0) {
-                            const double sh = 1.0 - mm;
-                            for (long i = 0; i < ROWS; i++) { if (is_dead(i)) continue; if (!is_soc(i) || (((i % RS) - S::R_SOC) % 4 == 0)) v[i] += sh; }
-                        }
-                    }
-                    } else {   // experiment: Mehrotra's starting point (shift by 1.5 x the violation, then by half the complementarity over the other's sum)
-                        const double ms = min_margin(s.data()), ml = min_margin(lam.data());
-                        add_e(s.data(), std::max(-1.5 * ms, 0.0)); add_e(lam.data(), std::max(-1.5 * ml, 0.0));
-                        double sl = 0.0, ss = 0.0, sm = 0.0;
-                        for (long i = 0; i < ROWS; i++) { if (is_dead(i)) continue; sl += s[i] * lam[i]; if (!is_soc(i) || (((i % RS) - S::R_SOC) % 4 == 0)) { ss += s[i]; sm += lam[i]; } }
-                        add_e(s.data(), 0.5 * sl / std::max(sm, 1e-300)); add_e(lam.data(), 0.5 * sl / std::max(ss, 1e-300));
-                        if (init_mode == 2) { const double m1 = min_margin(s.data()), m2 = min_margin(lam.data()); if (m1 < 1.0) add_e(s.data(), 1.0 - m1); if (m2 < 1.0) add_e(lam.data(), 1.0 - m2); }
-                    }
-                } else {
-                    double am_s = 1e300, am_l = 1e300;
-                    for (long i = 0; i < ROWS; i++) {
-                        const double d = -rz[i] - gd[i];
-                        ds[i] = d;
-                        if (is_dead(i) || is_soc(i)) continue;
-                        if (d < 0.0) am_s = std::min(am_s, -s[i] / d);
-                        if (dl[i] < 0.0) am_l = std::min(am_l, -lam[i] / dl[i]);
-                    }
-                    for (int k = 0; k < N; k++) for (int c = 0; c < nsoc; c++) { const long b0 = (long)k * RS + S::R_SOC + 4 * c; am_s = std::min(am_s, soc_step(&s[b0], &ds[b0])); am_l = std::min(am_l, soc_step(&lam[b0], &dl[b0])); }
-                    const double am = std::min(am_s, am_l);
-                    if (phase == 0) { const double a_aff = std::min(1.0, am); sigma = (1.0 - a_aff) * (1.0 - a_aff) * (1.0 - a_aff); }
-                    else {
-                        // experiment (SCP_CPU_GONDZIO = number of correctors): Gondzio's multiple centrality correctors on the linear rows --
-                        // aim at a longer step, move the complementarity products of the trial point that left [b_min, b_max] mu_t back to
-                        // the box with ONE more solve on the same factorisation (zero residual right-hand sides), keep it if the step grows
-                        static const int n_gondzio = std::getenv("SCP_CPU_GONDZIO") ? std::atoi(std::getenv("SCP_CPU_GONDZIO")) : 0;
-                        double am_cur = am;
-                        for (int gc = 0; gc < n_gondzio && am_cur < 1.0 / opt.step_frac; gc++) {
-                            const double a_t = std::min(1.0, opt.step_frac * am_cur * 1.0 + 0.1 + 0.08 * am_cur), mu_t = sigma * mu, bmin = 0.1, bmax = 10.0;
-                            std::vector<double> tcor(ROWS, 0.0), zx(XI, 0.0), cxi(XI), cgd(ROWS), cdl(ROWS);
-                            for (long i = 0; i < ROWS; i++) {
-                                if (is_dead(i) || is_soc(i)) continue;
-                                const double v = (s[i] + a_t * ds[i]) * (lam[i] + a_t * dl[i]);
-                                double t = v < bmin * mu_t ? bmin * mu_t - v : (v > bmax * mu_t ? bmax * mu_t - v : 0.0);
-                                if (t < -bmax * mu_t) t = -bmax * mu_t;
-                                tcor[i] = t / lam[i];
-                            }
-                            newton(w.data(), tcor.data(), zx.data(), cxi.data(), nuv.data());
-                            finish(w.data(), tcor.data(), zx.data(), cxi.data(), nuv.data(), cgd.data(), cdl.data());
-                            double as2 = 1e300, al2 = 1e300;
-                            std::vector<double> ds2(ROWS), dl2(ROWS);
-                            for (long i = 0; i < ROWS; i++) {
-                                ds2[i] = ds[i] - cgd[i]; dl2[i] = dl[i] + cdl[i];
-                                if (is_dead(i) || is_soc(i)) continue;
-                                if (ds2[i] < 0.0) as2 = std::min(as2, -s[i] / ds2[i]);
-                                if (dl2[i] < 0.0) al2 = std::min(al2, -lam[i] / dl2[i]);
-                            }
-                            for (int k = 0; k < N; k++) for (int c = 0; c < nsoc; c++) { const long b0 = (long)k * RS + S::R_SOC + 4 * c; as2 = std::min(as2, soc_step(&s[b0], &ds2[b0])); al2 = std::min(al2, soc_step(&lam[b0], &dl2[b0])); }
-                            const double am2 = std::min(as2, al2);
-                            gondzio_tried++;
-                            if (std::min(1.0, opt.step_frac * am2) >= 1.01 * std::min(1.0, opt.step_frac * am_cur)) {
-                                gondzio_kept++;
-                                for (long i = 0; i < ROWS; i++) { ds[i] = ds2[i]; dl[i] = dl2[i]; gd[i] += cgd[i]; }
-                                for (long i = 0; i < XI; i++) dxi[i] += cxi[i];
-                                am_cur = am2;
-                            } else break;
-                        }
-                        double alpha = std::min(1.0, opt.step_frac * am_cur);
-                        for (int bt = 0; bt < 60; bt++) {
-                            for (long i = 0; i < ROWS; i++) { sn[i] = s[i] + alpha * ds[i]; ln[i] = lam[i] + alpha * dl[i]; }
-                            for (int r = 0; r < 2 * nx; r++) { ROW(sn.data(), N - 1, r) = 1.0; ROW(ln.data(), N - 1, r) = 1.0; }
-                            bool ok = min_margin(sn.data()) > 0.0 && min_margin(ln.data()) > 0.0;
-                            if (ok && opt.cgamma > 0.0) {   // experiment: stay in the wide neighbourhood s_i lam_i >= cgamma * mu
-                                double g = 0.0, mp = 1e300;
-                                for (long i = 0; i < ROWS; i++) { if (is_dead(i)) continue; g += sn[i] * ln[i]; if (!is_soc(i)) mp = std::min(mp, sn[i] * ln[i]); }
-                                ok = mp >= opt.cgamma * g / deg;
-                            }
-                            if (ok) break;
-                            alpha *= 0.8;
-                        }
-                        s.swap(sn); lam.swap(ln); trace_alpha = alpha;
-                        for (long i = 0; i < XI; i++) xi[i] += alpha * dxi[i];
-                    }
-                }
-            }
+            // a factorisation that breaks down is repeated with 10x the static regularisation (kept for the rest of the subproblem)
+            bool fok = factor(w.data());
+            for (int tr = 0; !fok && tr < IpmOpts::reg_escalate; tr++) { reg *= 10.0; fok = factor(w.data()); }
+            if (!fok) { res.status = 3; break; }
+            if (it < 0) { initial_primal(); initial_dual(); continue; }
+            const int nref = relgap_it < ref_gap ? IpmOpts::nref : 0;
+            newton_refined(nref);                                   // predictor (affine direction)
+            const double a_aff = std::min(1.0, max_step());
+            sigma = (1.0 - a_aff) * (1.0 - a_aff) * (1.0 - a_aff);
+            combined_rhs(sigma, mu);
+            newton_refined(nref);                                   // corrector
+            take_step(max_step());
         }
         // ECOS "reduced tolerances" -> ALMOST_OPTIMAL (as the device solver)
         if (res.status != 0 && bestr.pres <= 1e-4 && bestr.dres <= 1e-4 && (bestr.gap <= 5e-5 || bestr.relgap <= 5e-5)) res.status = 1;
-        xi_prev = xi; lam_prev = lam;
-        // a warm solve that ended before it could refresh a snapshot (0 iterations on a converged reference) keeps the old one
-        const bool keep = it0 == 0 && !std::getenv("SCP_CPU_SNAP_NOKEEP");
-        if (opt.warm >= 3) snap_ok = snap_taken || (keep && snap_ok);
-        if (opt.warm == 4) snapA_ok = snapA_taken || (keep && snapA_ok);
-        if (opt.warm == 5) for (int l = 0; l < IpmOpts::NL; l++) { sn_new[l] = sn_taken[l]; sn_ok[l] = sn_taken[l] || ((keep || opt.cross) && it0 == 0 && sn_ok[l]); }
+        // a warm run that ended before it could refresh a snapshot (0 iterations on a converged reference) keeps the old one
+        for (int l = 0; l < IpmOpts::NL; l++) sn_ok[l] = taken[l] || (warm && sn_ok[l]);
         const int its = res.iters, stt = res.status;
         res = bestr; res.iters = its; res.status = stt;
         return res;
+    }
+
+    // ================ the subproblem: warm start and the repeats of a failed run (csrc/ipm2_run.hpp, `attempt`) ================
+    // level >= 0: start from that snapshot level (the caller passes only levels whose snapshot exists); level < 0: cold.
+    // attempt 0: warm start; 1: cold; 2: cold with the iterative refinement switched on from the first iteration.  A warm run that failed,
+    // or that ended at reduced accuracy with a primal / dual residual above the tolerance, is repeated cold (a cold ALMOST_OPTIMAL exit
+    // always has residuals at round-off: only the gap stalls); before that, a failed start from the very fine level is repeated from the
+    // next level (its snapshot is still there: a start at mu ~ 1e-10 never produces an iterate within two decades of 1e-8).  The
+    // iterations of all attempts are counted.
+    IpmResult solve(int level, std::vector<double>& best)
+    {
+        constexpr int NL = IpmOpts::NL;
+        setup();
+        reg = IpmOpts::reg;   // per subproblem, NOT per attempt: an escalation carries over into the repeats (device: reg_cur)
+        const bool next_ok = sn_ok[NL - 2];   // availability before the first attempt (device: snap_prev)
+        bool fell_back = false;
+        int iters_total = 0;
+        IpmResult r;
+        for (int attempt = level >= 0 ? 0 : 1; attempt < 3; attempt++) {
+            const bool warm = attempt == 0, robust = attempt == 2;
+            r = run(warm ? level : -1, robust, best);
+            iters_total += r.iters;
+            if (warm) {
+                if (!(r.status > 1 || (r.status == 1 && (r.pres > IpmOpts::feastol || r.dres > IpmOpts::feastol)))) break;
+                if (!fell_back && level == NL - 1 && next_ok) {
+                    fell_back = true; level = NL - 2; attempt = -1;
+                    sn_ok[NL - 2] = true;
+                }
+            } else if (r.status <= 1 || robust) break;
+        }
+        r.iters = iters_total;
+        return r;
     }
 };
 
@@ -1057,10 +992,11 @@ static void ptr_one(const double* par, int N, int Nsub, int iters, double wvc, d
         for (int k = 0; k < Mi; k++) for (int jj = 0; jj < M::npF; jj++) for (int i = 0; i < nx; i++) Fc[((size_t)k * npF + jj) * nx + i] = F[((size_t)k * npa + M::Fcol(jj)) * nx + i];
     };
     out->t_disc = out->t_form = out->t_solve = 0; out->ipm_iters = 0; out->ipm_status_worst = 0;
-    bool warm_ok = false;
+    // what the device keeps per problem between launches (IpmArgs status, cold_iters, prev_dev; the snapshots are in ipm)
+    bool warm_ok = false;      // the previous subproblem was solved (status <= ALMOST_OPTIMAL)
     int last_status = 0;
-    double prev_dev = 1e300;
-    int cold_iters = 0;
+    double prev_dev = 1e300;   // deviation of the previous solution from its reference
+    int cold_iters = 0;        // iterations of the last subproblem that started cold: warm starts pay only where cold solves are slow
     double t0 = now();
     disc();
     out->t_disc += now() - t0;
@@ -1074,84 +1010,15 @@ static void ptr_one(const double* par, int N, int Nsub, int iters, double wvc, d
         double t1 = now();
         out->t_form += t1 - t0;
         ipm.bind(slab.data(), N);
-        if (const char* e = std::getenv("SCP_CPU_WARM")) ipm.opt.warm = std::atoi(e);
-        if (const char* e = std::getenv("SCP_CPU_WARM_MU")) ipm.opt.warm_mu = std::atof(e);
-        if (const char* e = std::getenv("SCP_CPU_WARM_SAVE_MU")) ipm.opt.warm_save_mu = std::atof(e);
-        if (const char* e = std::getenv("SCP_CPU_STEPFRAC")) ipm.opt.step_frac = std::atof(e);
-        if (const char* e = std::getenv("SCP_CPU_STALL_REL")) ipm.opt.stall_rel = std::atof(e);
-        if (const char* e = std::getenv("SCP_CPU_CGAMMA")) ipm.opt.cgamma = std::atof(e);
-        if (const char* e = std::getenv("SCP_CPU_WARM_FROM")) ipm.opt.warm_from = std::atoi(e);
-        if (const char* e = std::getenv("SCP_CPU_WARM_MAXIT")) ipm.opt.warm_max_iter = std::atoi(e);
-        if (const char* e = std::getenv("SCP_CPU_NREF")) ipm.opt.nref = std::atoi(e);
-        if (const char* e = std::getenv("SCP_CPU_REFCORR")) ipm.opt.ref_corrector_only = std::atoi(e);
-        if (const char* e = std::getenv("SCP_CPU_REFSTALL")) ipm.opt.ref_on_stall = std::atoi(e);
-        if (const char* e = std::getenv("SCP_CPU_REFGAP")) ipm.opt.ref_gap = std::atof(e);
-        ipm.opt.reg = 1e-12;   // per solve; escalated x10 by a factorisation that breaks down (device: reg_cur)
-        if (const char* e = std::getenv("SCP_CPU_REG")) ipm.opt.reg = std::atof(e);
-        if (const char* e = std::getenv("SCP_CPU_REGESC")) ipm.opt.reg_escalate = std::atoi(e);
-        double warm_dev = ipm.opt.warm_dev;
-        if (const char* e = std::getenv("SCP_CPU_WARM_DEV")) warm_dev = std::atof(e);
-        int warm_min_cold = ipm.opt.warm_min_cold;
-        if (const char* e = std::getenv("SCP_CPU_WARM_MINCOLD")) warm_min_cold = std::atoi(e);
-        ipm.use_warm = ipm.opt.warm > 0 && it >= ipm.opt.warm_from && warm_ok && prev_dev <= warm_dev && cold_iters >= warm_min_cold;
-        if (const char* e = std::getenv("SCP_CPU_WARM_SAVE_MU_COARSE")) ipm.opt.warm_save_mu_coarse = std::atof(e);
-        if (ipm.opt.warm == 4) {   // two snapshot levels: the fine one for small reference deviations, the coarse one otherwise
-            ipm.snap_level = prev_dev <= warm_dev ? 1 : 0;
-            ipm.use_warm = it >= ipm.opt.warm_from && warm_ok && (ipm.snap_level == 1 ? ipm.snap_ok : (ipm.snapA_ok && cold_iters >= warm_min_cold));
-        }
-        if (ipm.opt.warm == 5) {
-            if (const char* e = std::getenv("SCP_CPU_LVL_MU")) std::sscanf(e, "%lf,%lf,%lf,%lf", &ipm.opt.lvl_mu[0], &ipm.opt.lvl_mu[1], &ipm.opt.lvl_mu[2], &ipm.opt.lvl_mu[3]);
-            if (const char* e = std::getenv("SCP_CPU_LVL_DEV")) std::sscanf(e, "%lf,%lf,%lf,%lf", &ipm.opt.lvl_dev[0], &ipm.opt.lvl_dev[1], &ipm.opt.lvl_dev[2], &ipm.opt.lvl_dev[3]);
-            if (const char* e = std::getenv("SCP_CPU_LVL_CAP")) std::sscanf(e, "%d,%d,%d,%d", &ipm.opt.lvl_cap[0], &ipm.opt.lvl_cap[1], &ipm.opt.lvl_cap[2], &ipm.opt.lvl_cap[3]);
-            if (const char* e = std::getenv("SCP_CPU_ALMOST_LVL")) ipm.opt.almost_lvl = std::atoi(e);
-            if (const char* e = std::getenv("SCP_CPU_CROSS")) ipm.opt.cross = std::atoi(e);
-            if (const char* e = std::getenv("SCP_CPU_LVL_FLOOR")) ipm.opt.lvl_floor = std::atof(e);
-            for (int l = 0; l < IpmOpts::NL; l++) ipm.sn_acc[l] = (ipm.sn_new[l] ? 0.0 : ipm.sn_acc[l]) + prev_dev;
-            for (int l = 0; l < IpmOpts::NL; l++) ipm.sn_ok_prev[l] = ipm.sn_ok[l];
-            int lvl = -1;
-            for (int l = (last_status == 1 ? ipm.opt.almost_lvl : IpmOpts::NL - 1); l >= 0; l--)
-                if ((ipm.opt.cross ? ipm.sn_acc[l] : prev_dev) <= ipm.opt.lvl_dev[l] && ipm.sn_ok[l] && (l > 0 || cold_iters >= warm_min_cold)) { lvl = l; break; }
-            ipm.snap_level = lvl < 0 ? 0 : lvl;
-            ipm.use_warm = it >= ipm.opt.warm_from && warm_ok && lvl >= 0;
-        }
-        if (std::getenv("SCP_CPU_COLD_STRUCT")) { ipm.opt.warm = 1; ipm.use_warm = true; }
-        const bool was_warm = ipm.use_warm;
-        IpmResult rr = ipm.solve(best);
-        // warm start failed, or ended at reduced accuracy with a primal / dual residual above the tolerance (a cold
-        // ALMOST_OPTIMAL exit always has residuals at round-off: only the gap stalls): cold restart, iterations of both counted
-        auto warm_failed = [&](const IpmResult& r_) { return r_.status > 1 || (r_.status == 1 && (r_.pres > ipm.opt.feastol || r_.dres > ipm.opt.feastol)); };
-        // round 6: a failed start from the very fine level is repeated from the next level (its snapshot is still there: a start at
-        // mu ~ 1e-10 never produces an iterate within two decades of 1e-8) before the cold repeat -- SCP_CPU_FALLBACK=0 goes cold at once
-        if (ipm.opt.warm == 5 && ipm.use_warm && ipm.snap_level == IpmOpts::NL - 1 && ipm.sn_ok_prev[IpmOpts::NL - 2] && warm_failed(rr) &&
-            !(std::getenv("SCP_CPU_FALLBACK") && std::atoi(std::getenv("SCP_CPU_FALLBACK")) == 0)) {
-            const int it_w = rr.iters;
-            ipm.snap_level = IpmOpts::NL - 2;
-            ipm.sn_ok[IpmOpts::NL - 2] = true;
-            rr = ipm.solve(best);
-            rr.iters += it_w;
-        }
-        if (ipm.use_warm && (rr.status > 1 || (rr.status == 1 && (rr.pres > ipm.opt.feastol || rr.dres > ipm.opt.feastol)))) {
-            const int it_w = rr.iters;
-            ipm.use_warm = false;
-            rr = ipm.solve(best);
-            rr.iters += it_w;
-        }
-        if (rr.status > 1) {   // cold solve failed: once more with the refinement on from the first iteration (device: attempt 2)
-            const int it_c = rr.iters;
-            const double rg = ipm.opt.ref_gap;
-            const int nr = ipm.opt.nref;
-            ipm.opt.ref_gap = 1e300; ipm.opt.nref = nr > 0 ? nr : 1;
-            ipm.use_warm = false;
-            rr = ipm.solve(best);
-            rr.iters += it_c;
-            ipm.opt.ref_gap = rg; ipm.opt.nref = nr;
-        }
-        if (std::getenv("SCP_CPU_ATTEMPTS"))     // diagnostic: which attempts a solve went through
-            std::fprintf(stderr, "ATT it %d warm %d level %d dev %.3e iters %d status %d snap %d%d\n", it, (int)was_warm, ipm.snap_level, prev_dev, rr.iters,
-                         rr.status, (int)ipm.snapA_ok, (int)ipm.snap_ok);
+        // snapshot level to start from: the finest whose deviation bound covers prev_dev and whose snapshot exists (rules: IpmOpts); -1 cold
+        int lvl = -1;
+        if (it >= IpmOpts::warm_from && warm_ok)
+            for (int l = (last_status == 1 ? IpmOpts::almost_lvl : IpmOpts::NL - 1); l >= 0; l--)
+                if (prev_dev <= IpmOpts::lvl_dev[l] && ipm.sn_ok[l] && (l > 0 || cold_iters >= IpmOpts::warm_min_cold)) { lvl = l; break; }
+        const IpmResult rr = ipm.solve(lvl, best);
         warm_ok = rr.status <= 1;
         last_status = rr.status;
-        if (!was_warm) cold_iters = rr.iters;   // iterations of the last COLD solve: warm starts pay only where cold solves are slow
+        if (lvl < 0) cold_iters = rr.iters;
         {   // deviation of this solution from its reference (scaled, inf-norm): solution_deviation, scp.jl:909-931 (q = Inf)
             double dx = 0.0, dpv = 0.0;
             for (int k = 0; k < N; k++) for (int j = 0; j < nx; j++) dx = std::max(dx, std::fabs(best[(size_t)k * nz + j] - slab[(size_t)k * S::SR + S::O_ZREF + j]));

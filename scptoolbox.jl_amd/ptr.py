@@ -60,7 +60,7 @@ class Parameters:
         # (include/scp_mi355x.h).  Once a PTR run has converged its reference moves by ~1e-8 and a solve restarts from the previous
         # solve's iterate at mu <= 1e-10: 1 ... 5 IPM iterations per launch instead of 9 ... 16 in the second half of a 15-iteration
         # run; the mid level saves ~10 iterations in the launch after the last large move.  Same optima (levels and bounds swept on
-        # the CPU twin -- oracle/cpu_ptr.cpp, SCP_CPU_LVL_MU / SCP_CPU_LVL_DEV -- then on the 4096 batch).
+        # the CPU twin, oracle/cpu_ptr.cpp -- the sweep switches are in its git history -- then on the 4096 batch).
         c.ipm_warm_mu = float(o.get("warm_mu", 1e-8))
         c.ipm_warm_mu_coarse = float(o.get("warm_mu_coarse", 1e-1))
         c.ipm_warm_dev = float(o.get("warm_dev", 1e-3))
