@@ -524,6 +524,18 @@ static int upload_traj(scp_problem* h, int B, const double* xd, const double* ud
     return SCP_OK;
 }
 
+// the opposite direction: the last solution (h->sol_*) or the reference (h->ref_*) and its defects; any pointer may be NULL
+static int download_traj(scp_problem* h, int B, bool from_sol, double* xd, double* ud, double* p, double* defect)
+{
+    const size_t nx = h->info.nx, nu = h->info.nu, np = h->npt, N = h->N, D = sizeof(double), b = B;
+    if (xd) HIP_TRY(h, hipMemcpyAsync(xd, from_sol ? h->sol_xd : h->ref_xd, nx * N * b * D, hipMemcpyDeviceToHost, h->stream));
+    if (ud) HIP_TRY(h, hipMemcpyAsync(ud, from_sol ? h->sol_ud : h->ref_ud, nu * N * b * D, hipMemcpyDeviceToHost, h->stream));
+    if (p && np > 0) HIP_TRY(h, hipMemcpyAsync(p, from_sol ? h->sol_p : h->ref_p, np * b * D, hipMemcpyDeviceToHost, h->stream));
+    if (defect)
+        HIP_TRY(h, hipMemcpyAsync(defect, (from_sol ? h->sol_dyn : h->ref_dyn).defect, nx * (N - 1) * b * D, hipMemcpyDeviceToHost, h->stream));
+    return SCP_OK;
+}
+
 static int feas_out(scp_problem* h, int B, const int* dfeas, uint8_t* feas)
 {
     std::vector<int> hf(B);
@@ -1084,14 +1096,11 @@ extern "C" int scp_ptr_get_host(scp_handle h, double* xd, double* ud, double* p,
 {
     if (!h || !h->run_ready || h->B < 1 || h->pars.iter_max > h->hist_cap) return SCP_ERR_BAD_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t nx = h->info.nx, nu = h->info.nu, np = h->npt, N = h->N, D = sizeof(double), b = h->B;
-    if (xd) HIP_TRY(h, hipMemcpyAsync(xd, h->sol_xd, nx * N * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (ud) HIP_TRY(h, hipMemcpyAsync(ud, h->sol_ud, nu * N * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (p && np > 0) HIP_TRY(h, hipMemcpyAsync(p, h->sol_p, np * b * D, hipMemcpyDeviceToHost, h->stream));
+    const size_t D = sizeof(double), b = h->B;
+    TRY(download_traj(h, h->B, true, xd, ud, p, defect));
     if (status) HIP_TRY(h, hipMemcpyAsync(status, h->scp_status, b * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (iterations) HIP_TRY(h, hipMemcpyAsync(iterations, h->iters_done, b * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (cost) HIP_TRY(h, hipMemcpyAsync(cost, h->cost, 4 * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (defect) HIP_TRY(h, hipMemcpyAsync(defect, h->sol_dyn.defect, nx * (N - 1) * b * D, hipMemcpyDeviceToHost, h->stream));
     if (hist) HIP_TRY(h, hipMemcpyAsync(hist, h->hist, (size_t)h->pars.iter_max * b * H_N * D, hipMemcpyDeviceToHost, h->stream));
     TRY(feas_out(h, h->B, h->d_feas, feas));
     return SCP_OK;
@@ -1142,16 +1151,13 @@ extern "C" int scp_ptr_solve_subproblem_batch_host(scp_handle h, int B, const sc
     TRY(subproblem_dev(h, B));
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     TRY(discretize_dev(h, B, h->sol_xd, h->sol_ud, h->sol_p, h->sol_dyn, h->d_feas_new, nullptr));
-    const size_t nx = h->info.nx, nu = h->info.nu, np = h->npt, N = h->N, D = sizeof(double), b = B;
-    if (x) HIP_TRY(h, hipMemcpyAsync(x, h->sol_xd, nx * N * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (u) HIP_TRY(h, hipMemcpyAsync(u, h->sol_ud, nu * N * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (p && np > 0) HIP_TRY(h, hipMemcpyAsync(p, h->sol_p, np * b * D, hipMemcpyDeviceToHost, h->stream));
+    const size_t N = h->N, D = sizeof(double), b = B;
+    TRY(download_traj(h, B, true, x, u, p, defect));
     if (cost) HIP_TRY(h, hipMemcpyAsync(cost, h->cost, 4 * b * D, hipMemcpyDeviceToHost, h->stream));
     if (eta) HIP_TRY(h, hipMemcpyAsync(eta, h->eta, (2 * N + 1) * b * D, hipMemcpyDeviceToHost, h->stream));
     if (solver_status) HIP_TRY(h, hipMemcpyAsync(solver_status, h->ipm_status, b * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (solver_iters) HIP_TRY(h, hipMemcpyAsync(solver_iters, h->ipm_iters, b * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (info) HIP_TRY(h, hipMemcpyAsync(info, h->ipm_info, 8 * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (defect) HIP_TRY(h, hipMemcpyAsync(defect, h->sol_dyn.defect, nx * (N - 1) * b * D, hipMemcpyDeviceToHost, h->stream));
     TRY(feas_out(h, B, h->d_feas_new, feas));
     if (seconds) {
         float ms = 0;

@@ -269,16 +269,19 @@ struct scp_sub {
     double* d_pp = nullptr;
     double* post = nullptr;  // [cap][4]
     std::vector<void*> allocs;
-    // outer-loop run state (SCvx: scvx.jl:459-540; GuSTO: gusto.jl:425-502)
-    scp_scvx_params sp{};
-    scp_gusto_params gp{};
-    bool scvx_ready = false, gusto_ready = false, ptr_ready = false;
-    scp_ptr_generic_params pp_{};
+    // outer-loop run state (SCvx: scvx.jl:459-540; GuSTO: gusto.jl:425-502; PTR: ptr.jl:448-532), set by the init that started
+    // the run (loop_begin); iterate and get_host of another loop refuse the handle
+    enum Loop { LOOP_NONE = 0, LOOP_SCVX, LOOP_GUSTO, LOOP_PTR } loop = LOOP_NONE;
+    scp::conic::Opts opts{};                  // subproblem solver options of the run
     double q_exit = std::numeric_limits<double>::infinity(), q_tr = std::numeric_limits<double>::infinity();   // norms of sub_post
     int B = 0, iter = 0, iter_max = 0, hist_cap = 0;
-    double* post2 = nullptr; // [cap][4] GuSTO: state penalty / lambda, dynamics error, its normalisation, max s
-    double *J_ref = nullptr, *hist = nullptr;   // [cap], [iter_max][cap][SCP_SCVX_HIST_WIDTH]
+    scp_scvx_params sp{};                     // the running loop's own parameters: its update kernel takes them by value
+    scp_gusto_params gp{};
+    scp_ptr_generic_params pg{};
+    double* post2 = nullptr; // [cap][4] GuSTO: state penalty / lambda, dynamics error, its normalisation, max s; PTR: cost split
+    double *J_ref = nullptr, *hist = nullptr;   // [2][cap] (reference, last solution), [iter_max][cap][SCP_SCVX_HIST_WIDTH]
     int *active = nullptr, *status = nullptr, *iters_done = nullptr, *n_active = nullptr;
+    int* accept = nullptr;   // [cap] ref <- sol of the last update (or of the guess projection)
     std::string err;
 };
 
@@ -288,6 +291,16 @@ struct scp_sub {
         if (e_ != hipSuccess) {                                                              \
             s->err = std::string(#call) + ": " + hipGetErrorString(e_);                      \
             return SCP_ERR_HIP;                                                              \
+        }                                                                                    \
+    } while (0)
+// a helper of the problem handle (upload_traj, discretize_dev, stamp_*, feas_out, ...) reports into h->err: the caller of a
+// scp_sub function reads s->err (scp_sub_last_error)
+#define SUB_CALL(call)                                                                       \
+    do {                                                                                     \
+        int rc_ = (call);                                                                    \
+        if (rc_ != SCP_OK) {                                                                 \
+            s->err = s->h->err;                                                              \
+            return rc_;                                                                      \
         }                                                                                    \
     } while (0)
 
@@ -472,10 +485,10 @@ static int sub_solve_dev(scp_sub* s, int B, const scp::conic::Opts& o, const int
         hipLaunchKernelGGL(scp::gen_gather_kernel, dim3((B + 63) / 64, (m.len + 3) / 4), dim3(256), 0, h->stream, g);
     }
     SUB_TRY(hipGetLastError());
-    TRY(stamp_begin(h, 2));
+    SUB_CALL(stamp_begin(h, 2));
     int rc = E.launch(h->stream, B, o, s->shared_mask, active);
     if (rc != SCP_OK) { s->err = E.err; return rc; }
-    TRY(stamp_end(h));
+    SUB_CALL(stamp_end(h));
     const int nx = h->info.nx, nu = h->info.nu, np = h->npt, N = h->N;
     auto ro = [&](const int* idx, int len, int dim, const double* S, const double* c, double* out) {
         if (len == 0) return;
@@ -493,7 +506,7 @@ static int sub_solve_dev(scp_sub* s, int B, const scp::conic::Opts& o, const int
         hipLaunchKernelGGL(scp::gen_gather_kernel, dim3((B + 63) / 64, (s->nfun + 3) / 4), dim3(256), 0, h->stream, g);
     }
     SUB_TRY(hipGetLastError());
-    TRY(discretize_dev(h, B, h->sol_xd, h->sol_ud, h->sol_p, h->sol_dyn, h->d_feas_new, active));
+    SUB_CALL(discretize_dev(h, B, h->sol_xd, h->sol_ud, h->sol_p, h->sol_dyn, h->d_feas_new, active));
     // d_feas keeps the flag of every problem's LAST solution (d_feas_new is only meaningful for the problems of this launch)
     hipLaunchKernelGGL(merge_feas_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, B, active, h->d_feas_new, h->d_feas);
     SUB_TRY(hipGetLastError());
@@ -540,23 +553,19 @@ extern "C" int scp_sub_solve_batch_host(scp_sub_handle s, int B, const double* x
     if (B > h->cap) { s->err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
     if ((h->npt > 0 && !p_ref) || (h->info.npp > 0 && !pp) || (s->nscal > 0 && !scal)) { s->err = "missing input"; return SCP_ERR_BAD_ARGUMENT; }
     SUB_TRY(hipSetDevice(h->device));
-    TRY(upload_traj(h, B, xd_ref, ud_ref, p_ref, h->ref_xd, h->ref_ud, h->ref_p));
+    SUB_CALL(upload_traj(h, B, xd_ref, ud_ref, p_ref, h->ref_xd, h->ref_ud, h->ref_p));
     if (h->info.npp > 0) SUB_TRY(hipMemcpyAsync(s->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
     SUB_TRY(hipEventRecord(h->ev0, h->stream));
-    TRY(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
+    SUB_CALL(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
     int rc;
     if ((rc = sub_fill_sources(s, B, nullptr)) != SCP_OK) return rc;
     if ((rc = sub_put_scal(s, B, scal)) != SCP_OK) return rc;
     if ((rc = sub_solve_dev(s, B, sub_opts(opts), nullptr)) != SCP_OK) return rc;
     SUB_TRY(hipEventRecord(h->ev1, h->stream));
-    const size_t nx = h->info.nx, nu = h->info.nu, np = h->npt, N = h->N, D = sizeof(double), b = B;
-    if (x) SUB_TRY(hipMemcpyAsync(x, h->sol_xd, nx * N * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (u) SUB_TRY(hipMemcpyAsync(u, h->sol_ud, nu * N * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (p && np > 0) SUB_TRY(hipMemcpyAsync(p, h->sol_p, np * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (defect) SUB_TRY(hipMemcpyAsync(defect, h->sol_dyn.defect, nx * (N - 1) * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (status) SUB_TRY(hipMemcpyAsync(status, s->eng.status, sizeof(int) * b, hipMemcpyDeviceToHost, h->stream));
-    if (iters) SUB_TRY(hipMemcpyAsync(iters, s->eng.iters, sizeof(int) * b, hipMemcpyDeviceToHost, h->stream));
-    TRY(feas_out(h, B, h->d_feas_new, feas));
+    SUB_CALL(download_traj(h, B, true, x, u, p, defect));
+    if (status) SUB_TRY(hipMemcpyAsync(status, s->eng.status, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+    if (iters) SUB_TRY(hipMemcpyAsync(iters, s->eng.iters, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+    SUB_CALL(feas_out(h, B, h->d_feas_new, feas));
     if ((rc = sub_get_il(s, B, s->funv, s->nfun, fun)) != SCP_OK) return rc;
     if ((rc = sub_get_il(s, B, s->eng.x, s->eng.sched.n, xconic)) != SCP_OK) return rc;
     if ((rc = sub_get_il(s, B, s->eng.info, 8, info)) != SCP_OK) return rc;
@@ -707,7 +716,10 @@ static int sub_loop_state(scp_sub* s, int iter_max)
         if ((rc = sub_alloc(s, &s->active, 4 * (size_t)h->cap + 1)) != SCP_OK) return rc;
         if ((rc = sub_alloc(s, &s->post2, 4 * (size_t)h->cap)) != SCP_OK) return rc;
         s->status = s->active + h->cap; s->iters_done = s->status + h->cap; s->n_active = s->iters_done + h->cap;
+        s->accept = s->n_active + 1;
     }
+    // one history buffer serves the three loops: SCvx and GuSTO records and the PTR record (the columns of scp_ptr_get_host)
+    static_assert(SCP_HIST_WIDTH == SCP_SCVX_HIST_WIDTH, "the loops share one history allocation, zeroing and read-back");
     if (s->hist_cap < iter_max) {
         if ((rc = sub_alloc(s, &s->hist, (size_t)iter_max * h->cap * SCP_SCVX_HIST_WIDTH)) != SCP_OK) return rc;
         s->hist_cap = iter_max;
@@ -715,76 +727,73 @@ static int sub_loop_state(scp_sub* s, int iter_max)
     return SCP_OK;
 }
 
-extern "C" int scp_scvx_init_host(scp_sub_handle s, scp_sub_handle proj, int B, const scp_scvx_params* pars, const double* xd,
-                                  const double* ud, const double* p, const double* pp)
+// What the three inits share: start a run of `loop` on s.  Uploads the guess and pp, clears the run state, projects the guess
+// onto the convex sets when `proj` is given (generate_initial_guess -> correct_convex!, scvx.jl:555-565, gusto.jl:516-521,
+// scp.jl:275-361) and discretises the reference.  The caller has checked s, pars, B >= 1, xd, ud and its own template; it
+// seeds its loop scalars behind this and ends with loop_begun.
+static int loop_begin(scp_sub* s, scp_sub* proj, scp_sub::Loop loop, int B, int iter_max, const scp_conic_opts& solver,
+                      double q_exit, double q_tr, const double* xd, const double* ud, const double* p, const double* pp)
 {
-    if (!s || !pars || B < 1 || !xd || !ud) return SCP_ERR_BAD_ARGUMENT;
     scp_problem* h = s->h;
     if (B > h->cap) { s->err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
     if ((h->npt > 0 && !p) || (h->info.npp > 0 && !pp)) { s->err = "missing input"; return SCP_ERR_BAD_ARGUMENT; }
-    if (pars->iter_max < 1 || s->nscal != 1 || s->nfun < 1) { s->err = "not an SCvx template (nscal = 1: eta, fun[0] = penalty)"; return SCP_ERR_BAD_ARGUMENT; }
     if (proj && proj->h != h) { s->err = "projection template belongs to another problem handle"; return SCP_ERR_BAD_ARGUMENT; }
     SUB_TRY(hipSetDevice(h->device));
     int rc;
-    if ((rc = sub_loop_state(s, pars->iter_max)) != SCP_OK) return rc;
-    if (!(pars->q_exit >= 1.0)) { s->err = "q_exit must be >= 1 (or Inf)"; return SCP_ERR_BAD_ARGUMENT; }
-    s->sp = *pars; s->B = B; s->iter = 0; s->iter_max = pars->iter_max; s->scvx_ready = true; s->gusto_ready = false; s->ptr_ready = false;
-    s->q_exit = pars->q_exit; s->q_tr = pars->q_exit;
-    TRY(upload_traj(h, B, xd, ud, p, h->ref_xd, h->ref_ud, h->ref_p));
+    if ((rc = sub_loop_state(s, iter_max)) != SCP_OK) return rc;
+    s->loop = loop; s->B = B; s->iter = 0; s->iter_max = iter_max; s->opts = sub_opts(&solver); s->q_exit = q_exit; s->q_tr = q_tr;
+    SUB_CALL(upload_traj(h, B, xd, ud, p, h->ref_xd, h->ref_ud, h->ref_p));
     if (h->info.npp > 0) {
         SUB_TRY(hipMemcpyAsync(s->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
         if (proj) SUB_TRY(hipMemcpyAsync(proj->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
     }
-    SUB_TRY(hipMemsetAsync(s->hist, 0, sizeof(double) * (size_t)pars->iter_max * B * SCP_SCVX_HIST_WIDTH, h->stream));
+    SUB_TRY(hipMemsetAsync(s->hist, 0, sizeof(double) * (size_t)iter_max * B * SCP_SCVX_HIST_WIDTH, h->stream));
     SUB_TRY(hipMemsetAsync(s->status, 0, sizeof(int) * (size_t)B, h->stream));
     SUB_TRY(hipMemsetAsync(s->iters_done, 0, sizeof(int) * (size_t)B, h->stream));
+    if (loop == scp_sub::LOOP_PTR) SUB_TRY(hipMemsetAsync(s->post2, 0, sizeof(double) * 4 * (size_t)B, h->stream));   // its cost[B][4]
     std::vector<int> ones(B, 1);
     SUB_TRY(hipMemcpyAsync(s->active, ones.data(), sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
     SUB_TRY(hipStreamSynchronize(h->stream));
-    // ---- generate_initial_guess (scvx.jl:555-565): correct_convex! projects the guess onto the convex sets ----
     if (proj) {
-        TRY(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
+        SUB_CALL(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
         if ((rc = sub_fill_sources(proj, B, nullptr)) != SCP_OK) { s->err = proj->err; return rc; }
-        if ((rc = sub_solve_dev(proj, B, sub_opts(&pars->solver), nullptr)) != SCP_OK) { s->err = proj->err; return rc; }
-        int* acc = s->active + 3 * (size_t)h->cap + 1;
+        if ((rc = sub_solve_dev(proj, B, s->opts, nullptr)) != SCP_OK) { s->err = proj->err; return rc; }
         hipLaunchKernelGGL(scp::proj_status_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, proj->eng.status, s->active,
-                           s->status, acc, B);
-        if ((rc = sub_masked_copy_all(s, B, acc, true)) != SCP_OK) return rc;   // x_ref .= value(opti.x) (scp.jl:346-349)
+                           s->status, s->accept, B);
+        if ((rc = sub_masked_copy_all(s, B, s->accept, true)) != SCP_OK) return rc;   // x_ref .= value(opti.x) (scp.jl:346-349)
     }
-    TRY(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
-    // nonlinear cost of the initial reference (solution_cost!(ref, :nonlinear), scvx.jl:724)
-    if ((rc = sub_post(s, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn.defect, nullptr)) != SCP_OK) return rc;
-    hipLaunchKernelGGL(scp::jref_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, s->post, pars->lam, s->J_ref, B);
-    hipLaunchKernelGGL(scp::fill_strided_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream,
-                       s->src + s->lay.off[scp::SEG_SCAL] * s->eng.BS, pars->eta_init, B);
+    SUB_CALL(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
+    return SCP_OK;
+}
+// the end of every init, behind the kernels that seed the loop scalars
+static int loop_begun(scp_sub* s)
+{
     SUB_TRY(hipGetLastError());
-    SUB_TRY(hipStreamSynchronize(h->stream));
-    stamps_collect(h);
+    SUB_TRY(hipStreamSynchronize(s->h->stream));
+    stamps_collect(s->h);
     return SCP_OK;
 }
 
-extern "C" int scp_scvx_iterate(scp_sub_handle s, int* n_active)
+// One iteration of `loop`: formulate + solve_subproblem! + discretize! + the costs of the new point for every active problem,
+// then update() -- the launch of the loop's own kernel(s): stopping rule, trust region, accept -- then ref = sol for the accepted
+// steps and the number of problems still active.
+template <class Update>
+static int loop_step(scp_sub* s, scp_sub::Loop loop, int* n_active, Update&& update)
 {
-    if (!s || !s->scvx_ready) return SCP_ERR_BAD_ARGUMENT;
+    if (!s || s->loop != loop) return SCP_ERR_BAD_ARGUMENT;
     scp_problem* h = s->h;
     SUB_TRY(hipSetDevice(h->device));
-    if (s->iter >= s->sp.iter_max) { if (n_active) *n_active = 0; return SCP_OK; }
+    if (s->iter >= s->iter_max) { if (n_active) *n_active = 0; return SCP_OK; }
     const int B = s->B;
     s->iter += 1;
     int rc;
-    int* acc = s->active + 3 * (size_t)h->cap + 1;
     SUB_TRY(hipMemsetAsync(s->n_active, 0, sizeof(int), h->stream));
     if ((rc = sub_fill_sources(s, B, s->active)) != SCP_OK) return rc;
-    if ((rc = sub_solve_dev(s, B, sub_opts(&s->sp.solver), s->active)) != SCP_OK) return rc;
+    if ((rc = sub_solve_dev(s, B, s->opts, s->active)) != SCP_OK) return rc;
     if ((rc = sub_post(s, B, h->sol_xd, h->sol_ud, h->sol_p, h->sol_dyn.defect, s->active)) != SCP_OK) return rc;
-    scp::ScvxUpdateArgs a;
-    a.B = B; a.iter = s->iter; a.BS = s->eng.BS; a.sp = s->sp; a.post = s->post; a.fun = s->funv; a.feas = h->d_feas_new;
-    a.ipm_status = s->eng.status; a.ipm_iters = s->eng.iters; a.J_ref = s->J_ref; a.J_last = s->J_ref + h->cap;
-    a.eta = s->src + s->lay.off[scp::SEG_SCAL] * s->eng.BS; a.active = s->active; a.accept = acc; a.scp_status = s->status;
-    a.iters_done = s->iters_done; a.hist = s->hist; a.n_active = s->n_active;
-    hipLaunchKernelGGL(scp::scvx_update_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, a);
+    if ((rc = update()) != SCP_OK) return rc;
     SUB_TRY(hipGetLastError());
-    if ((rc = sub_masked_copy_all(s, B, acc, true)) != SCP_OK) return rc;    // ref = sol for the accepted steps
+    if ((rc = sub_masked_copy_all(s, B, s->accept, true)) != SCP_OK) return rc;    // ref = sol for the accepted steps
     int na = 0;
     SUB_TRY(hipMemcpyAsync(&na, s->n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     SUB_TRY(hipStreamSynchronize(h->stream));
@@ -793,28 +802,64 @@ extern "C" int scp_scvx_iterate(scp_sub_handle s, int* n_active)
     return SCP_OK;
 }
 
-extern "C" int scp_scvx_get_host(scp_sub_handle s, double* xd, double* ud, double* p, int32_t* status, int32_t* iterations,
-                                 double* cost, uint8_t* feas, double* defect, double* hist)
+// The result of a run of `loop`.  cost (SCvx, GuSTO): [2][B] = J of the reference, J of the last solution.
+static int loop_get(scp_sub* s, scp_sub::Loop loop, double* xd, double* ud, double* p, int32_t* status, int32_t* iterations,
+                    double* cost, uint8_t* feas, double* defect, double* hist)
 {
-    if (!s || !(s->scvx_ready || s->gusto_ready || s->ptr_ready)) return SCP_ERR_BAD_ARGUMENT;
+    if (!s || s->loop != loop) return SCP_ERR_BAD_ARGUMENT;
     scp_problem* h = s->h;
     SUB_TRY(hipSetDevice(h->device));
-    const size_t nx = h->info.nx, nu = h->info.nu, np = h->npt, N = h->N, D = sizeof(double), b = s->B;
+    const size_t D = sizeof(double), b = s->B;
     // SCPSolution(history): the LAST subproblem's solution (scp.jl:196-245); before the first iteration: the reference
-    const bool none = s->iter == 0;
-    if (xd) SUB_TRY(hipMemcpyAsync(xd, none ? h->ref_xd : h->sol_xd, nx * N * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (ud) SUB_TRY(hipMemcpyAsync(ud, none ? h->ref_ud : h->sol_ud, nu * N * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (p && np > 0) SUB_TRY(hipMemcpyAsync(p, none ? h->ref_p : h->sol_p, np * b * D, hipMemcpyDeviceToHost, h->stream));
-    if (defect) SUB_TRY(hipMemcpyAsync(defect, none ? h->ref_dyn.defect : h->sol_dyn.defect, nx * (N - 1) * b * D, hipMemcpyDeviceToHost, h->stream));
+    SUB_CALL(download_traj(h, s->B, s->iter > 0, xd, ud, p, defect));
     if (status) SUB_TRY(hipMemcpyAsync(status, s->status, sizeof(int) * b, hipMemcpyDeviceToHost, h->stream));
     if (iterations) SUB_TRY(hipMemcpyAsync(iterations, s->iters_done, sizeof(int) * b, hipMemcpyDeviceToHost, h->stream));
     if (cost) {
-        SUB_TRY(hipMemcpyAsync(cost, s->J_ref, D * b, hipMemcpyDeviceToHost, h->stream));                  // J of the reference
-        SUB_TRY(hipMemcpyAsync(cost + b, s->J_ref + h->cap, D * b, hipMemcpyDeviceToHost, h->stream));     // J of the last solution
+        SUB_TRY(hipMemcpyAsync(cost, s->J_ref, D * b, hipMemcpyDeviceToHost, h->stream));
+        SUB_TRY(hipMemcpyAsync(cost + b, s->J_ref + h->cap, D * b, hipMemcpyDeviceToHost, h->stream));
     }
     if (hist) SUB_TRY(hipMemcpyAsync(hist, s->hist, D * (size_t)s->iter_max * b * SCP_SCVX_HIST_WIDTH, hipMemcpyDeviceToHost, h->stream));
-    TRY(feas_out(h, s->B, h->d_feas, feas));
+    SUB_CALL(feas_out(h, s->B, h->d_feas, feas));
     return SCP_OK;
+}
+
+extern "C" int scp_scvx_init_host(scp_sub_handle s, scp_sub_handle proj, int B, const scp_scvx_params* pars, const double* xd,
+                                  const double* ud, const double* p, const double* pp)
+{
+    if (!s || !pars || B < 1 || !xd || !ud) return SCP_ERR_BAD_ARGUMENT;
+    if (pars->iter_max < 1 || s->nscal != 1 || s->nfun < 1) { s->err = "not an SCvx template (nscal = 1: eta, fun[0] = penalty)"; return SCP_ERR_BAD_ARGUMENT; }
+    if (!(pars->q_exit >= 1.0)) { s->err = "q_exit must be >= 1 (or Inf)"; return SCP_ERR_BAD_ARGUMENT; }
+    int rc = loop_begin(s, proj, scp_sub::LOOP_SCVX, B, pars->iter_max, pars->solver, pars->q_exit, pars->q_exit, xd, ud, p, pp);
+    if (rc != SCP_OK) return rc;
+    s->sp = *pars;
+    scp_problem* h = s->h;
+    // nonlinear cost of the initial reference (solution_cost!(ref, :nonlinear), scvx.jl:724)
+    if ((rc = sub_post(s, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn.defect, nullptr)) != SCP_OK) return rc;
+    hipLaunchKernelGGL(scp::jref_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, s->post, pars->lam, s->J_ref, B);
+    hipLaunchKernelGGL(scp::fill_strided_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream,
+                       s->src + s->lay.off[scp::SEG_SCAL] * s->eng.BS, pars->eta_init, B);
+    return loop_begun(s);
+}
+
+extern "C" int scp_scvx_iterate(scp_sub_handle s, int* n_active)
+{
+    return loop_step(s, scp_sub::LOOP_SCVX, n_active, [&]() -> int {
+        scp_problem* h = s->h;
+        const int B = s->B;
+        scp::ScvxUpdateArgs a;
+        a.B = B; a.iter = s->iter; a.BS = s->eng.BS; a.sp = s->sp; a.post = s->post; a.fun = s->funv; a.feas = h->d_feas_new;
+        a.ipm_status = s->eng.status; a.ipm_iters = s->eng.iters; a.J_ref = s->J_ref; a.J_last = s->J_ref + h->cap;
+        a.eta = s->src + s->lay.off[scp::SEG_SCAL] * s->eng.BS; a.active = s->active; a.accept = s->accept; a.scp_status = s->status;
+        a.iters_done = s->iters_done; a.hist = s->hist; a.n_active = s->n_active;
+        hipLaunchKernelGGL(scp::scvx_update_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, a);
+        return (int)SCP_OK;
+    });
+}
+
+extern "C" int scp_scvx_get_host(scp_sub_handle s, double* xd, double* ud, double* p, int32_t* status, int32_t* iterations,
+                                 double* cost, uint8_t* feas, double* defect, double* hist)
+{
+    return loop_get(s, scp_sub::LOOP_SCVX, xd, ud, p, status, iterations, cost, feas, defect, hist);
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -990,13 +1035,10 @@ extern "C" int scp_gusto_init_host(scp_sub_handle s, scp_sub_handle proj, int B,
 {
     if (!s || !pars || B < 1 || !xd || !ud) return SCP_ERR_BAD_ARGUMENT;
     scp_problem* h = s->h;
-    if (B > h->cap) { s->err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
-    if ((h->npt > 0 && !p) || (h->info.npp > 0 && !pp)) { s->err = "missing input"; return SCP_ERR_BAD_ARGUMENT; }
     if (pars->iter_max < 1 || pars->nst < 0 || s->nscal != 2 || s->nfun != h->N * (1 + pars->nst)) {
         s->err = "not a GuSTO template (nscal = 2: eta, lambda; fun = v_tr[N], v_st[nst, N])";
         return SCP_ERR_BAD_ARGUMENT;
     }
-    if (proj && proj->h != h) { s->err = "projection template belongs to another problem handle"; return SCP_ERR_BAD_ARGUMENT; }
     {   // the solution costs (gusto_post_kernel) penalise exactly: the cone indicators of the model's convex state set X + its s rows
         int nq = 0, ok = 0;
         (void)with_model(h->model_id, [&](auto m) -> int {
@@ -1011,91 +1053,49 @@ extern "C" int scp_gusto_init_host(scp_sub_handle s, scp_sub_handle proj, int B,
             return SCP_ERR_UNSUPPORTED;
         }
     }
-    SUB_TRY(hipSetDevice(h->device));
-    int rc;
-    if ((rc = sub_loop_state(s, pars->iter_max)) != SCP_OK) return rc;
     if (!(pars->q_exit >= 1.0) || !(pars->q_tr >= 1.0)) { s->err = "q_exit and q_tr must be >= 1 (or Inf)"; return SCP_ERR_BAD_ARGUMENT; }
     if ((pars->pen != 0 && pars->pen != 1) || (pars->pen == 1 && !(pars->hom > 0.0))) { s->err = "pen must be 0 (:quad) or 1 (:softplus, hom > 0)"; return SCP_ERR_BAD_ARGUMENT; }
     if (pars->pen == 1 && s->eng.sched.nexp == 0) { s->err = "pen = :softplus needs a template with exponential cones"; return SCP_ERR_BAD_ARGUMENT; }
-    s->gp = *pars; s->B = B; s->iter = 0; s->iter_max = pars->iter_max; s->gusto_ready = true; s->scvx_ready = false; s->ptr_ready = false;
-    s->q_exit = pars->q_exit; s->q_tr = pars->q_tr;
-    TRY(upload_traj(h, B, xd, ud, p, h->ref_xd, h->ref_ud, h->ref_p));
-    if (h->info.npp > 0) {
-        SUB_TRY(hipMemcpyAsync(s->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
-        if (proj) SUB_TRY(hipMemcpyAsync(proj->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
-    }
-    SUB_TRY(hipMemsetAsync(s->hist, 0, sizeof(double) * (size_t)pars->iter_max * B * SCP_SCVX_HIST_WIDTH, h->stream));
-    SUB_TRY(hipMemsetAsync(s->status, 0, sizeof(int) * (size_t)B, h->stream));
-    SUB_TRY(hipMemsetAsync(s->iters_done, 0, sizeof(int) * (size_t)B, h->stream));
-    std::vector<int> ones(B, 1);
-    SUB_TRY(hipMemcpyAsync(s->active, ones.data(), sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    SUB_TRY(hipStreamSynchronize(h->stream));
-    if (proj) {   // generate_initial_guess, gusto.jl:516-521 -> correct_convex!, scp.jl:275-361
-        TRY(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
-        if ((rc = sub_fill_sources(proj, B, nullptr)) != SCP_OK) { s->err = proj->err; return rc; }
-        if ((rc = sub_solve_dev(proj, B, sub_opts(&pars->solver), nullptr)) != SCP_OK) { s->err = proj->err; return rc; }
-        int* acc = s->active + 3 * (size_t)h->cap + 1;
-        hipLaunchKernelGGL(scp::proj_status_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, proj->eng.status, s->active,
-                           s->status, acc, B);
-        if ((rc = sub_masked_copy_all(s, B, acc, true)) != SCP_OK) return rc;
-    }
-    TRY(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
+    int rc = loop_begin(s, proj, scp_sub::LOOP_GUSTO, B, pars->iter_max, pars->solver, pars->q_exit, pars->q_tr, xd, ud, p, pp);
+    if (rc != SCP_OK) return rc;
+    s->gp = *pars;
     double* scal = s->src + s->lay.off[scp::SEG_SCAL] * s->eng.BS;
     const dim3 g((B + 255) / 256), t(256);
     hipLaunchKernelGGL(scp::fill_nan_kernel, g, t, 0, h->stream, s->J_ref, B);           // ref.J_aug = NaN before the first solve
     hipLaunchKernelGGL(scp::fill_strided_kernel, g, t, 0, h->stream, scal, pars->eta_init, B);
     hipLaunchKernelGGL(scp::fill_strided_kernel, g, t, 0, h->stream, scal + s->eng.BS, pars->lam_init, B);
-    SUB_TRY(hipGetLastError());
-    SUB_TRY(hipStreamSynchronize(h->stream));
-    stamps_collect(h);
-    return SCP_OK;
+    return loop_begun(s);
 }
 
 extern "C" int scp_gusto_iterate(scp_sub_handle s, int* n_active)
 {
-    if (!s || !s->gusto_ready) return SCP_ERR_BAD_ARGUMENT;
-    scp_problem* h = s->h;
-    SUB_TRY(hipSetDevice(h->device));
-    if (s->iter >= s->gp.iter_max) { if (n_active) *n_active = 0; return SCP_OK; }
-    const int B = s->B;
-    s->iter += 1;
-    int rc;
-    int* acc = s->active + 3 * (size_t)h->cap + 1;
-    SUB_TRY(hipMemsetAsync(s->n_active, 0, sizeof(int), h->stream));
-    if ((rc = sub_fill_sources(s, B, s->active)) != SCP_OK) return rc;
-    if ((rc = sub_solve_dev(s, B, sub_opts(&s->gp.solver), s->active)) != SCP_OK) return rc;
-    if ((rc = sub_post(s, B, h->sol_xd, h->sol_ud, h->sol_p, h->sol_dyn.defect, s->active)) != SCP_OK) return rc;
-    scp::GustoPostArgs pa;
-    pa.B = B; pa.N = h->N; pa.xd = h->sol_xd; pa.ud = h->sol_ud; pa.p = h->sol_p; pa.rxd = h->ref_xd; pa.rud = h->ref_ud;
-    pa.rp = h->ref_p; pa.post2 = s->post2; pa.active = s->active; pa.pen = s->gp.pen; pa.hom = s->gp.hom;
-    rc = with_model(h->model_id, [&](auto m) -> int {
-        using M = decltype(m);
-        typename M::Params P = M::make_params(h->par.data());
-        hipLaunchKernelGGL(scp::gusto_post_kernel<M>, dim3(B), dim3(64), 0, h->stream, pa, P);
+    return loop_step(s, scp_sub::LOOP_GUSTO, n_active, [&]() -> int {
+        scp_problem* h = s->h;
+        const int B = s->B;
+        scp::GustoPostArgs pa;
+        pa.B = B; pa.N = h->N; pa.xd = h->sol_xd; pa.ud = h->sol_ud; pa.p = h->sol_p; pa.rxd = h->ref_xd; pa.rud = h->ref_ud;
+        pa.rp = h->ref_p; pa.post2 = s->post2; pa.active = s->active; pa.pen = s->gp.pen; pa.hom = s->gp.hom;
+        int rc = with_model(h->model_id, [&](auto m) -> int {
+            using M = decltype(m);
+            typename M::Params P = M::make_params(h->par.data());
+            hipLaunchKernelGGL(scp::gusto_post_kernel<M>, dim3(B), dim3(64), 0, h->stream, pa, P);
+            return (int)SCP_OK;
+        });
+        if (rc != SCP_OK) return rc;
+        scp::GustoUpdateArgs a;
+        a.B = B; a.iter = s->iter; a.N = h->N; a.nst = s->gp.nst; a.BS = s->eng.BS; a.gp = s->gp; a.post = s->post; a.post2 = s->post2;
+        a.fun = s->funv; a.feas = h->d_feas_new; a.ipm_status = s->eng.status; a.ipm_iters = s->eng.iters; a.J_ref = s->J_ref;
+        a.J_last = s->J_ref + h->cap; a.scal = s->src + s->lay.off[scp::SEG_SCAL] * s->eng.BS; a.active = s->active;
+        a.accept = s->accept; a.scp_status = s->status; a.iters_done = s->iters_done; a.hist = s->hist; a.n_active = s->n_active;
+        hipLaunchKernelGGL(scp::gusto_update_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, a);
         return (int)SCP_OK;
     });
-    if (rc != SCP_OK) return rc;
-    scp::GustoUpdateArgs a;
-    a.B = B; a.iter = s->iter; a.N = h->N; a.nst = s->gp.nst; a.BS = s->eng.BS; a.gp = s->gp; a.post = s->post; a.post2 = s->post2;
-    a.fun = s->funv; a.feas = h->d_feas_new; a.ipm_status = s->eng.status; a.ipm_iters = s->eng.iters; a.J_ref = s->J_ref;
-    a.J_last = s->J_ref + h->cap; a.scal = s->src + s->lay.off[scp::SEG_SCAL] * s->eng.BS; a.active = s->active; a.accept = acc;
-    a.scp_status = s->status; a.iters_done = s->iters_done; a.hist = s->hist; a.n_active = s->n_active;
-    hipLaunchKernelGGL(scp::gusto_update_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, a);
-    SUB_TRY(hipGetLastError());
-    if ((rc = sub_masked_copy_all(s, B, acc, true)) != SCP_OK) return rc;    // ref = sol for the accepted steps
-    int na = 0;
-    SUB_TRY(hipMemcpyAsync(&na, s->n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    SUB_TRY(hipStreamSynchronize(h->stream));
-    stamps_collect(h);
-    if (n_active) *n_active = na;
-    return SCP_OK;
 }
 
 extern "C" int scp_gusto_get_host(scp_sub_handle s, double* xd, double* ud, double* p, int32_t* status, int32_t* iterations,
                                   double* cost, uint8_t* feas, double* defect, double* hist)
 {
-    if (!s || !s->gusto_ready) return SCP_ERR_BAD_ARGUMENT;
-    return scp_scvx_get_host(s, xd, ud, p, status, iterations, cost, feas, defect, hist);
+    return loop_get(s, scp_sub::LOOP_GUSTO, xd, ud, p, status, iterations, cost, feas, defect, hist);
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -1161,75 +1161,40 @@ extern "C" int scp_ptr_generic_init_host(scp_sub_handle s, int B, const scp_ptr_
                                          const double* ud, const double* p, const double* pp)
 {
     if (!s || !pars || B < 1 || !xd || !ud) return SCP_ERR_BAD_ARGUMENT;
-    scp_problem* h = s->h;
-    if (B > h->cap) { s->err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
-    if ((h->npt > 0 && !p) || (h->info.npp > 0 && !pp)) { s->err = "missing input"; return SCP_ERR_BAD_ARGUMENT; }
     if (pars->iter_max < 1 || s->nscal > 1 || s->nfun < 2) { s->err = "not a PTR template (nscal <= 1 and unused, fun[0] = virtual-control penalty, fun[1] = trust-region penalty)"; return SCP_ERR_BAD_ARGUMENT; }
     if (!(pars->q_exit >= 1.0)) { s->err = "q_exit must be >= 1 (or Inf)"; return SCP_ERR_BAD_ARGUMENT; }
-    SUB_TRY(hipSetDevice(h->device));
-    int rc;
-    if ((rc = sub_loop_state(s, pars->iter_max)) != SCP_OK) return rc;
-    s->pp_ = *pars; s->B = B; s->iter = 0; s->iter_max = pars->iter_max; s->ptr_ready = true; s->scvx_ready = false; s->gusto_ready = false;
-    s->q_exit = pars->q_exit; s->q_tr = pars->q_exit;
-    TRY(upload_traj(h, B, xd, ud, p, h->ref_xd, h->ref_ud, h->ref_p));
-    if (h->info.npp > 0) SUB_TRY(hipMemcpyAsync(s->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
-    SUB_TRY(hipMemsetAsync(s->hist, 0, sizeof(double) * (size_t)pars->iter_max * B * SCP_HIST_WIDTH, h->stream));
-    SUB_TRY(hipMemsetAsync(s->status, 0, sizeof(int) * (size_t)B, h->stream));
-    SUB_TRY(hipMemsetAsync(s->iters_done, 0, sizeof(int) * (size_t)B, h->stream));
-    SUB_TRY(hipMemsetAsync(s->post2, 0, sizeof(double) * 4 * (size_t)B, h->stream));
-    std::vector<int> ones(B, 1);
-    SUB_TRY(hipMemcpyAsync(s->active, ones.data(), sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    SUB_TRY(hipStreamSynchronize(h->stream));
-    // generate_initial_guess: discretize!(guess) (ptr.jl:548-555); J_aug of the guess is NaN (ptr.jl:350)
-    TRY(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
-    hipLaunchKernelGGL(scp::fill_nan_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, s->J_ref, B);
-    SUB_TRY(hipGetLastError());
-    SUB_TRY(hipStreamSynchronize(h->stream));
-    stamps_collect(h);
-    return SCP_OK;
+    // generate_initial_guess: discretize!(guess) (ptr.jl:548-555)
+    int rc = loop_begin(s, nullptr, scp_sub::LOOP_PTR, B, pars->iter_max, pars->solver, pars->q_exit, pars->q_exit, xd, ud, p, pp);
+    if (rc != SCP_OK) return rc;
+    s->pg = *pars;
+    // J_aug of the guess is NaN (ptr.jl:350)
+    hipLaunchKernelGGL(scp::fill_nan_kernel, dim3((B + 255) / 256), dim3(256), 0, s->h->stream, s->J_ref, B);
+    return loop_begun(s);
 }
 
 extern "C" int scp_ptr_generic_iterate(scp_sub_handle s, int* n_active)
 {
-    if (!s || !s->ptr_ready) return SCP_ERR_BAD_ARGUMENT;
-    scp_problem* h = s->h;
-    SUB_TRY(hipSetDevice(h->device));
-    if (s->iter >= s->pp_.iter_max) { if (n_active) *n_active = 0; return SCP_OK; }
-    const int B = s->B;
-    s->iter += 1;
-    int rc;
-    int* acc = s->active + 3 * (size_t)h->cap + 1;
-    SUB_TRY(hipMemsetAsync(s->n_active, 0, sizeof(int), h->stream));
-    if ((rc = sub_fill_sources(s, B, s->active)) != SCP_OK) return rc;
-    if ((rc = sub_solve_dev(s, B, sub_opts(&s->pp_.solver), s->active)) != SCP_OK) return rc;
-    if ((rc = sub_post(s, B, h->sol_xd, h->sol_ud, h->sol_p, h->sol_dyn.defect, s->active)) != SCP_OK) return rc;
-    scp::PtrgUpdateArgs a;
-    a.B = B; a.iter = s->iter; a.BS = s->eng.BS; a.pp = s->pp_; a.post = s->post; a.fun = s->funv; a.info = s->eng.info;
-    a.feas = h->d_feas_new; a.ipm_status = s->eng.status; a.ipm_iters = s->eng.iters; a.J_ref = s->J_ref; a.cost = s->post2;
-    a.active = s->active; a.accept = acc; a.scp_status = s->status; a.iters_done = s->iters_done; a.hist = s->hist;
-    a.n_active = s->n_active;
-    hipLaunchKernelGGL(scp::ptrg_update_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, a);
-    SUB_TRY(hipGetLastError());
-    if ((rc = sub_masked_copy_all(s, B, acc, true)) != SCP_OK) return rc;    // ref = spbm.sol (ptr.jl:509)
-    int na = 0;
-    SUB_TRY(hipMemcpyAsync(&na, s->n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    SUB_TRY(hipStreamSynchronize(h->stream));
-    stamps_collect(h);
-    if (n_active) *n_active = na;
-    return SCP_OK;
+    return loop_step(s, scp_sub::LOOP_PTR, n_active, [&]() -> int {
+        scp_problem* h = s->h;
+        const int B = s->B;
+        scp::PtrgUpdateArgs a;
+        a.B = B; a.iter = s->iter; a.BS = s->eng.BS; a.pp = s->pg; a.post = s->post; a.fun = s->funv; a.info = s->eng.info;
+        a.feas = h->d_feas_new; a.ipm_status = s->eng.status; a.ipm_iters = s->eng.iters; a.J_ref = s->J_ref; a.cost = s->post2;
+        a.active = s->active; a.accept = s->accept; a.scp_status = s->status; a.iters_done = s->iters_done; a.hist = s->hist;
+        a.n_active = s->n_active;
+        hipLaunchKernelGGL(scp::ptrg_update_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, a);
+        return (int)SCP_OK;
+    });
 }
 
 extern "C" int scp_ptr_generic_get_host(scp_sub_handle s, double* xd, double* ud, double* p, int32_t* status, int32_t* iterations,
                                         double* cost, uint8_t* feas, double* defect, double* hist)
 {
-    if (!s || !s->ptr_ready) return SCP_ERR_BAD_ARGUMENT;
-    scp_problem* h = s->h;
-    SUB_TRY(hipSetDevice(h->device));
-    int rc = scp_scvx_get_host(s, xd, ud, p, status, iterations, nullptr, feas, defect, hist);
+    int rc = loop_get(s, scp_sub::LOOP_PTR, xd, ud, p, status, iterations, nullptr, feas, defect, hist);
     if (rc != SCP_OK) return rc;
-    if (cost) {
-        SUB_TRY(hipMemcpyAsync(cost, s->post2, sizeof(double) * 4 * (size_t)s->B, hipMemcpyDeviceToHost, h->stream));
-        SUB_TRY(hipStreamSynchronize(h->stream));
+    if (cost) {   // [B][4]: J, J_tr, J_vc, J_aug of the last subproblem
+        SUB_TRY(hipMemcpyAsync(cost, s->post2, sizeof(double) * 4 * (size_t)s->B, hipMemcpyDeviceToHost, s->h->stream));
+        SUB_TRY(hipStreamSynchronize(s->h->stream));
     }
     return SCP_OK;
 }

@@ -5,11 +5,13 @@ affine value maps and read-out indices are uploaded, and every `solve` is discre
 conic_ipm_kernel -> read-out -> discretize! on the MI355X (scp_sub_solve_batch_host).  The reference does the same work
 per iteration and per problem in Julia/JuMP + ECOS (src/solvers/scp.jl:942-950 and the add_*! functions)."""
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import _lib
 from .conic import default_options
+from .scp import SCPProblem
 from .subproblem import trapz_weights
 
 
@@ -162,3 +164,70 @@ class GenericSubproblem:
                 if name in self.T.variables:
                     out[name] = xc[:, self.T.variables[name]]
         return out
+
+
+# ---- what the device-resident outer loops (SCvx, GuSTO, PTR on the generic path; csrc/scp_generic.hpp) share on the host ----
+class LoopProblem(SCPProblem):
+    """An SCPProblem that owns its subproblem template `sub` and its guess projection `proj` (SCvx, GuSTO)."""
+
+    def close(self):
+        for s in ("sub", "proj"):
+            if getattr(self, s, None) is not None:
+                getattr(self, s).close()
+                setattr(self, s, None)
+        super().close()
+
+
+def stack_guesses(pbm, pp, guess=None):
+    """The initial guess of every instance as contiguous arrays xd[B,N,nx], ud[B,N,nu], p[B,np]: `guess` = (xd, ud, p) of the
+    caller, or traj.guess per instance."""
+    if guess is None:
+        g = [pbm.traj.guess(pbm.pars.N, pp[b]) for b in range(pp.shape[0])]
+        guess = [np.stack([gi[j] for gi in g]) for j in range(3)]
+    return tuple(np.ascontiguousarray(a, np.float64) for a in guess)
+
+
+def run_loop(pbm, sub, fns, head, guess, pp, cost_shape, hist_width, all_reduce=None):
+    """One run of a device-resident loop on `sub`: fns = its (init, iterate, get_host) of the C ABI; `head` = the arguments of
+    init between the handle and the guess (projection handle, B, parameter struct).  all_reduce: n -> global n (the
+    per-iteration convergence all-reduce of a batch sharded over GPUs, dist.py; identity on one GPU).  Returns every output of
+    get_host: xd, ud, p, status, iterations, cost[cost_shape], feas, defect, hist[iter_max, B, hist_width]."""
+    init, iterate, get_host = fns
+    xd, ud, p = guess
+    B, N, iter_max = pp.shape[0], pbm.pars.N, pbm.pars.iter_max
+    sub._check(init(sub._h, *head, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np else None, _ptr(pp) if pbm.info.npp else None))
+    na = ctypes.c_int(1)
+    k, n = 0, 1
+    while k < iter_max and n > 0:
+        sub._check(iterate(sub._h, ctypes.byref(na)))
+        n = na.value if all_reduce is None else all_reduce(na.value)
+        k += 1
+    r = SimpleNamespace(xd=np.zeros((B, N, pbm.nx)), ud=np.zeros((B, N, pbm.nu)), p=np.zeros((B, pbm.np)),
+                        status=np.zeros(B, np.int32), iterations=np.zeros(B, np.int32), cost=np.zeros(cost_shape),
+                        feas=np.zeros(B, np.uint8), defect=np.zeros((B, N - 1, pbm.nx)), hist=np.zeros((iter_max, B, hist_width)))
+    sub._check(get_host(sub._h, _ptr(r.xd), _ptr(r.ud), _ptr(r.p) if pbm.np else None, _ptr(r.status), _ptr(r.iterations),
+                        _ptr(r.cost), _ptr(r.feas), _ptr(r.defect), _ptr(r.hist)))
+    r.feas = r.feas.astype(bool)
+    return r
+
+
+class SCPSolutionBatch:
+    """Batched `SCPSolution` of SCvx and GuSTO from the outputs of run_loop (cost[2, B] = J of the reference, J of the last
+    solution: the nonlinear augmented cost, sol.J_aug)."""
+    STATUS = {0: "SCP_SOLVED", 1: "SCP_FAILED", 2: "SCP_GUESS_PROJECTION_FAILED"}
+
+    def __init__(self, r):
+        self.xd, self.ud, self.p, self.defect = r.xd, r.ud, r.p, r.defect
+        self.status = [self.STATUS[int(v)] for v in r.status]
+        self.iterations, self.feas = r.iterations, r.feas
+        self.J_ref, self.cost = r.cost[0], r.cost[1]
+
+
+def solve_projected(pbm, fns, cp, pp, guess, project_guess, all_reduce, h_names):
+    """`solve` of SCvx and GuSTO: the guess is projected onto the convex sets first (pbm.proj) unless project_guess=False.
+    Returns (SCPSolutionBatch, history by column name)."""
+    pp = np.ascontiguousarray(np.atleast_2d(pbm.traj.mdl.nominal_pp() if pp is None else pp), np.float64)
+    B = pp.shape[0]
+    r = run_loop(pbm, pbm.sub, fns, (pbm.proj._h if project_guess else None, B, ctypes.byref(cp)), stack_guesses(pbm, pp, guess),
+                 pp, (2, B), _lib.SCVX_HIST_WIDTH, all_reduce)
+    return SCPSolutionBatch(r), {nm: r.hist[:, :, j] for j, nm in enumerate(h_names)}

@@ -9,7 +9,10 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
+from .conic import default_options
+from .generic import GenericSubproblem, run_loop, stack_guesses
 from .scp import FOH, SCPProblem
+from .subproblem import ModelRows, build_ptr
 
 SOLVER_STATUS = {0: "OPTIMAL", 1: "ALMOST_OPTIMAL", 2: "ITERATION_LIMIT", 3: "NUMERICAL_ERROR"}
 
@@ -118,15 +121,6 @@ def _vp(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
 
 
-def _guess_batch(pbm, pp):
-    xs, us, ps = [], [], []
-    for b in range(pp.shape[0]):
-        x, u, p = pbm.traj.guess(pbm.pars.N, pp[b])
-        xs.append(x); us.append(u); ps.append(p)
-    return (np.ascontiguousarray(np.stack(xs)), np.ascontiguousarray(np.stack(us)),
-            np.ascontiguousarray(np.stack(ps).reshape(pp.shape[0], -1)))
-
-
 def solve(pbm, pp=None, warm=None, all_reduce=None, device_guess=False):
     """`PTR.solve(pbm[, warm])` (src/solvers/ptr.jl:448-532) for a batch.
 
@@ -160,8 +154,6 @@ def _qnorm(v, q):
 
 def _generic_sub(pbm):
     """the PTR subproblem of this problem as a conic template bound to the device (built once per SCPProblem)"""
-    from .generic import GenericSubproblem
-    from .subproblem import ModelRows, build_ptr
     if getattr(pbm, "_generic_sub", None) is None:
         pars = pbm.pars
         T = build_ptr(ModelRows(pbm.traj.mdl), pars.N, pbm.scale, pars.wvc, pars.wtr, pars.q_tr)
@@ -193,32 +185,19 @@ def _solve_generic(pbm, pp, warm=None, all_reduce=None):
     """PTR loop (ptr.jl:448-532) on the generic subproblem pipeline, RESIDENT on the device (scp_ptr_generic_*): every
     iteration is discretize! + formulate + conic solve + discretize! + the cost split, the stopping rule (ptr.jl:908-932,
     solution_deviation scp.jl:909-931 in the q_exit norm) and ref = sol; only the active count comes back per iteration."""
-    from .conic import default_options
     pars = pbm.pars
     if not pars.q_exit >= 1:
         raise _lib.ScpError(1, "q_exit must be >= 1 or Inf")
     L = _lib.lib()
     sub = _generic_sub(pbm)
     B = pp.shape[0]
-    xd, ud, p = _guess_batch(pbm, pp) if warm is None else [np.ascontiguousarray(a, dtype=np.float64) for a in warm]
     cp = _lib.ScpPtrGenericParams()
     cp.iter_max, cp.wvc, cp.wtr, cp.eps_abs, cp.eps_rel, cp.q_exit = pars.iter_max, pars.wvc, pars.wtr, pars.eps_abs, pars.eps_rel, pars.q_exit
     cp.cost_const = sub.T.cost_const
     cp.solver = default_options(**generic_solver_options(pars.solver_opts))
-    sub._check(L.scp_ptr_generic_init_host(sub._h, B, ctypes.byref(cp), _vp(xd), _vp(ud), _vp(p) if pbm.np else None,
-                                           _vp(pp) if pbm.info.npp else None))
-    na = ctypes.c_int(1)
-    k, n = 0, 1
-    while k < pars.iter_max and n > 0:
-        sub._check(L.scp_ptr_generic_iterate(sub._h, ctypes.byref(na)))
-        n = na.value if all_reduce is None else all_reduce(na.value)
-        k += 1
-    N = pars.N
-    x = np.zeros((B, N, pbm.nx)); u = np.zeros((B, N, pbm.nu)); po = np.zeros((B, pbm.np))
-    status = np.zeros(B, np.int32); iters = np.zeros(B, np.int32); cost = np.zeros((B, 4)); feas = np.zeros(B, np.uint8)
-    defect = np.zeros((B, N - 1, pbm.nx)); hist = np.zeros((pars.iter_max, B, _lib.HIST_WIDTH))
-    sub._check(L.scp_ptr_generic_get_host(sub._h, _vp(x), _vp(u), _vp(po) if pbm.np else None, _vp(status), _vp(iters), _vp(cost),
-                                          _vp(feas), _vp(defect), _vp(hist)))
+    r = run_loop(pbm, sub, (L.scp_ptr_generic_init_host, L.scp_ptr_generic_iterate, L.scp_ptr_generic_get_host),
+                 (B, ctypes.byref(cp)), stack_guesses(pbm, pp, warm), pp, (B, 4), _lib.HIST_WIDTH, all_reduce)
+    hist, iters, status, cost = r.hist, r.iterations, r.status, r.cost
     keys = ("J", "J_tr", "J_vc", "J_aug", "deviation", "improv_rel", "feas", "solver_status", "solver_iters", "active", "gap",
             "pres", "dres")
     H = {kk: hist[:, :, j] for j, kk in enumerate(keys)}
@@ -226,8 +205,8 @@ def _solve_generic(pbm, pp, warm=None, all_reduce=None):
     failed = status != 0
     st = ["SCP_FAILED (%s)" % SOLVER_STATUS.get(int(last_st[b]), "?") if failed[b] else "SCP_SOLVED" for b in range(B)]
     sol = SCPSolutionBatch(status=st, algo="PTR (backend: MI355X generic conic IPM)", iterations=iters,
-                           cost=np.where(failed, math.inf, cost[:, 3]), J=cost[:, 0].copy(), td=pbm.t_grid.copy(), xd=x, ud=u, p=po,
-                           J_aug=cost[:, 3].copy(), feas=feas.astype(bool), defect=defect)
+                           cost=np.where(failed, math.inf, cost[:, 3]), J=cost[:, 0].copy(), td=pbm.t_grid.copy(), xd=r.xd, ud=r.ud, p=r.p,
+                           J_aug=cost[:, 3].copy(), feas=r.feas, defect=r.defect)
     hb = SCPHistoryBatch(**{kk: (H[kk] > 0 if kk in ("feas", "active") else (H[kk].astype(int) if kk.startswith("solver_") else H[kk]))
                             for kk in keys})
     return sol, hb
@@ -244,7 +223,7 @@ def upload(pbm, pp=None, warm=None, device_guess=False):
         cp = pbm.pars.c_struct()
         _lib.check(L.scp_ptr_init_guess_host(pbm.handle, B, ctypes.byref(cp), _vp(pp)), pbm.handle)
         return B
-    xd, ud, p = _guess_batch(pbm, pp) if warm is None else [np.ascontiguousarray(a, dtype=np.float64) for a in warm]
+    xd, ud, p = stack_guesses(pbm, pp, warm)
     cp = pbm.pars.c_struct()
     _lib.check(L.scp_ptr_init_host(pbm.handle, B, ctypes.byref(cp), _vp(xd), _vp(ud), _vp(p) if pbm.np else None,
                                    _vp(pp)), pbm.handle)
