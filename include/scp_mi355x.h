@@ -177,7 +177,8 @@ int scp_set_stream_priority(scp_handle h, int level);
  *   (only the npF structurally non-zero columns, in Fcols order),
  *   r[nx,N-1,B], E[nx,nx,N-1,B], defect[nx,N-1,B], feas[B] (ref.feas),
  *   *seconds = device time of the call (ref.dyn.timing, :162,:214).
- * Any output pointer may be NULL to skip the copy-out (host variant).
+ * Any output pointer may be NULL to skip the copy-out (host variant).  The call stages its input in the handle's solution
+ * buffers: during a run it overwrites the last solution that run's get_host returns.
  */
 int scp_discretize_batch_host(scp_handle h, int B, const double *xd, const double *ud, const double *p,
                               double *A, double *Bm, double *Bp, double *F, double *r, double *E,
@@ -205,6 +206,7 @@ int scp_discretize_batch_dev(scp_handle h, int B, const double *xd, const double
  * response applied, x0 = xd[:,k] + f(t_k, -k, xd[:,k], ud[:,k], p), and coasts with idle inputs over LinRange(t_k, t_{k+1},
  * subres), subres = ceil(res / (N - 1)); xc[nx, 1 + (N-1) subres, B]: sample 0 = xd[:,1], then the intervals' samples (the
  * reference's sample times are those grids with the first time of every interval shifted by sqrt(eps)).  Host pointers.
+ * Like scp_discretize_batch_host it stages its input in the handle's solution buffers and so overwrites a run's last solution.
  */
 int scp_propagate_batch_host(scp_handle h, int B, const double *xd, const double *ud, const double *p, int res,
                              double *xc);
@@ -255,7 +257,9 @@ typedef struct {
      * otherwise coarse (a level whose snapshot was never taken falls through to the next coarser one).  The right level is a matter of
      * scale: the new problem's residual at an old iterate is of the order of d; an iterate at mu = 1e-10 is the best start when the
      * reference moved by 1e-8 (the solve then needs 1 ... 3 iterations) and a trap when it moved by 1e-4 (steps of 0.01 until the
-     * iteration limit of a warm attempt, then the cold repeat).  <= 0: the defaults 1e-5, 1e-1, 1e-10, 1e-6; with them ipm_warm_mu = 1e-8.
+     * iteration limit of a warm attempt, then the cold repeat).  <= 0: the defaults 1e-5, 1e-1, 1e-10, 1e-6 of these four fields.  The
+     * fine level itself has NO default in the library: ipm_warm_mu <= 0 with ipm_warm != 0 is SCP_ERR_BAD_ARGUMENT and ipm_warm_dev is
+     * taken as given (the levels above were tuned together with ipm_warm_mu = 1e-8, ipm_warm_dev = 1e-3).
      * Two fixed rules keep the levels honest: a level is refreshed only by an iterate within two decades below it (a warm solve that
      * starts far below a level leaves that snapshot alone), and after a solve that ended ALMOST_OPTIMAL the very fine level is not used. */
     double ipm_warm_mu_mid, ipm_warm_dev_mid, ipm_warm_mu_vfine, ipm_warm_dev_vfine;

@@ -1,5 +1,5 @@
 // K4: per-problem reductions and PTR outer-loop logic on the device.
-//   ptr_extract_kernel : un-scale the subproblem solution (value(blk), src/parser/block.jl:368-394), cost
+//   ptr_extract_body   : un-scale the subproblem solution (value(blk), src/parser/block.jl:368-394), cost
 //                        split J / J_tr / J_vc / J_aug (ptr.jl:753-895) and deviation (scp.jl:909-931)
 //   ptr_update_kernel  : unsafe_solution (scp.jl:965-980), check_stopping_criterion! (ptr.jl:908-932),
 //                        ref <- sol bookkeeping (ptr.jl:509), history record
@@ -67,9 +67,9 @@ __device__ __forceinline__ void small_solve(const double* Mcm, const double* b, 
     }
 }
 
-// the body of K4a for problem b by one wavefront -- the stand-alone kernel below, or the tail of the wave that solved the
-// problem (ipm2_solve_kernel with IpmArgs::ext: the wave that holds the slot does the extraction instead of 2 048 new waves
-// queueing for slots behind the other stream's solves -- 21 ms per launch under two concurrent streams against 0.27 ms alone)
+// the body of K4a for problem b by one wavefront: the tail of the wave that solved the problem (ipm2_solve_kernel's second
+// argument: the wave that holds the slot does the extraction instead of 2 048 new waves queueing for slots behind the other
+// stream's solves -- 21 ms per launch of a separate kernel under two concurrent streams against 0.27 ms alone)
 // (CALLER: one instantiation per calling kernel, so that the kernel's occupancy attribute propagates to this function --
 // a callee shared by kernels with different register budgets gets none, and the solver kernel would drop to one wave per SIMD)
 template <class M, int CALLER>
@@ -159,13 +159,6 @@ __device__ __noinline__ void ptr_extract_body(const ExtractArgs& a, const int b,
         a.dev[b] = ep + devx;  // ||dp||_inf + max_k ||dx_k||_inf   (q_exit = Inf)
         a.eta[(long)b * (2 * N + 1) + 2 * N] = ep;
     }
-}
-
-template <class M>
-__global__ __launch_bounds__(64) void ptr_extract_kernel(ExtractArgs a)
-{
-    if (!a.active[blockIdx.x]) return;
-    ptr_extract_body<M, 0>(a, blockIdx.x, threadIdx.x);
 }
 
 struct UpdateArgs {

@@ -34,6 +34,16 @@ struct DynBuf {  // one DLTV + defect on the device
 
 struct StarshipGuessState;
 static void starship_guess_free(StarshipGuessState* g);
+struct scp_sub;
+
+// What owns a problem handle's trajectory buffers (ref_*, sol_*, ref_dyn, sol_dyn, d_feas): the structured PTR run and every
+// subproblem handle created on the problem (scp_generic.hpp) write into the same set, so at most one run is alive per handle.
+// An init takes them over and thereby ends whatever ran before; the stand-alone subproblem solves leave them to nobody.
+enum RunKind { RUN_NONE = 0, RUN_PTR, RUN_SCVX, RUN_GUSTO, RUN_PTR_GENERIC };
+struct Run {
+    RunKind kind = RUN_NONE;
+    const scp_sub* sub = nullptr;   // the subproblem handle whose loop it is (RUN_SCVX, RUN_GUSTO, RUN_PTR_GENERIC)
+};
 
 struct scp_problem {
     int model_id = -1;
@@ -73,10 +83,9 @@ struct scp_problem {
         *n_active = nullptr, *cold_iters = nullptr, *snap = nullptr;
     long slab_stride = 0, work_stride = 0;
     bool ptr_ready = false;   // subproblem buffers allocated
-    bool run_ready = false;   // a PTR run was initialised by scp_ptr_init_host / scp_ptr_init_guess_host (guesses resident)
     bool sub_ready = false;   // a subproblem has been solved (virtual controls available)
+    Run run;                  // RUN_PTR: initialised by scp_ptr_init_host / scp_ptr_init_guess_host (guesses resident)
     int num_cus = 256;      // multiProcessorCount of the device (set at create)
-    int wpe_override = std::getenv("SCP_IPM_WPE") ? std::atoi(std::getenv("SCP_IPM_WPE")) : 0;   // tuning aid
     // debugging / parity aid: force the reference formulation of discretize! (K1) for const-Jacobian models too
     bool disc_reference_form = std::getenv("SCP_DISC_REFERENCE_FORM") != nullptr;
     int disc_bits = 64;     // arithmetic of discretize! (scp_set_discretize_precision): 64 = reference, 32 = tolerance check
@@ -98,6 +107,17 @@ struct scp_problem {
             return SCP_ERR_HIP;                                                              \
         }                                                                                    \
     } while (0)
+
+// The one check of every entry point that continues a run (iterate, poll, restart, get_host): is the run theirs?
+static int check_run(scp_problem* h, RunKind kind, const scp_sub* sub, const char* who)
+{
+    if (!h) return SCP_ERR_BAD_ARGUMENT;
+    if (h->run.kind == kind && h->run.sub == sub) return SCP_OK;
+    static const char* const names[] = {"no run", "a structured PTR run", "an SCvx loop", "a GuSTO loop", "a generic PTR loop"};
+    h->err = std::string(who) + " of " + names[kind] + ": the handle's trajectory buffers belong to " + names[h->run.kind] +
+             (h->run.kind == kind ? " of another subproblem handle" : "") + "; start the run with its init";
+    return SCP_ERR_BAD_ARGUMENT;
+}
 
 template <class M>
 static void fill_info(scp_model_info* i)
@@ -133,14 +153,10 @@ static int with_model(int model_id, Fn&& fn)
 template <class Fn>
 static int with_structured_model(int model_id, Fn&& fn)
 {
-    switch (model_id) {
-        case SCP_MODEL_DOUBLE_INTEGRATOR: return fn(DoubleIntegrator{});
-        case SCP_MODEL_QUADROTOR: return fn(Quadrotor{});
-        case SCP_MODEL_ROCKET_LANDING: return fn(RocketLanding{});
-        case SCP_MODEL_STARSHIP: return SCP_ERR_UNSUPPORTED;
-        case SCP_MODEL_FREEFLYER: return SCP_ERR_UNSUPPORTED;
-        default: return SCP_ERR_UNKNOWN_MODEL;
-    }
+    return with_model(model_id, [&](auto m) -> int {
+        if constexpr (decltype(m)::structured) return fn(m);
+        else return (int)SCP_ERR_UNSUPPORTED;
+    });
 }
 
 extern "C" int scp_model_query(int model_id, scp_model_info* info)
@@ -269,14 +285,17 @@ static int stamp_end(scp_problem* h)
     HIP_TRY(h, hipEventRecord(h->stamps_pending.back().b, h->stream));
     return SCP_OK;
 }
+// a finished stamp: its time into the totals of its kernel, its events back to the free list
+static void stamp_fold(scp_problem* h, const scp_problem::Stamp& st)
+{
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, st.a, st.b) == hipSuccess) { h->t_kernel[st.kind] += ms * 1e-3; h->n_kernel[st.kind] += 1; }
+    h->stamps_free.push_back(st);
+}
 // call after a stream synchronise
 static void stamps_collect(scp_problem* h)
 {
-    for (auto& st : h->stamps_pending) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, st.a, st.b) == hipSuccess) { h->t_kernel[st.kind] += ms * 1e-3; h->n_kernel[st.kind] += 1; }
-        h->stamps_free.push_back(st);
-    }
+    for (auto& st : h->stamps_pending) stamp_fold(h, st);
     h->stamps_pending.clear();
 }
 
@@ -284,13 +303,7 @@ static void stamps_collect(scp_problem* h)
 static void stamps_collect_ready(scp_problem* h)
 {
     size_t n = 0;
-    while (n < h->stamps_pending.size() && hipEventQuery(h->stamps_pending[n].b) == hipSuccess) {
-        auto& st = h->stamps_pending[n];
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, st.a, st.b) == hipSuccess) { h->t_kernel[st.kind] += ms * 1e-3; h->n_kernel[st.kind] += 1; }
-        h->stamps_free.push_back(st);
-        n++;
-    }
+    while (n < h->stamps_pending.size() && hipEventQuery(h->stamps_pending[n].b) == hipSuccess) stamp_fold(h, h->stamps_pending[n++]);
     h->stamps_pending.erase(h->stamps_pending.begin(), h->stamps_pending.begin() + (long)n);
 }
 
@@ -304,6 +317,38 @@ static int dalloc(scp_problem* h, T** p, size_t count)
     return SCP_OK;
 }
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+
+// *seconds = device time between the handle's ev0 and ev1 (recorded on its stream, which has been synchronised since)
+static int elapsed_out(scp_problem* h, double* seconds)
+{
+    if (!seconds) return SCP_OK;
+    float ms = 0;
+    HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    *seconds = ms * 1e-3;
+    return SCP_OK;
+}
+
+struct Traj { double *xd, *ud, *p; };   // one trajectory triple on the device
+static Traj traj_guess(scp_problem* h) { return {h->guess_xd, h->guess_ud, h->guess_p}; }
+static Traj traj_ref(scp_problem* h) { return {h->ref_xd, h->ref_ud, h->ref_p}; }
+static Traj traj_sol(scp_problem* h) { return {h->sol_xd, h->sol_ud, h->sol_p}; }
+// dst <- src for a trajectory triple: cp(dst, src, doubles per problem) copies one array; a model without parameters has no p
+template <class Copy>
+static int copy_traj(scp_problem* h, const Traj& dst, const Traj& src, Copy&& cp)
+{
+    const size_t nx = h->info.nx, nu = h->info.nu, np = h->npt, N = h->N;
+    TRY(cp(dst.xd, src.xd, nx * N)); TRY(cp(dst.ud, src.ud, nu * N));
+    if (np > 0) TRY(cp(dst.p, src.p, np));
+    return SCP_OK;
+}
+// the `cp` of the structured path: the whole batch, device to device, on the handle's stream
+static auto copy_d2d(scp_problem* h, int B)
+{
+    return [h, B](double* dst, const double* src, size_t n) -> int {
+        HIP_TRY(h, hipMemcpyAsync(dst, src, n * (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        return SCP_OK;
+    };
+}
 
 static int alloc_dyn(scp_problem* h, DynBuf& d)
 {
@@ -561,12 +606,7 @@ extern "C" int scp_discretize_batch_host(scp_handle h, int B, const double* xd, 
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     TRY(copy_dyn_out(h, B, h->sol_dyn, A, Bm, Bp, F, r, E, defect));
     TRY(feas_out(h, B, h->d_feas_new, feas));
-    if (seconds) {
-        float ms = 0;
-        HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        *seconds = ms * 1e-3;
-    }
-    return SCP_OK;
+    return elapsed_out(h, seconds);
 }
 
 extern "C" int scp_propagate_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, int res,
@@ -657,83 +697,91 @@ static int check_pars(const scp_ptr_params* p)
     return SCP_OK;
 }
 
-// formulate (K2) + solve (K3) + extract (K4a) about (ref trajectory, ref_dyn); results in sol_*
+// ---- the argument blocks of K2, K3 and K4a ----
+static AsmArgs asm_args(const scp_problem* h, int B)
+{
+    AsmArgs aa;
+    aa.B = B; aa.N = h->N; aa.wvc = h->pars.wvc; aa.wtr = h->pars.wtr;
+    aa.xd = h->ref_xd; aa.ud = h->ref_ud; aa.p = h->ref_p; aa.pp = h->d_pp;
+    aa.A = h->ref_dyn.A; aa.Bm = h->ref_dyn.Bm; aa.Bp = h->ref_dyn.Bp; aa.F = h->ref_dyn.F; aa.r = h->ref_dyn.r;
+    aa.Sx = h->d_Sx; aa.cx = h->d_cx; aa.Su = h->d_Su; aa.cu = h->d_cu; aa.Sp = h->d_Sp; aa.cp = h->d_cp;
+    aa.slab = h->slab; aa.slab_stride = h->slab_stride; aa.active = h->active;
+    return aa;
+}
+
+// The snapshot levels of the warm start, coarse ... very fine, and THE place of their defaults (<= 0 selects one); the fine
+// level (ipm_warm_mu, ipm_warm_dev) has none: it is the caller's, and check_pars refuses ipm_warm_mu <= 0 with the warm start on
+static void warm_levels(const scp_ptr_params& q, double (&mu)[4], double (&dev)[4])
+{
+    auto dflt = [](double v, double d) { return v > 0.0 ? v : d; };
+    mu[0] = dflt(q.ipm_warm_mu_coarse, 1e-1); dev[0] = std::numeric_limits<double>::infinity();
+    mu[1] = dflt(q.ipm_warm_mu_mid, 1e-5);    dev[1] = dflt(q.ipm_warm_dev_mid, 1e-1);
+    mu[2] = q.ipm_warm_mu;                    dev[2] = q.ipm_warm_dev;
+    mu[3] = dflt(q.ipm_warm_mu_vfine, 1e-10); dev[3] = dflt(q.ipm_warm_dev_vfine, 1e-6);
+}
+
+static IpmArgs ipm_args(const scp_problem* h, int B)
+{
+    const scp_ptr_params& q = h->pars;
+    IpmArgs ia;
+    ia.B = B; ia.N = h->N; ia.max_iter = q.ipm_max_iter; ia.nref = q.ipm_nref; ia.stall = q.ipm_stall;
+    ia.feastol = q.ipm_feastol; ia.abstol = q.ipm_abstol; ia.reltol = q.ipm_reltol; ia.reg = q.ipm_reg;
+    ia.ref_gap = q.ipm_ref_gap; ia.ref_tol = q.ipm_ref_tol; ia.split_step = q.ipm_split_step;
+    ia.slab = h->slab; ia.slab_stride = h->slab_stride; ia.work = h->work; ia.work_stride = h->work_stride;
+    ia.z_out = h->z_out; ia.p_out = h->p_out; ia.status = h->ipm_status; ia.iters = h->ipm_iters; ia.info = h->ipm_info;
+    ia.active = h->active; ia.prof = h->prof;
+    // warm start only inside a running PTR loop, from the second iteration on (the workspace then holds the snapshots of the
+    // previous subproblem's solve and h->dev the previous solution's deviation)
+    ia.warm_allowed = (h->run.kind == RUN_PTR && h->iter >= 2 && q.ipm_warm != 0) ? 1 : 0;
+    ia.warm_min_cold = q.ipm_warm_min_cold;
+    warm_levels(q, ia.warm_mu, ia.warm_dev);
+    ia.prev_dev = h->dev; ia.cold_iters = h->cold_iters; ia.snap = h->snap;
+    return ia;
+}
+
+static ExtractArgs extract_args(const scp_problem* h, int B)
+{
+    ExtractArgs ea;
+    ea.B = B; ea.N = h->N; ea.slab = h->slab; ea.slab_stride = h->slab_stride; ea.z = h->z_out; ea.ph = h->p_out;
+    ea.Sx = h->d_Sx; ea.cx = h->d_cx; ea.Su = h->d_Su; ea.cu = h->d_cu; ea.Sp = h->d_Sp; ea.cp = h->d_cp;
+    ea.active = h->active; ea.xd = h->sol_xd; ea.ud = h->sol_ud; ea.p = h->sol_p; ea.cost = h->cost; ea.dev = h->dev;
+    ea.eta = h->eta;
+    ea.Eref = h->ref_dyn.E; ea.vd = h->vd; ea.vs = h->vs; ea.vic = h->vic; ea.vtc = h->vtc; ea.Ppen = h->Ppen; ea.Pf = h->Pf;
+    ea.wvc = h->pars.wvc;
+    return ea;
+}
+
+// formulate (K2) + solve (K3), with the extraction (K4a) in the tail of the solving wave, about (ref trajectory, ref_dyn);
+// results in sol_*
 static int subproblem_dev(scp_problem* h, int B)
 {
     return with_structured_model(h->model_id, [&](auto m) -> int {
         using M = decltype(m);
         typename M::Params P = M::make_params(h->par.data());
-        AsmArgs aa;
-        aa.B = B; aa.N = h->N; aa.wvc = h->pars.wvc; aa.wtr = h->pars.wtr;
-        aa.xd = h->ref_xd; aa.ud = h->ref_ud; aa.p = h->ref_p; aa.pp = h->d_pp;
-        aa.A = h->ref_dyn.A; aa.Bm = h->ref_dyn.Bm; aa.Bp = h->ref_dyn.Bp; aa.F = h->ref_dyn.F; aa.r = h->ref_dyn.r;
-        aa.Sx = h->d_Sx; aa.cx = h->d_cx; aa.Su = h->d_Su; aa.cu = h->d_cu; aa.Sp = h->d_Sp; aa.cp = h->d_cp;
-        aa.slab = h->slab; aa.slab_stride = h->slab_stride; aa.active = h->active;
         const long nthreads = (long)B * (h->N + 1);
         TRY(stamp_begin(h, 1));
-        hipLaunchKernelGGL(ptr_assemble_kernel<M>, dim3((unsigned)((nthreads + 63) / 64)), dim3(64), 0, h->stream, aa, P);
+        hipLaunchKernelGGL(ptr_assemble_kernel<M>, dim3((unsigned)((nthreads + 63) / 64)), dim3(64), 0, h->stream, asm_args(h, B), P);
         TRY(stamp_end(h));
         HIP_TRY(h, hipGetLastError());
-        IpmArgs ia;
-        ia.B = B; ia.N = h->N; ia.max_iter = h->pars.ipm_max_iter; ia.nref = h->pars.ipm_nref; ia.stall = h->pars.ipm_stall;
-        ia.feastol = h->pars.ipm_feastol; ia.abstol = h->pars.ipm_abstol; ia.reltol = h->pars.ipm_reltol; ia.reg = h->pars.ipm_reg; ia.ref_gap = h->pars.ipm_ref_gap; ia.ref_tol = h->pars.ipm_ref_tol; ia.split_step = h->pars.ipm_split_step;
-        ia.slab = h->slab; ia.slab_stride = h->slab_stride; ia.work = h->work; ia.work_stride = h->work_stride;
-        ia.z_out = h->z_out; ia.p_out = h->p_out; ia.status = h->ipm_status; ia.iters = h->ipm_iters; ia.info = h->ipm_info;
-        ia.active = h->active; ia.prof = h->prof;
-        // warm start only inside a running PTR loop, from the second iteration on (the workspace then holds the snapshots of the
-        // previous subproblem's solve and h->dev the previous solution's deviation)
-        ia.warm_allowed = (h->run_ready && h->iter >= 2 && h->pars.ipm_warm != 0) ? 1 : 0;
-        ia.warm_min_cold = h->pars.ipm_warm_min_cold;
-        {   // snapshot levels, coarse ... very fine (scp_ptr_params: <= 0 selects the default of a level)
-            auto dflt = [](double v, double d) { return v > 0.0 ? v : d; };
-            const scp_ptr_params& q = h->pars;
-            ia.warm_mu[0] = dflt(q.ipm_warm_mu_coarse, 1e-1); ia.warm_dev[0] = std::numeric_limits<double>::infinity();
-            ia.warm_mu[1] = dflt(q.ipm_warm_mu_mid, 1e-5);    ia.warm_dev[1] = dflt(q.ipm_warm_dev_mid, 1e-1);
-            ia.warm_mu[2] = q.ipm_warm_mu;                    ia.warm_dev[2] = q.ipm_warm_dev;
-            ia.warm_mu[3] = dflt(q.ipm_warm_mu_vfine, 1e-10); ia.warm_dev[3] = dflt(q.ipm_warm_dev_vfine, 1e-6);
-        }
-        ia.prev_dev = h->dev; ia.cold_iters = h->cold_iters; ia.snap = h->snap;
-        ExtractArgs ea;
-        ea.B = B; ea.N = h->N; ea.slab = h->slab; ea.slab_stride = h->slab_stride; ea.z = h->z_out; ea.ph = h->p_out;
-        ea.Sx = h->d_Sx; ea.cx = h->d_cx; ea.Su = h->d_Su; ea.cu = h->d_cu; ea.Sp = h->d_Sp; ea.cp = h->d_cp;
-        ea.active = h->active; ea.xd = h->sol_xd; ea.ud = h->sol_ud; ea.p = h->sol_p; ea.cost = h->cost; ea.dev = h->dev;
-        ea.eta = h->eta;
-        ea.Eref = h->ref_dyn.E; ea.vd = h->vd; ea.vs = h->vs; ea.vic = h->vic; ea.vtc = h->vtc; ea.Ppen = h->Ppen; ea.Pf = h->Pf;
-        ea.wvc = h->pars.wvc;
-        // K4a runs in the tail of the solving wave (ipm2_solve_kernel's second argument) unless SCP_K3_FUSE_EXTRACT=0 asks for
-        // the separate launch (A/B measurements; the results are bit-identical: the same code on the same data)
-        static const bool fuse = []() { const char* e = getenv("SCP_K3_FUSE_EXTRACT"); return !(e && e[0] == '0'); }();
-        ExtractArgs ef = ea;
-        if (!fuse) ef.xd = nullptr;
+        int wpe = (B > 4 * h->num_cus) ? 2 : 1;   // more problems than SIMDs: two problems per SIMD
+        if (h->pars.ipm_wpe == 1 || h->pars.ipm_wpe == 2) wpe = h->pars.ipm_wpe;
+        const IpmArgs ia = ipm_args(h, B);
+        const ExtractArgs ea = extract_args(h, B);
         TRY(stamp_begin(h, 2));
-        {
-#ifdef SCP_IPM_ONLY_WPE   // experiment: a library with a single kernel variant
-            hipLaunchKernelGGL((ipm2_solve_kernel<M, SCP_IPM_ONLY_WPE>), dim3(B), dim3(64), 0, h->stream, ia, ef);
-#else
-            int wpe = (B > 4 * h->num_cus) ? 2 : 1;   // more problems than SIMDs: two problems per SIMD
-            if (h->pars.ipm_wpe == 1 || h->pars.ipm_wpe == 2) wpe = h->pars.ipm_wpe;
-            if (h->wpe_override > 0) wpe = h->wpe_override;
-            if (wpe >= 2) hipLaunchKernelGGL((ipm2_solve_kernel<M, 2>), dim3(B), dim3(64), 0, h->stream, ia, ef);
-            else hipLaunchKernelGGL((ipm2_solve_kernel<M, 1>), dim3(B), dim3(64), 0, h->stream, ia, ef);
-#endif
-        }
+        if (wpe >= 2) hipLaunchKernelGGL((ipm2_solve_kernel<M, 2>), dim3(B), dim3(64), 0, h->stream, ia, ea);
+        else hipLaunchKernelGGL((ipm2_solve_kernel<M, 1>), dim3(B), dim3(64), 0, h->stream, ia, ea);
         TRY(stamp_end(h));
         HIP_TRY(h, hipGetLastError());
-        if (!fuse) {
-            TRY(stamp_begin(h, 3));
-            hipLaunchKernelGGL(ptr_extract_kernel<M>, dim3(B), dim3(64), 0, h->stream, ea);
-            TRY(stamp_end(h));
-            HIP_TRY(h, hipGetLastError());
-        }
         h->sub_ready = true;
         return (int)SCP_OK;
     });
 }
 
-static int set_active_all(scp_problem* h, int B)
+// active[0 .. B) = 1 for a run that starts; waits for the stream (the source is on this stack frame)
+static int set_active_all(scp_problem* h, int* active, int B)
 {
     std::vector<int> ones(B, 1);
-    HIP_TRY(h, hipMemcpyAsync(h->active, ones.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(active, ones.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     stamps_collect(h);
     return SCP_OK;
@@ -742,20 +790,16 @@ static int set_active_all(scp_problem* h, int B)
 static int ptr_start_dev(scp_problem* h)
 {
     const int B = h->B;
-    const size_t nx = h->info.nx, nu = h->info.nu, np = h->npt, N = h->N, D = sizeof(double), b = B;
-    HIP_TRY(h, hipMemcpyAsync(h->ref_xd, h->guess_xd, nx * N * b * D, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->ref_ud, h->guess_ud, nu * N * b * D, hipMemcpyDeviceToDevice, h->stream));
-    if (np > 0) HIP_TRY(h, hipMemcpyAsync(h->ref_p, h->guess_p, np * b * D, hipMemcpyDeviceToDevice, h->stream));
+    const auto cp = copy_d2d(h, B);
+    TRY(copy_traj(h, traj_ref(h), traj_guess(h), cp));
     // until the first iteration has run, the "solution" returned by scp_ptr_get_host is the guess itself
-    HIP_TRY(h, hipMemcpyAsync(h->sol_xd, h->guess_xd, nx * N * b * D, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->sol_ud, h->guess_ud, nu * N * b * D, hipMemcpyDeviceToDevice, h->stream));
-    if (np > 0) HIP_TRY(h, hipMemcpyAsync(h->sol_p, h->guess_p, np * b * D, hipMemcpyDeviceToDevice, h->stream));
+    TRY(copy_traj(h, traj_sol(h), traj_guess(h), cp));
     h->iter = 0;
     // generate_initial_guess: discretize!(guess)  (ptr.jl:548-555); J_aug of the guess is NaN (ptr.jl:350)
     TRY(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas_new, nullptr));
     // scp_ptr_get_host straight after init / restart returns the guess: its feasibility flag and defects are the guess's
     HIP_TRY(h, hipMemcpyAsync(h->d_feas, h->d_feas_new, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->sol_dyn.defect, h->ref_dyn.defect, nx * (N - 1) * b * D, hipMemcpyDeviceToDevice, h->stream));
+    TRY(cp(h->sol_dyn.defect, h->ref_dyn.defect, (size_t)h->info.nx * (h->N - 1)));
     std::vector<double> nan(B, std::numeric_limits<double>::quiet_NaN());
     HIP_TRY(h, hipMemcpyAsync(h->Jaug_ref, nan.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemsetAsync(h->scp_status, 0, (size_t)B * sizeof(int), h->stream));
@@ -763,48 +807,60 @@ static int ptr_start_dev(scp_problem* h)
     HIP_TRY(h, hipMemsetAsync(h->cold_iters, 0, (size_t)B * sizeof(int), h->stream));
     HIP_TRY(h, hipMemsetAsync(h->snap, 0, (size_t)B * sizeof(int), h->stream));
     HIP_TRY(h, hipMemsetAsync(h->hist, 0, (size_t)h->pars.iter_max * B * H_N * sizeof(double), h->stream));
-    TRY(set_active_all(h, B));
+    TRY(set_active_all(h, h->active, B));
+    return SCP_OK;
+}
+
+// What scp_ptr_init_host, scp_ptr_init_guess_host and scp_ptr_solve_subproblem_batch_host share: argument checks, buffers, run
+// state, uploads.  The inits take the trajectory buffers over for a structured run; the stand-alone solve reuses them for its
+// one subproblem, so any run on the handle ends there (iterate / restart / get_host are refused until the next init).
+enum PtrBegin { PTR_BEGIN_HOST_GUESS, PTR_BEGIN_DEVICE_GUESS, PTR_BEGIN_SINGLE_SOLVE };
+static int ptr_begin(scp_problem* h, PtrBegin what, int B, const scp_ptr_params* pars, const double* xd, const double* ud,
+                     const double* p, const double* pp)
+{
+    const bool traj = what != PTR_BEGIN_DEVICE_GUESS, run = what != PTR_BEGIN_SINGLE_SOLVE;
+    if (!h || B < 1 || (traj && (!xd || !ud))) return SCP_ERR_BAD_ARGUMENT;
+    if (B > h->cap) return SCP_ERR_BATCH_TOO_LARGE;
+    if (traj && h->npt > 0 && !p) return SCP_ERR_BAD_ARGUMENT;
+    if (h->info.npp > 0 && !pp) return SCP_ERR_BAD_ARGUMENT;
+    TRY(check_pars(pars));
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(ensure_ptr_buffers(h, run ? pars->iter_max : 1));
+    h->pars = *pars; h->B = B; h->iter = 0; h->run = Run{run ? RUN_PTR : RUN_NONE, nullptr};
+    if (run) h->sub_ready = false;
+    const Traj dst = run ? traj_guess(h) : traj_ref(h);
+    if (traj) TRY(upload_traj(h, B, xd, ud, p, dst.xd, dst.ud, dst.p));
+    if (h->info.npp > 0)
+        HIP_TRY(h, hipMemcpyAsync(h->d_pp, pp, (size_t)h->info.npp * B * sizeof(double), hipMemcpyHostToDevice, h->stream));
     return SCP_OK;
 }
 
 extern "C" int scp_ptr_init_host(scp_handle h, int B, const scp_ptr_params* pars, const double* xd, const double* ud,
                                  const double* p, const double* pp)
 {
-    if (!h || B < 1 || !xd || !ud) return SCP_ERR_BAD_ARGUMENT;
-    if (B > h->cap) return SCP_ERR_BATCH_TOO_LARGE;
-    if (h->npt > 0 && !p) return SCP_ERR_BAD_ARGUMENT;
-    if (h->info.npp > 0 && !pp) return SCP_ERR_BAD_ARGUMENT;
-    TRY(check_pars(pars));
-    HIP_TRY(h, hipSetDevice(h->device));
-    TRY(ensure_ptr_buffers(h, pars->iter_max));
-    h->pars = *pars; h->B = B; h->iter = 0; h->run_ready = true; h->sub_ready = false;
-    TRY(upload_traj(h, B, xd, ud, p, h->guess_xd, h->guess_ud, h->guess_p));
-    if (h->info.npp > 0)
-        HIP_TRY(h, hipMemcpyAsync(h->d_pp, pp, (size_t)h->info.npp * B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    TRY(ptr_begin(h, PTR_BEGIN_HOST_GUESS, B, pars, xd, ud, p, pp));
     return ptr_start_dev(h);
+}
+
+// traj.guess(N) of the handle's model on the device (ptr_guess_kernel: the model's own straight-line rule)
+static int guess_dev(scp_problem* h, const GuessArgs& g)
+{
+    TRY(with_model(h->model_id, [&](auto m) -> int {
+        using M = decltype(m);
+        const long n = (long)g.B * g.N;
+        hipLaunchKernelGGL(ptr_guess_kernel<M>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, g, M::make_params(h->par.data()));
+        return (int)SCP_OK;
+    }));
+    HIP_TRY(h, hipGetLastError());
+    return SCP_OK;
 }
 
 extern "C" int scp_ptr_init_guess_host(scp_handle h, int B, const scp_ptr_params* pars, const double* pp)
 {
-    if (!h || B < 1) return SCP_ERR_BAD_ARGUMENT;
-    if (B > h->cap) return SCP_ERR_BATCH_TOO_LARGE;
-    if (h->info.npp > 0 && !pp) return SCP_ERR_BAD_ARGUMENT;
-    TRY(check_pars(pars));
-    HIP_TRY(h, hipSetDevice(h->device));
-    TRY(ensure_ptr_buffers(h, pars->iter_max));
-    h->pars = *pars; h->B = B; h->iter = 0; h->run_ready = true; h->sub_ready = false;
-    if (h->info.npp > 0)
-        HIP_TRY(h, hipMemcpyAsync(h->d_pp, pp, (size_t)h->info.npp * B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    TRY(ptr_begin(h, PTR_BEGIN_DEVICE_GUESS, B, pars, nullptr, nullptr, nullptr, pp));
     GuessArgs g;
     g.B = B; g.N = h->N; g.pp = h->d_pp; g.xd = h->guess_xd; g.ud = h->guess_ud; g.p = h->guess_p;
-    TRY(with_model(h->model_id, [&](auto m) -> int {
-        using M = decltype(m);
-        typename M::Params P = M::make_params(h->par.data());
-        const long n = (long)B * h->N;
-        hipLaunchKernelGGL(ptr_guess_kernel<M>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, g, P);
-        return (int)SCP_OK;
-    }));
-    HIP_TRY(h, hipGetLastError());
+    TRY(guess_dev(h, g));
     return ptr_start_dev(h);
 }
 
@@ -954,19 +1010,9 @@ extern "C" int scp_guess_batch_host(scp_handle h, int B, const double* pp, doubl
     GuessArgs g;
     g.B = B; g.N = h->N; g.pp = h->q_pp; g.xd = h->q_xd; g.ud = h->q_ud; g.p = h->q_p;
     h->guess_failures = 0;
-    if (h->model_id == Starship::id && !std::getenv("SCP_STARSHIP_STRAIGHT_LINE_GUESS")) {
-        // the reference's own guess: bang-bang flip + convex terminal descent, per instance (starship_guess.hpp)
-        TRY(starship_guess_dev(h, B, h->q_pp, h->q_xd, h->q_ud, h->q_p));
-    } else {
-    TRY(with_model(h->model_id, [&](auto m) -> int {
-        using M = decltype(m);
-        typename M::Params P = M::make_params(h->par.data());
-        const long n = (long)B * h->N;
-        hipLaunchKernelGGL(ptr_guess_kernel<M>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, g, P);
-        return (int)SCP_OK;
-    }));
-    }
-    HIP_TRY(h, hipGetLastError());
+    // Starship: the reference's own guess, bang-bang flip + convex terminal descent per instance (starship_guess.hpp)
+    if (h->model_id == Starship::id) TRY(starship_guess_dev(h, B, h->q_pp, h->q_xd, h->q_ud, h->q_p));
+    else TRY(guess_dev(h, g));
     HIP_TRY(h, hipMemcpyAsync(xd, h->q_xd, nx * N * b * D, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(ud, h->q_ud, nu * N * b * D, hipMemcpyDeviceToHost, h->stream));
     if (np > 0) HIP_TRY(h, hipMemcpyAsync(p, h->q_p, np * b * D, hipMemcpyDeviceToHost, h->stream));
@@ -976,7 +1022,7 @@ extern "C" int scp_guess_batch_host(scp_handle h, int B, const double* pp, doubl
 
 extern "C" int scp_ptr_restart(scp_handle h)
 {
-    if (!h || !h->run_ready || h->B < 1 || h->pars.iter_max > h->hist_cap) return SCP_ERR_BAD_ARGUMENT;
+    TRY(check_run(h, RUN_PTR, nullptr, "scp_ptr_restart"));
     HIP_TRY(h, hipSetDevice(h->device));
     return ptr_start_dev(h);
 }
@@ -994,15 +1040,13 @@ extern "C" int scp_get_kernel_timing(scp_handle h, double seconds[4], long launc
 
 static int copy_sol_to_ref(scp_problem* h, int B)
 {
-    const size_t nx = h->info.nx, nu = h->info.nu, np = h->npt, npF = h->info.npF > 0 ? h->info.npF : 1, N = h->N,
-                 M = N - 1, D = sizeof(double), b = B;
-    auto cp = [&](double* dst, const double* src, size_t n) { return hipMemcpyAsync(dst, src, n * D, hipMemcpyDeviceToDevice, h->stream); };
-    HIP_TRY(h, cp(h->ref_xd, h->sol_xd, nx * N * b)); HIP_TRY(h, cp(h->ref_ud, h->sol_ud, nu * N * b));
-    if (np > 0) HIP_TRY(h, cp(h->ref_p, h->sol_p, np * b));
-    HIP_TRY(h, cp(h->ref_dyn.A, h->sol_dyn.A, nx * nx * M * b)); HIP_TRY(h, cp(h->ref_dyn.Bm, h->sol_dyn.Bm, nx * nu * M * b));
-    HIP_TRY(h, cp(h->ref_dyn.Bp, h->sol_dyn.Bp, nx * nu * M * b)); HIP_TRY(h, cp(h->ref_dyn.F, h->sol_dyn.F, nx * npF * M * b));
-    HIP_TRY(h, cp(h->ref_dyn.r, h->sol_dyn.r, nx * M * b));
-    HIP_TRY(h, cp(h->ref_dyn.E, h->sol_dyn.E, nx * nx * M * b));   // ref.dyn.E enters the next subproblem's vd (ptr.jl:805)
+    const size_t nx = h->info.nx, nu = h->info.nu, npF = h->info.npF > 0 ? h->info.npF : 1, M = h->N - 1;
+    const auto cp = copy_d2d(h, B);
+    TRY(copy_traj(h, traj_ref(h), traj_sol(h), cp));
+    TRY(cp(h->ref_dyn.A, h->sol_dyn.A, nx * nx * M)); TRY(cp(h->ref_dyn.Bm, h->sol_dyn.Bm, nx * nu * M));
+    TRY(cp(h->ref_dyn.Bp, h->sol_dyn.Bp, nx * nu * M)); TRY(cp(h->ref_dyn.F, h->sol_dyn.F, nx * npF * M));
+    TRY(cp(h->ref_dyn.r, h->sol_dyn.r, nx * M));
+    TRY(cp(h->ref_dyn.E, h->sol_dyn.E, nx * nx * M));   // ref.dyn.E enters the next subproblem's vd (ptr.jl:805)
     return SCP_OK;
 }
 
@@ -1017,7 +1061,7 @@ __global__ void merge_feas_kernel(int B, const int* active, const int* fnew, int
 // longer idle the rest of the chip.  scp_ptr_poll waits and returns the active count.
 extern "C" int scp_ptr_iterate_async(scp_handle h)
 {
-    if (!h || !h->run_ready || h->B < 1 || h->pars.iter_max > h->hist_cap) return SCP_ERR_BAD_ARGUMENT;
+    TRY(check_run(h, RUN_PTR, nullptr, "scp_ptr_iterate"));
     HIP_TRY(h, hipSetDevice(h->device));
     const int B = h->B;
     h->iter += 1;
@@ -1060,7 +1104,7 @@ extern "C" int scp_ptr_iterate_async(scp_handle h)
 
 extern "C" int scp_ptr_poll(scp_handle h, int* n_active)
 {
-    if (!h || !h->run_ready || h->B < 1) return SCP_ERR_BAD_ARGUMENT;
+    TRY(check_run(h, RUN_PTR, nullptr, "scp_ptr_poll"));
     HIP_TRY(h, hipSetDevice(h->device));
     int na = 0;
     if (h->iter >= 1 && h->iter <= h->pars.iter_max)   // n_active of the last enqueued iteration (0 once iter_max is passed)
@@ -1075,7 +1119,8 @@ extern "C" int scp_ptr_poll(scp_handle h, int* n_active)
 // caller enqueues window k + 1, then reads the count of window k (multi-GPU loop: the queue never drains at a window boundary).
 extern "C" int scp_ptr_poll_iteration(scp_handle h, int iteration, int* n_active)
 {
-    if (!h || !h->run_ready || h->B < 1 || !n_active || iteration < 1 || iteration > h->iter) return SCP_ERR_BAD_ARGUMENT;
+    TRY(check_run(h, RUN_PTR, nullptr, "scp_ptr_poll_iteration"));
+    if (!n_active || iteration < 1 || iteration > h->iter) return SCP_ERR_BAD_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
     if (iteration > h->pars.iter_max) { *n_active = 0; return SCP_OK; }     // nothing was enqueued beyond iter_max
     if (!h->na_ring || (int)h->na_ev.size() <= iteration) return SCP_ERR_BAD_ARGUMENT;
@@ -1094,7 +1139,7 @@ extern "C" int scp_ptr_iterate(scp_handle h, int* n_active)
 extern "C" int scp_ptr_get_host(scp_handle h, double* xd, double* ud, double* p, int32_t* status, int32_t* iterations,
                                 double* cost, uint8_t* feas, double* defect, double* hist)
 {
-    if (!h || !h->run_ready || h->B < 1 || h->pars.iter_max > h->hist_cap) return SCP_ERR_BAD_ARGUMENT;
+    TRY(check_run(h, RUN_PTR, nullptr, "scp_ptr_get_host"));
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t D = sizeof(double), b = h->B;
     TRY(download_traj(h, h->B, true, xd, ud, p, defect));
@@ -1118,12 +1163,7 @@ extern "C" int scp_ptr_solve_batch_host(scp_handle h, int B, const scp_ptr_param
     while (na > 0) TRY(scp_ptr_iterate(h, &na));
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     TRY(scp_ptr_get_host(h, xd_out, ud_out, p_out, status, iterations, cost, feas, nullptr, nullptr));
-    if (seconds) {
-        float ms = 0;
-        HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        *seconds = ms * 1e-3;
-    }
-    return SCP_OK;
+    return elapsed_out(h, seconds);
 }
 
 extern "C" int scp_ptr_solve_subproblem_batch_host(scp_handle h, int B, const scp_ptr_params* pars,
@@ -1132,20 +1172,8 @@ extern "C" int scp_ptr_solve_subproblem_batch_host(scp_handle h, int B, const sc
                                                    double* eta, int32_t* solver_status, int32_t* solver_iters,
                                                    double* info, double* defect, uint8_t* feas, double* seconds)
 {
-    if (!h || B < 1 || !xd_ref || !ud_ref) return SCP_ERR_BAD_ARGUMENT;
-    if (B > h->cap) return SCP_ERR_BATCH_TOO_LARGE;
-    if (h->npt > 0 && !p_ref) return SCP_ERR_BAD_ARGUMENT;
-    if (h->info.npp > 0 && !pp) return SCP_ERR_BAD_ARGUMENT;
-    TRY(check_pars(pars));
-    HIP_TRY(h, hipSetDevice(h->device));
-    TRY(ensure_ptr_buffers(h, 1));
-    // a stand-alone subproblem solve reuses the run's trajectory buffers: any initialised PTR run ends here
-    // (restart / iterate / get_host are refused until the next scp_ptr_init_*)
-    h->pars = *pars; h->B = B; h->iter = 0; h->run_ready = false;
-    TRY(upload_traj(h, B, xd_ref, ud_ref, p_ref, h->ref_xd, h->ref_ud, h->ref_p));
-    if (h->info.npp > 0)
-        HIP_TRY(h, hipMemcpyAsync(h->d_pp, pp, (size_t)h->info.npp * B * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    TRY(set_active_all(h, B));
+    TRY(ptr_begin(h, PTR_BEGIN_SINGLE_SOLVE, B, pars, xd_ref, ud_ref, p_ref, pp));
+    TRY(set_active_all(h, h->active, B));
     TRY(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas_new, nullptr));
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     TRY(subproblem_dev(h, B));
@@ -1159,12 +1187,7 @@ extern "C" int scp_ptr_solve_subproblem_batch_host(scp_handle h, int B, const sc
     if (solver_iters) HIP_TRY(h, hipMemcpyAsync(solver_iters, h->ipm_iters, b * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (info) HIP_TRY(h, hipMemcpyAsync(info, h->ipm_info, 8 * b * D, hipMemcpyDeviceToHost, h->stream));
     TRY(feas_out(h, B, h->d_feas_new, feas));
-    if (seconds) {
-        float ms = 0;
-        HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        *seconds = ms * 1e-3;
-    }
-    return SCP_OK;
+    return elapsed_out(h, seconds);
 }
 
 extern "C" int scp_ptr_get_virtual_controls_host(scp_handle h, double* vd, double* vs, double* vic, double* vtc, double* P,
@@ -1389,7 +1412,7 @@ extern "C" int scp_ptr_run_sharded(scp_comm_handle c, scp_handle* parts, int npa
     int iter_max = -1;
     for (int i = 0; i < nparts; i++) {
         scp_problem* h = parts[i];
-        if (!h || !h->run_ready || h->B < 1 || h->device != c->device) { c->err = "scp_ptr_run_sharded: every part needs an initialised PTR run on the communicator's device"; return SCP_ERR_BAD_ARGUMENT; }
+        if (check_run(h, RUN_PTR, nullptr, "scp_ptr_run_sharded") != SCP_OK || h->device != c->device) { c->err = "scp_ptr_run_sharded: every part needs an initialised PTR run on the communicator's device"; return SCP_ERR_BAD_ARGUMENT; }
         if (iter_max >= 0 && h->pars.iter_max != iter_max) { c->err = "scp_ptr_run_sharded: parts with different iter_max"; return SCP_ERR_BAD_ARGUMENT; }
         iter_max = h->pars.iter_max;
     }

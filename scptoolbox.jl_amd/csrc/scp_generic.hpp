@@ -270,8 +270,7 @@ struct scp_sub {
     double* post = nullptr;  // [cap][4]
     std::vector<void*> allocs;
     // outer-loop run state (SCvx: scvx.jl:459-540; GuSTO: gusto.jl:425-502; PTR: ptr.jl:448-532), set by the init that started
-    // the run (loop_begin); iterate and get_host of another loop refuse the handle
-    enum Loop { LOOP_NONE = 0, LOOP_SCVX, LOOP_GUSTO, LOOP_PTR } loop = LOOP_NONE;
+    // the run (loop_begin).  WHICH loop runs, and whether it still owns the trajectory buffers, is h->run (check_run)
     scp::conic::Opts opts{};                  // subproblem solver options of the run
     double q_exit = std::numeric_limits<double>::infinity(), q_tr = std::numeric_limits<double>::infinity();   // norms of sub_post
     int B = 0, iter = 0, iter_max = 0, hist_cap = 0;
@@ -365,6 +364,7 @@ extern "C" int scp_sub_destroy(scp_sub_handle s)
     if (!s) return SCP_ERR_BAD_ARGUMENT;
     (void)hipSetDevice(s->h->device);
     (void)hipStreamSynchronize(s->h->stream);
+    if (s->h->run.sub == s) s->h->run = Run{};   // its loop ends with it
     s->eng.destroy();
     for (void* p : s->allocs) (void)hipFree(p);
     delete s;
@@ -441,15 +441,10 @@ static int sub_fill_sources(scp_sub* s, int B, const int* active)
         return scp::conic::transpose_to_interleaved(h->stream, src, s->src + L.off[seg] * BS, len, B, (int)BS);
     };
     int rc;
-    if ((rc = tr(h->ref_xd, scp::SEG_XREF)) != SCP_OK) return rc;
-    if ((rc = tr(h->ref_ud, scp::SEG_UREF)) != SCP_OK) return rc;
-    if ((rc = tr(h->ref_p, scp::SEG_PREF)) != SCP_OK) return rc;
-    if ((rc = tr(h->ref_dyn.A, scp::SEG_A)) != SCP_OK) return rc;
-    if ((rc = tr(h->ref_dyn.Bm, scp::SEG_BM)) != SCP_OK) return rc;
-    if ((rc = tr(h->ref_dyn.Bp, scp::SEG_BP)) != SCP_OK) return rc;
-    if ((rc = tr(h->ref_dyn.F, scp::SEG_F)) != SCP_OK) return rc;
-    if ((rc = tr(h->ref_dyn.r, scp::SEG_R)) != SCP_OK) return rc;
-    if ((rc = tr(h->ref_dyn.E, scp::SEG_E)) != SCP_OK) return rc;
+    const DynBuf& d = h->ref_dyn;
+    const double* const resident[] = {h->ref_xd, h->ref_ud, h->ref_p, d.A, d.Bm, d.Bp, d.F, d.r, d.E};   // SEG_XREF ... SEG_E
+    for (int seg = scp::SEG_XREF; seg <= scp::SEG_E; seg++)
+        if ((rc = tr(resident[seg], seg)) != SCP_OK) return rc;
     scp::GenLinArgs a;
     a.B = B; a.N = h->N; a.BS = BS; a.xd = h->ref_xd; a.ud = h->ref_ud; a.p = h->ref_p; a.pp = s->d_pp; a.src = s->src;
     a.oC = L.off[scp::SEG_C]; a.oD = L.off[scp::SEG_D]; a.oG = L.off[scp::SEG_GS]; a.oRS = L.off[scp::SEG_RS];
@@ -553,6 +548,7 @@ extern "C" int scp_sub_solve_batch_host(scp_sub_handle s, int B, const double* x
     if (B > h->cap) { s->err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
     if ((h->npt > 0 && !p_ref) || (h->info.npp > 0 && !pp) || (s->nscal > 0 && !scal)) { s->err = "missing input"; return SCP_ERR_BAD_ARGUMENT; }
     SUB_TRY(hipSetDevice(h->device));
+    h->run = Run{};   // a stand-alone solve reuses the trajectory buffers: any run on the problem handle ends here
     SUB_CALL(upload_traj(h, B, xd_ref, ud_ref, p_ref, h->ref_xd, h->ref_ud, h->ref_p));
     if (h->info.npp > 0) SUB_TRY(hipMemcpyAsync(s->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
     SUB_TRY(hipEventRecord(h->ev0, h->stream));
@@ -569,7 +565,7 @@ extern "C" int scp_sub_solve_batch_host(scp_sub_handle s, int B, const double* x
     if ((rc = sub_get_il(s, B, s->funv, s->nfun, fun)) != SCP_OK) return rc;
     if ((rc = sub_get_il(s, B, s->eng.x, s->eng.sched.n, xconic)) != SCP_OK) return rc;
     if ((rc = sub_get_il(s, B, s->eng.info, 8, info)) != SCP_OK) return rc;
-    if (seconds) { float ms = 0; SUB_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1)); *seconds = ms * 1e-3; }
+    SUB_CALL(elapsed_out(h, seconds));
     return SCP_OK;
 }
 
@@ -669,18 +665,18 @@ __global__ void proj_status_kernel(const int* ipm_status, int* active, int* scp_
 
 }  // namespace scp
 
-static int sub_masked_copy_all(scp_sub* s, int B, const int* mask, bool to_ref)
+// ref <- sol (trajectory, its discretisation and defects) for the problems with mask[b] != 0
+static int sub_masked_copy_all(scp_sub* s, int B, const int* mask)
 {
     scp_problem* h = s->h;
-    const long nx = h->info.nx, nu = h->info.nu, np = h->npt, npF = h->info.npF, N = h->N, M = N - 1;
-    auto cp = [&](double* a, double* b_, long len) {
-        if (len == 0) return;
-        double* dst = to_ref ? a : b_;
-        const double* src = to_ref ? b_ : a;
+    const long nx = h->info.nx, nu = h->info.nu, npF = h->info.npF, M = h->N - 1;
+    auto cp = [&](double* dst, const double* src, long len) -> int {
+        if (len == 0) return SCP_OK;
         const unsigned gx = (unsigned)std::min<long>((len + 255) / 256, 64);
         hipLaunchKernelGGL(scp::masked_copy_kernel, dim3(gx, B), dim3(256), 0, h->stream, dst, src, len, mask, B);
+        return SCP_OK;
     };
-    cp(h->ref_xd, h->sol_xd, nx * N); cp(h->ref_ud, h->sol_ud, nu * N); cp(h->ref_p, h->sol_p, np);
+    SUB_CALL(copy_traj(h, traj_ref(h), traj_sol(h), cp));
     cp(h->ref_dyn.A, h->sol_dyn.A, nx * nx * M); cp(h->ref_dyn.Bm, h->sol_dyn.Bm, nx * nu * M); cp(h->ref_dyn.Bp, h->sol_dyn.Bp, nx * nu * M);
     cp(h->ref_dyn.F, h->sol_dyn.F, nx * npF * M); cp(h->ref_dyn.r, h->sol_dyn.r, nx * M); cp(h->ref_dyn.E, h->sol_dyn.E, nx * nx * M);
     cp(h->ref_dyn.defect, h->sol_dyn.defect, nx * M);
@@ -731,7 +727,7 @@ static int sub_loop_state(scp_sub* s, int iter_max)
 // onto the convex sets when `proj` is given (generate_initial_guess -> correct_convex!, scvx.jl:555-565, gusto.jl:516-521,
 // scp.jl:275-361) and discretises the reference.  The caller has checked s, pars, B >= 1, xd, ud and its own template; it
 // seeds its loop scalars behind this and ends with loop_begun.
-static int loop_begin(scp_sub* s, scp_sub* proj, scp_sub::Loop loop, int B, int iter_max, const scp_conic_opts& solver,
+static int loop_begin(scp_sub* s, scp_sub* proj, RunKind loop, int B, int iter_max, const scp_conic_opts& solver,
                       double q_exit, double q_tr, const double* xd, const double* ud, const double* p, const double* pp)
 {
     scp_problem* h = s->h;
@@ -741,7 +737,8 @@ static int loop_begin(scp_sub* s, scp_sub* proj, scp_sub::Loop loop, int B, int 
     SUB_TRY(hipSetDevice(h->device));
     int rc;
     if ((rc = sub_loop_state(s, iter_max)) != SCP_OK) return rc;
-    s->loop = loop; s->B = B; s->iter = 0; s->iter_max = iter_max; s->opts = sub_opts(&solver); s->q_exit = q_exit; s->q_tr = q_tr;
+    h->run = Run{loop, s};   // takes the trajectory buffers over; the projection below (sub_solve_dev) leaves that alone
+    s->B = B; s->iter = 0; s->iter_max = iter_max; s->opts = sub_opts(&solver); s->q_exit = q_exit; s->q_tr = q_tr;
     SUB_CALL(upload_traj(h, B, xd, ud, p, h->ref_xd, h->ref_ud, h->ref_p));
     if (h->info.npp > 0) {
         SUB_TRY(hipMemcpyAsync(s->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
@@ -750,17 +747,15 @@ static int loop_begin(scp_sub* s, scp_sub* proj, scp_sub::Loop loop, int B, int 
     SUB_TRY(hipMemsetAsync(s->hist, 0, sizeof(double) * (size_t)iter_max * B * SCP_SCVX_HIST_WIDTH, h->stream));
     SUB_TRY(hipMemsetAsync(s->status, 0, sizeof(int) * (size_t)B, h->stream));
     SUB_TRY(hipMemsetAsync(s->iters_done, 0, sizeof(int) * (size_t)B, h->stream));
-    if (loop == scp_sub::LOOP_PTR) SUB_TRY(hipMemsetAsync(s->post2, 0, sizeof(double) * 4 * (size_t)B, h->stream));   // its cost[B][4]
-    std::vector<int> ones(B, 1);
-    SUB_TRY(hipMemcpyAsync(s->active, ones.data(), sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    SUB_TRY(hipStreamSynchronize(h->stream));
+    if (loop == RUN_PTR_GENERIC) SUB_TRY(hipMemsetAsync(s->post2, 0, sizeof(double) * 4 * (size_t)B, h->stream));   // its cost[B][4]
+    SUB_CALL(set_active_all(h, s->active, B));
     if (proj) {
         SUB_CALL(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
         if ((rc = sub_fill_sources(proj, B, nullptr)) != SCP_OK) { s->err = proj->err; return rc; }
         if ((rc = sub_solve_dev(proj, B, s->opts, nullptr)) != SCP_OK) { s->err = proj->err; return rc; }
         hipLaunchKernelGGL(scp::proj_status_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, proj->eng.status, s->active,
                            s->status, s->accept, B);
-        if ((rc = sub_masked_copy_all(s, B, s->accept, true)) != SCP_OK) return rc;   // x_ref .= value(opti.x) (scp.jl:346-349)
+        if ((rc = sub_masked_copy_all(s, B, s->accept)) != SCP_OK) return rc;   // x_ref .= value(opti.x) (scp.jl:346-349)
     }
     SUB_CALL(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
     return SCP_OK;
@@ -778,10 +773,11 @@ static int loop_begun(scp_sub* s)
 // then update() -- the launch of the loop's own kernel(s): stopping rule, trust region, accept -- then ref = sol for the accepted
 // steps and the number of problems still active.
 template <class Update>
-static int loop_step(scp_sub* s, scp_sub::Loop loop, int* n_active, Update&& update)
+static int loop_step(scp_sub* s, RunKind loop, int* n_active, Update&& update)
 {
-    if (!s || s->loop != loop) return SCP_ERR_BAD_ARGUMENT;
+    if (!s) return SCP_ERR_BAD_ARGUMENT;
     scp_problem* h = s->h;
+    SUB_CALL(check_run(h, loop, s, "iterate"));
     SUB_TRY(hipSetDevice(h->device));
     if (s->iter >= s->iter_max) { if (n_active) *n_active = 0; return SCP_OK; }
     const int B = s->B;
@@ -793,7 +789,7 @@ static int loop_step(scp_sub* s, scp_sub::Loop loop, int* n_active, Update&& upd
     if ((rc = sub_post(s, B, h->sol_xd, h->sol_ud, h->sol_p, h->sol_dyn.defect, s->active)) != SCP_OK) return rc;
     if ((rc = update()) != SCP_OK) return rc;
     SUB_TRY(hipGetLastError());
-    if ((rc = sub_masked_copy_all(s, B, s->accept, true)) != SCP_OK) return rc;    // ref = sol for the accepted steps
+    if ((rc = sub_masked_copy_all(s, B, s->accept)) != SCP_OK) return rc;    // ref = sol for the accepted steps
     int na = 0;
     SUB_TRY(hipMemcpyAsync(&na, s->n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     SUB_TRY(hipStreamSynchronize(h->stream));
@@ -803,11 +799,12 @@ static int loop_step(scp_sub* s, scp_sub::Loop loop, int* n_active, Update&& upd
 }
 
 // The result of a run of `loop`.  cost (SCvx, GuSTO): [2][B] = J of the reference, J of the last solution.
-static int loop_get(scp_sub* s, scp_sub::Loop loop, double* xd, double* ud, double* p, int32_t* status, int32_t* iterations,
+static int loop_get(scp_sub* s, RunKind loop, double* xd, double* ud, double* p, int32_t* status, int32_t* iterations,
                     double* cost, uint8_t* feas, double* defect, double* hist)
 {
-    if (!s || s->loop != loop) return SCP_ERR_BAD_ARGUMENT;
+    if (!s) return SCP_ERR_BAD_ARGUMENT;
     scp_problem* h = s->h;
+    SUB_CALL(check_run(h, loop, s, "get_host"));
     SUB_TRY(hipSetDevice(h->device));
     const size_t D = sizeof(double), b = s->B;
     // SCPSolution(history): the LAST subproblem's solution (scp.jl:196-245); before the first iteration: the reference
@@ -829,7 +826,7 @@ extern "C" int scp_scvx_init_host(scp_sub_handle s, scp_sub_handle proj, int B, 
     if (!s || !pars || B < 1 || !xd || !ud) return SCP_ERR_BAD_ARGUMENT;
     if (pars->iter_max < 1 || s->nscal != 1 || s->nfun < 1) { s->err = "not an SCvx template (nscal = 1: eta, fun[0] = penalty)"; return SCP_ERR_BAD_ARGUMENT; }
     if (!(pars->q_exit >= 1.0)) { s->err = "q_exit must be >= 1 (or Inf)"; return SCP_ERR_BAD_ARGUMENT; }
-    int rc = loop_begin(s, proj, scp_sub::LOOP_SCVX, B, pars->iter_max, pars->solver, pars->q_exit, pars->q_exit, xd, ud, p, pp);
+    int rc = loop_begin(s, proj, RUN_SCVX, B, pars->iter_max, pars->solver, pars->q_exit, pars->q_exit, xd, ud, p, pp);
     if (rc != SCP_OK) return rc;
     s->sp = *pars;
     scp_problem* h = s->h;
@@ -843,7 +840,7 @@ extern "C" int scp_scvx_init_host(scp_sub_handle s, scp_sub_handle proj, int B, 
 
 extern "C" int scp_scvx_iterate(scp_sub_handle s, int* n_active)
 {
-    return loop_step(s, scp_sub::LOOP_SCVX, n_active, [&]() -> int {
+    return loop_step(s, RUN_SCVX, n_active, [&]() -> int {
         scp_problem* h = s->h;
         const int B = s->B;
         scp::ScvxUpdateArgs a;
@@ -859,7 +856,7 @@ extern "C" int scp_scvx_iterate(scp_sub_handle s, int* n_active)
 extern "C" int scp_scvx_get_host(scp_sub_handle s, double* xd, double* ud, double* p, int32_t* status, int32_t* iterations,
                                  double* cost, uint8_t* feas, double* defect, double* hist)
 {
-    return loop_get(s, scp_sub::LOOP_SCVX, xd, ud, p, status, iterations, cost, feas, defect, hist);
+    return loop_get(s, RUN_SCVX, xd, ud, p, status, iterations, cost, feas, defect, hist);
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -1056,7 +1053,7 @@ extern "C" int scp_gusto_init_host(scp_sub_handle s, scp_sub_handle proj, int B,
     if (!(pars->q_exit >= 1.0) || !(pars->q_tr >= 1.0)) { s->err = "q_exit and q_tr must be >= 1 (or Inf)"; return SCP_ERR_BAD_ARGUMENT; }
     if ((pars->pen != 0 && pars->pen != 1) || (pars->pen == 1 && !(pars->hom > 0.0))) { s->err = "pen must be 0 (:quad) or 1 (:softplus, hom > 0)"; return SCP_ERR_BAD_ARGUMENT; }
     if (pars->pen == 1 && s->eng.sched.nexp == 0) { s->err = "pen = :softplus needs a template with exponential cones"; return SCP_ERR_BAD_ARGUMENT; }
-    int rc = loop_begin(s, proj, scp_sub::LOOP_GUSTO, B, pars->iter_max, pars->solver, pars->q_exit, pars->q_tr, xd, ud, p, pp);
+    int rc = loop_begin(s, proj, RUN_GUSTO, B, pars->iter_max, pars->solver, pars->q_exit, pars->q_tr, xd, ud, p, pp);
     if (rc != SCP_OK) return rc;
     s->gp = *pars;
     double* scal = s->src + s->lay.off[scp::SEG_SCAL] * s->eng.BS;
@@ -1069,7 +1066,7 @@ extern "C" int scp_gusto_init_host(scp_sub_handle s, scp_sub_handle proj, int B,
 
 extern "C" int scp_gusto_iterate(scp_sub_handle s, int* n_active)
 {
-    return loop_step(s, scp_sub::LOOP_GUSTO, n_active, [&]() -> int {
+    return loop_step(s, RUN_GUSTO, n_active, [&]() -> int {
         scp_problem* h = s->h;
         const int B = s->B;
         scp::GustoPostArgs pa;
@@ -1095,7 +1092,7 @@ extern "C" int scp_gusto_iterate(scp_sub_handle s, int* n_active)
 extern "C" int scp_gusto_get_host(scp_sub_handle s, double* xd, double* ud, double* p, int32_t* status, int32_t* iterations,
                                   double* cost, uint8_t* feas, double* defect, double* hist)
 {
-    return loop_get(s, scp_sub::LOOP_GUSTO, xd, ud, p, status, iterations, cost, feas, defect, hist);
+    return loop_get(s, RUN_GUSTO, xd, ud, p, status, iterations, cost, feas, defect, hist);
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -1164,7 +1161,7 @@ extern "C" int scp_ptr_generic_init_host(scp_sub_handle s, int B, const scp_ptr_
     if (pars->iter_max < 1 || s->nscal > 1 || s->nfun < 2) { s->err = "not a PTR template (nscal <= 1 and unused, fun[0] = virtual-control penalty, fun[1] = trust-region penalty)"; return SCP_ERR_BAD_ARGUMENT; }
     if (!(pars->q_exit >= 1.0)) { s->err = "q_exit must be >= 1 (or Inf)"; return SCP_ERR_BAD_ARGUMENT; }
     // generate_initial_guess: discretize!(guess) (ptr.jl:548-555)
-    int rc = loop_begin(s, nullptr, scp_sub::LOOP_PTR, B, pars->iter_max, pars->solver, pars->q_exit, pars->q_exit, xd, ud, p, pp);
+    int rc = loop_begin(s, nullptr, RUN_PTR_GENERIC, B, pars->iter_max, pars->solver, pars->q_exit, pars->q_exit, xd, ud, p, pp);
     if (rc != SCP_OK) return rc;
     s->pg = *pars;
     // J_aug of the guess is NaN (ptr.jl:350)
@@ -1174,7 +1171,7 @@ extern "C" int scp_ptr_generic_init_host(scp_sub_handle s, int B, const scp_ptr_
 
 extern "C" int scp_ptr_generic_iterate(scp_sub_handle s, int* n_active)
 {
-    return loop_step(s, scp_sub::LOOP_PTR, n_active, [&]() -> int {
+    return loop_step(s, RUN_PTR_GENERIC, n_active, [&]() -> int {
         scp_problem* h = s->h;
         const int B = s->B;
         scp::PtrgUpdateArgs a;
@@ -1190,7 +1187,7 @@ extern "C" int scp_ptr_generic_iterate(scp_sub_handle s, int* n_active)
 extern "C" int scp_ptr_generic_get_host(scp_sub_handle s, double* xd, double* ud, double* p, int32_t* status, int32_t* iterations,
                                         double* cost, uint8_t* feas, double* defect, double* hist)
 {
-    int rc = loop_get(s, scp_sub::LOOP_PTR, xd, ud, p, status, iterations, nullptr, feas, defect, hist);
+    int rc = loop_get(s, RUN_PTR_GENERIC, xd, ud, p, status, iterations, nullptr, feas, defect, hist);
     if (rc != SCP_OK) return rc;
     if (cost) {   // [B][4]: J, J_tr, J_vc, J_aug of the last subproblem
         SUB_TRY(hipMemcpyAsync(cost, s->post2, sizeof(double) * 4 * (size_t)s->B, hipMemcpyDeviceToHost, s->h->stream));

@@ -194,7 +194,7 @@ def run_loop(pbm, sub, fns, head, guess, pp, cost_shape, hist_width, all_reduce=
     get_host: xd, ud, p, status, iterations, cost[cost_shape], feas, defect, hist[iter_max, B, hist_width]."""
     init, iterate, get_host = fns
     xd, ud, p = guess
-    B, N, iter_max = pp.shape[0], pbm.pars.N, pbm.pars.iter_max
+    B, iter_max = pp.shape[0], pbm.pars.iter_max
     sub._check(init(sub._h, *head, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np else None, _ptr(pp) if pbm.info.npp else None))
     na = ctypes.c_int(1)
     k, n = 0, 1
@@ -202,13 +202,22 @@ def run_loop(pbm, sub, fns, head, guess, pp, cost_shape, hist_width, all_reduce=
         sub._check(iterate(sub._h, ctypes.byref(na)))
         n = na.value if all_reduce is None else all_reduce(na.value)
         k += 1
+    rc, r = read_result(pbm, B, get_host, sub._h, cost_shape, hist_width)
+    sub._check(rc)
+    return r
+
+
+def read_result(pbm, B, get_host, handle, cost_shape, hist_width):
+    """(status, outputs) of one of the get_host entry points of the C ABI, which share one signature (structured PTR run: `handle`
+    = the problem handle; the loops: the subproblem handle)"""
+    N, iter_max = pbm.pars.N, pbm.pars.iter_max
     r = SimpleNamespace(xd=np.zeros((B, N, pbm.nx)), ud=np.zeros((B, N, pbm.nu)), p=np.zeros((B, pbm.np)),
                         status=np.zeros(B, np.int32), iterations=np.zeros(B, np.int32), cost=np.zeros(cost_shape),
                         feas=np.zeros(B, np.uint8), defect=np.zeros((B, N - 1, pbm.nx)), hist=np.zeros((iter_max, B, hist_width)))
-    sub._check(get_host(sub._h, _ptr(r.xd), _ptr(r.ud), _ptr(r.p) if pbm.np else None, _ptr(r.status), _ptr(r.iterations),
-                        _ptr(r.cost), _ptr(r.feas), _ptr(r.defect), _ptr(r.hist)))
+    rc = get_host(handle, _ptr(r.xd), _ptr(r.ud), _ptr(r.p) if pbm.np else None, _ptr(r.status), _ptr(r.iterations),
+                  _ptr(r.cost), _ptr(r.feas), _ptr(r.defect), _ptr(r.hist))
     r.feas = r.feas.astype(bool)
-    return r
+    return rc, r
 
 
 class SCPSolutionBatch:

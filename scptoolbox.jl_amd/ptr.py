@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from .conic import default_options
-from .generic import GenericSubproblem, run_loop, stack_guesses
+from .generic import GenericSubproblem, _ptr as _vp, read_result, run_loop, stack_guesses
 from .scp import FOH, SCPProblem
 from .subproblem import ModelRows, build_ptr
 
@@ -64,12 +64,14 @@ class Parameters:
         # solve's iterate at mu <= 1e-10: 1 ... 5 IPM iterations per launch instead of 9 ... 16 in the second half of a 15-iteration
         # run; the mid level saves ~10 iterations in the launch after the last large move.  Same optima (levels and bounds swept on
         # the CPU twin, oracle/cpu_ptr.cpp -- the sweep switches are in its git history -- then on the 4096 batch).
+        # The fine level is this module's to set (the library has no default for it); 0 = the library's default for the others:
+        # mu 1e-1 / 1e-5 / 1e-10 for coarse / mid / very fine, deviation bounds 1e-1 / 1e-6 for mid / very fine (warm_levels, scp_api.hip)
         c.ipm_warm_mu = float(o.get("warm_mu", 1e-8))
-        c.ipm_warm_mu_coarse = float(o.get("warm_mu_coarse", 1e-1))
         c.ipm_warm_dev = float(o.get("warm_dev", 1e-3))
         c.ipm_warm_min_cold = int(o.get("warm_min_cold", 25))   # gates the COARSE level only
-        c.ipm_warm_mu_mid = float(o.get("warm_mu_mid", 1e-5)); c.ipm_warm_dev_mid = float(o.get("warm_dev_mid", 1e-1))
-        c.ipm_warm_mu_vfine = float(o.get("warm_mu_vfine", 1e-10)); c.ipm_warm_dev_vfine = float(o.get("warm_dev_vfine", 1e-6))
+        c.ipm_warm_mu_coarse = float(o.get("warm_mu_coarse", 0.0))
+        c.ipm_warm_mu_mid = float(o.get("warm_mu_mid", 0.0)); c.ipm_warm_dev_mid = float(o.get("warm_dev_mid", 0.0))
+        c.ipm_warm_mu_vfine = float(o.get("warm_mu_vfine", 0.0)); c.ipm_warm_dev_vfine = float(o.get("warm_dev_vfine", 0.0))
         c.ipm_wpe = int(o.get("wpe", 0))
         return c
 
@@ -117,8 +119,29 @@ class SCPHistoryBatch:
     dres: np.ndarray
 
 
-def _vp(a):
-    return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+# the named columns of one history record (SCP_HIST_WIDTH doubles, include/scp_mi355x.h), in the order of SCPHistoryBatch
+HIST_COLUMNS = tuple(SCPHistoryBatch.__dataclass_fields__)
+
+
+def _batch_pp(pbm, pp):
+    """pp as a contiguous [B, npp] array (None = one nominal problem)"""
+    return np.ascontiguousarray(pbm.traj.mdl.nominal_pp()[None] if pp is None else pp, dtype=np.float64)
+
+
+def _result(pbm, algo, r):
+    """(SCPSolutionBatch, SCPHistoryBatch) from the raw outputs r of a PTR get_host (scp_ptr_get_host,
+    scp_ptr_generic_get_host): xd, ud, p, status, iterations, cost[B, 4], feas, defect, hist[iter_max, B, SCP_HIST_WIDTH]."""
+    H = {k: r.hist[:, :, j] for j, k in enumerate(HIST_COLUMNS)}
+    H.update({k: H[k] > 0 for k in ("feas", "active")}, **{k: H[k].astype(int) for k in ("solver_status", "solver_iters")})
+    # final status string of the LAST subproblem solve (scp.jl:211-222)
+    failed = r.status != 0
+    last = H["solver_status"][np.maximum(r.iterations - 1, 0), np.arange(len(failed))]
+    st = ["SCP_FAILED (%s)" % SOLVER_STATUS.get(int(s), "?") if f else "SCP_SOLVED" for s, f in zip(last, failed)]
+    J_aug = r.cost[:, 3].copy()   # SCPSolution.cost = last_sol.J_aug (scp.jl:238), Inf on failure (scp.jl:219)
+    sol = SCPSolutionBatch(status=st, algo=algo, iterations=r.iterations, cost=np.where(failed, math.inf, J_aug),
+                           J=r.cost[:, 0].copy(), td=pbm.t_grid.copy(), xd=r.xd, ud=r.ud, p=r.p, J_aug=J_aug,
+                           feas=r.feas, defect=r.defect)
+    return sol, SCPHistoryBatch(**H)
 
 
 def solve(pbm, pp=None, warm=None, all_reduce=None, device_guess=False):
@@ -129,23 +152,14 @@ def solve(pbm, pp=None, warm=None, all_reduce=None, device_guess=False):
     (the per-iteration convergence all-reduce across GPUs; identity on one GPU).  device_guess: generate the
     initial guesses on the device (scp_ptr_init_guess_host).
     Returns (SCPSolutionBatch, SCPHistoryBatch)."""
-    L = _lib.lib()
     pars = pbm.pars
-    mdl = pbm.traj.mdl
-    pp = np.ascontiguousarray(mdl.nominal_pp()[None] if pp is None else pp, dtype=np.float64)
-    B = pp.shape[0]
     if pars.q_tr != math.inf or pars.q_exit != math.inf or not pbm.info.structured:
         # trust-region norms 1, 2, 4 (ptr.jl:582-739) and models without a stage-structured fast path (Starship):
         # generic conic path
-        return _solve_generic(pbm, pp, warm, all_reduce)
-    upload(pbm, pp, warm, device_guess)   # device_guess: traj.guess runs on the device, only pp is uploaded
-    na = ctypes.c_int(B)
-    while True:
-        _lib.check(L.scp_ptr_iterate(pbm.handle, ctypes.byref(na)), pbm.handle)
-        n = na.value if all_reduce is None else all_reduce(na.value)
-        if n <= 0:
-            break
-    return _collect(pbm, B)
+        return _solve_generic(pbm, _batch_pp(pbm, pp), warm, all_reduce)
+    B = upload(pbm, pp, warm, device_guess)   # device_guess: traj.guess runs on the device, only pp is uploaded
+    run_resident(pbm, all_reduce)
+    return collect(pbm, B)
 
 
 def _qnorm(v, q):
@@ -197,36 +211,22 @@ def _solve_generic(pbm, pp, warm=None, all_reduce=None):
     cp.solver = default_options(**generic_solver_options(pars.solver_opts))
     r = run_loop(pbm, sub, (L.scp_ptr_generic_init_host, L.scp_ptr_generic_iterate, L.scp_ptr_generic_get_host),
                  (B, ctypes.byref(cp)), stack_guesses(pbm, pp, warm), pp, (B, 4), _lib.HIST_WIDTH, all_reduce)
-    hist, iters, status, cost = r.hist, r.iterations, r.status, r.cost
-    keys = ("J", "J_tr", "J_vc", "J_aug", "deviation", "improv_rel", "feas", "solver_status", "solver_iters", "active", "gap",
-            "pres", "dres")
-    H = {kk: hist[:, :, j] for j, kk in enumerate(keys)}
-    last_st = np.array([int(H["solver_status"][max(int(iters[b]) - 1, 0), b]) for b in range(B)])
-    failed = status != 0
-    st = ["SCP_FAILED (%s)" % SOLVER_STATUS.get(int(last_st[b]), "?") if failed[b] else "SCP_SOLVED" for b in range(B)]
-    sol = SCPSolutionBatch(status=st, algo="PTR (backend: MI355X generic conic IPM)", iterations=iters,
-                           cost=np.where(failed, math.inf, cost[:, 3]), J=cost[:, 0].copy(), td=pbm.t_grid.copy(), xd=r.xd, ud=r.ud, p=r.p,
-                           J_aug=cost[:, 3].copy(), feas=r.feas, defect=r.defect)
-    hb = SCPHistoryBatch(**{kk: (H[kk] > 0 if kk in ("feas", "active") else (H[kk].astype(int) if kk.startswith("solver_") else H[kk]))
-                            for kk in keys})
-    return sol, hb
+    return _result(pbm, "PTR (backend: MI355X generic conic IPM)", r)
 
 
 def upload(pbm, pp=None, warm=None, device_guess=False):
     """Upload guesses + per-problem data and discretise the guess (start of PTR.solve).
     device_guess=True: only pp is uploaded, the model's guess rule runs on the device (scp_ptr_init_guess_host)."""
     L = _lib.lib()
-    mdl = pbm.traj.mdl
-    pp = np.ascontiguousarray(mdl.nominal_pp()[None] if pp is None else pp, dtype=np.float64)
+    pp = _batch_pp(pbm, pp)
     B = pp.shape[0]
-    if device_guess and warm is None:
-        cp = pbm.pars.c_struct()
-        _lib.check(L.scp_ptr_init_guess_host(pbm.handle, B, ctypes.byref(cp), _vp(pp)), pbm.handle)
-        return B
-    xd, ud, p = stack_guesses(pbm, pp, warm)
     cp = pbm.pars.c_struct()
-    _lib.check(L.scp_ptr_init_host(pbm.handle, B, ctypes.byref(cp), _vp(xd), _vp(ud), _vp(p) if pbm.np else None,
-                                   _vp(pp)), pbm.handle)
+    if device_guess and warm is None:
+        rc = L.scp_ptr_init_guess_host(pbm.handle, B, ctypes.byref(cp), _vp(pp))
+    else:
+        xd, ud, p = stack_guesses(pbm, pp, warm)
+        rc = L.scp_ptr_init_host(pbm.handle, B, ctypes.byref(cp), _vp(xd), _vp(ud), _vp(p) if pbm.np else None, _vp(pp))
+    _lib.check(rc, pbm.handle)
     return B
 
 
@@ -263,38 +263,10 @@ def kernel_timing(pbm, reset=False):
 
 
 def collect(pbm, B):
-    return _collect(pbm, B)
-
-
-def _collect(pbm, B):
-    L = _lib.lib()
-    pars = pbm.pars
-    N, nx, nu, np_ = pars.N, pbm.nx, pbm.nu, pbm.np
-    xd = np.empty((B, N, nx)); ud = np.empty((B, N, nu)); p = np.empty((B, np_))
-    status = np.zeros(B, dtype=np.int32); iters = np.zeros(B, dtype=np.int32)
-    cost = np.empty((B, 4)); feas = np.zeros(B, dtype=np.uint8); defect = np.empty((B, N - 1, nx))
-    hist = np.zeros((pars.iter_max, B, _lib.HIST_WIDTH))
-    _lib.check(L.scp_ptr_get_host(pbm.handle, _vp(xd), _vp(ud), _vp(p) if np_ else None, _vp(status), _vp(iters),
-                                  _vp(cost), _vp(feas), _vp(defect), _vp(hist)), pbm.handle)
-    # final status string of the LAST subproblem solve (scp.jl:211-222)
-    st = []
-    J = cost[:, 3].copy()   # SCPSolution.cost = last_sol.J_aug (scp.jl:238)
-    for b in range(B):
-        if status[b] == 0:
-            st.append("SCP_SOLVED")
-        else:
-            last = int(hist[max(iters[b] - 1, 0), b, 7])
-            st.append("SCP_FAILED (%s)" % SOLVER_STATUS.get(last, "?"))
-            J[b] = math.inf
-    sol = SCPSolutionBatch(status=st, algo="PTR (backend: MI355X structured IPM)", iterations=iters, cost=J,
-                           J=cost[:, 0].copy(), td=pbm.t_grid.copy(), xd=xd, ud=ud, p=p, J_aug=cost[:, 3].copy(), feas=feas.astype(bool),
-                           defect=defect)
-    h = hist
-    history = SCPHistoryBatch(J=h[:, :, 0], J_tr=h[:, :, 1], J_vc=h[:, :, 2], J_aug=h[:, :, 3], deviation=h[:, :, 4],
-                              improv_rel=h[:, :, 5], feas=h[:, :, 6] > 0, solver_status=h[:, :, 7].astype(int),
-                              solver_iters=h[:, :, 8].astype(int), active=h[:, :, 9] > 0, gap=h[:, :, 10],
-                              pres=h[:, :, 11], dres=h[:, :, 12])
-    return sol, history
+    """(SCPSolutionBatch, SCPHistoryBatch) of the resident batch (scp_ptr_get_host)."""
+    rc, r = read_result(pbm, B, _lib.lib().scp_ptr_get_host, pbm.handle, (B, 4), _lib.HIST_WIDTH)
+    _lib.check(rc, pbm.handle)
+    return _result(pbm, "PTR (backend: MI355X structured IPM)", r)
 
 
 def solve_subproblem_(pbm, xd_ref, ud_ref, p_ref, pp=None):
@@ -375,9 +347,8 @@ class SCPProblemGroup:
             self.pars = pars
         self.parts = [create(pars, traj, batch_capacity=hi - lo, device=device) for lo, hi in self.ranges]
         # sub-batches at DIFFERENT stream priorities (scp_set_stream_priority): no lockstep between their K3 launches, the short
-        # kernels of the high-priority sub-batch overtake the other's pending K3 workgroups.  SCP_STREAM_PRIORITIES=0 switches it off.
-        import os
-        if streams > 1 and os.environ.get("SCP_STREAM_PRIORITIES", "1") != "0":
+        # kernels of the high-priority sub-batch overtake the other's pending K3 workgroups
+        if streams > 1:
             for i, p in enumerate(self.parts):
                 _lib.check(_lib.lib().scp_set_stream_priority(p.handle, 1 if i == 0 else (-1 if i == streams - 1 else 0)), p.handle)
         p0 = self.parts[0]
@@ -477,13 +448,13 @@ def group_sync(grp):
 
 
 def group_collect(grp):
-    sols, hists = zip(*[_collect(p, hi - lo) for p, (lo, hi) in zip(grp.parts, grp.ranges)])
+    sols, hists = zip(*[collect(p, hi - lo) for p, (lo, hi) in zip(grp.parts, grp.ranges)])
     cat = lambda xs, ax=0: np.concatenate(xs, axis=ax)
     sol = SCPSolutionBatch(status=sum((s.status for s in sols), []), algo=sols[0].algo, iterations=cat([s.iterations for s in sols]),
                            cost=cat([s.cost for s in sols]), J=cat([s.J for s in sols]), td=sols[0].td, xd=cat([s.xd for s in sols]),
                            ud=cat([s.ud for s in sols]), p=cat([s.p for s in sols]), J_aug=cat([s.J_aug for s in sols]),
                            feas=cat([s.feas for s in sols]), defect=cat([s.defect for s in sols]))
-    hist = SCPHistoryBatch(**{f: cat([getattr(h, f) for h in hists], 1) for f in SCPHistoryBatch.__dataclass_fields__})
+    hist = SCPHistoryBatch(**{f: cat([getattr(h, f) for h in hists], 1) for f in HIST_COLUMNS})
     return sol, hist
 
 
