@@ -211,6 +211,55 @@ int scp_discretize_batch_dev(scp_handle h, int B, const double *xd, const double
 int scp_propagate_batch_host(scp_handle h, int B, const double *xd, const double *ud, const double *p, int res,
                              double *xc);
 
+/*
+ * Continuous-time audit of a batch of solutions: what a user asks of SCPSolution(history) (src/solvers/scp.jl:196-245) once
+ * xc = propagate(last_sol, pbm; res) is there -- did it arrive, did it stay inside the constraints BETWEEN the grid nodes,
+ * what did it cost -- answered on the device, fused into the propagation: no sample of xc is stored or copied.
+ *
+ * Samples tc = LinRange(0,1,res), res >= 2; xc_j = the single-shooting RK4 propagation of scp_propagate_batch_host (FOH);
+ * uc_j = the first-order-hold input at tc_j.  The model functions are called with t = tc_j and the node index k_j = the
+ * 1-based index of the last grid node <= tc_j (N at t = 1).  One record audit[SCP_AUDIT_WIDTH, B] per problem:
+ *   [0], [1]   max over the samples and rows of s(tc_j, k_j, xc_j, uc_j, p), and the tc_j where it is attained
+ *   [2], [3]   the same for the linear rows L z + Lp p + l of the convex sets X and U together, z = [xc_j; uc_j]
+ *   [4], [5]   the same for the second-order cones, as ||z_1..3|| - z_0
+ *   [6]        max_i (Lg p + lg)_i, the parameter-only rows
+ *   [7]        ||g_tc(xc(1), p, pp)||_inf, the open-loop residual of the terminal boundary condition
+ *   [8]        ||Sx^-1 (xc(1) - xd[:,N])||_inf, the open-loop drift from the discrete terminal state
+ *   [9]        the cost flown, phi(xc(1), p) + trapz over tc of Gamma(xc_j, uc_j)  (normalised time, like the discrete J)
+ *   [10]       number of samples at which any of [0], [2], [4]'s families exceeds viol_tol
+ *   [11]       1 if any sample or quantity was not finite, else 0
+ *   [12..15]   0 (reserved)
+ * On ties the first sample wins; a family without rows reports -Inf and the time 0.
+ *
+ * SCP_ERR_UNSUPPORTED (with an error text where there is a handle) for IMPULSE handles and for models with node parameters
+ * (np_node > 0, the free-flyer): a row of X at node k reads that node's own slack there, and between the nodes no such
+ * slack exists.  SCP_ERR_BAD_ARGUMENT for res < 2, a NULL audit and a missing p / pp where the model has one;
+ * SCP_ERR_BATCH_TOO_LARGE for B above the handle's capacity.
+ */
+#define SCP_AUDIT_WIDTH 16
+/*
+ * The audit of B trajectories given on the host (xd[nx,N,B], ud[nu,N,B], p[np,B], pp[npp,B]); *seconds = device time of the
+ * kernel.  Like scp_propagate_batch_host it stages its input in the handle's solution buffers and so overwrites a run's last
+ * solution (the run's pp is left alone).
+ */
+int scp_audit_batch_host(scp_handle h, int B, const double *xd, const double *ud, const double *p, const double *pp,
+                         int res, double viol_tol, double *audit, double *seconds);
+/*
+ * The audit of the batch RESIDENT in the handle: exactly the trajectories the owning run's *_get_host would return at this
+ * moment (structured PTR, SCvx, GuSTO or generic PTR) with that run's pp; problems whose SCP status is not "solved" (0) are
+ * skipped and their record is NaN.  Only SCP_AUDIT_WIDTH * B doubles cross PCIe and no buffer of the run is modified:
+ * get_host and further iterations behave as if the call had not been made.  SCP_ERR_BAD_ARGUMENT, with an error text,
+ * when no run owns the handle.
+ */
+int scp_audit_resident(scp_handle h, int res, double viol_tol, double *audit, double *seconds);
+/*
+ * The same record for ONE problem computed on the host by the same code (no device needed): xd[nx,N], ud[nu,N], p[np],
+ * pp[npp], Sx[nx] = the diagonal of the state scaling -> audit[SCP_AUDIT_WIDTH].  The counterpart of scp_model_eval_host
+ * for the audit: lets a maintainer and the CPU tests check it against the closures it replaces.
+ */
+int scp_model_audit_host(int model_id, const double *model_par, int N, const double *xd, const double *ud,
+                         const double *p, const double *pp, const double *Sx, int res, double viol_tol, double *audit);
+
 /* ------------------------------------------------------------------------ */
 /* PTR: solve_subproblem! and the outer loop                                  */
 /* ------------------------------------------------------------------------ */

@@ -1,0 +1,62 @@
+// The continuous-time audit's own translation unit: the four instantiations of audit_foh_kernel (audit_kernel.hpp), their
+// launch for the handle-level entry points of scp_api.hip, and the pure-host twin scp_model_audit_host.
+#include <hip/hip_runtime.h>
+
+#include "../../include/scp_mi355x.h"
+#include "audit_kernel.hpp"
+#include "models/double_integrator.hpp"
+#include "models/quadrotor.hpp"
+#include "models/rocket_landing.hpp"
+#include "models/starship.hpp"
+
+namespace scp {
+
+// the models the audit is defined for: FOH, no node parameters (the free-flyer's X rows read the slacks of their own node)
+template <class Fn>
+static int with_audit_model(int model_id, Fn&& fn)
+{
+    switch (model_id) {
+        case SCP_MODEL_DOUBLE_INTEGRATOR: return fn(DoubleIntegrator{});
+        case SCP_MODEL_QUADROTOR: return fn(Quadrotor{});
+        case SCP_MODEL_ROCKET_LANDING: return fn(RocketLanding{});
+        case SCP_MODEL_STARSHIP: return fn(Starship{});
+        case SCP_MODEL_FREEFLYER: return (int)SCP_ERR_UNSUPPORTED;
+        default: return (int)SCP_ERR_UNKNOWN_MODEL;
+    }
+}
+
+__global__ void audit_mask_kernel(const int* status, int* mask, int B)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) mask[b] = status[b] == 0 ? 1 : 0;
+}
+
+int audit_mask_from_status(const int* status, int* mask, int B, hipStream_t stream)
+{
+    hipLaunchKernelGGL(audit_mask_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, status, mask, B);
+    return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+}
+
+int audit_launch(int model_id, const double* model_par, const AuditArgs& a, hipStream_t stream)
+{
+    return with_audit_model(model_id, [&](auto m) -> int {
+        using M = decltype(m);
+        hipLaunchKernelGGL(audit_foh_kernel<M>, dim3((a.B + 63) / 64), dim3(64), 0, stream, a, M::make_params(model_par));
+        return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+    });
+}
+
+}  // namespace scp
+
+extern "C" int scp_model_audit_host(int model_id, const double* model_par, int N, const double* xd, const double* ud,
+                                    const double* p, const double* pp, const double* Sx, int res, double viol_tol,
+                                    double* audit)
+{
+    if (!model_par || N < 2 || !xd || !ud || !Sx || !audit || res < 2) return SCP_ERR_BAD_ARGUMENT;
+    return scp::with_audit_model(model_id, [&](auto m) -> int {
+        using M = decltype(m);
+        if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
+        scp::audit_one<M>(M::make_params(model_par), N, res, viol_tol, xd, ud, p, pp, Sx, audit);
+        return (int)SCP_OK;
+    });
+}

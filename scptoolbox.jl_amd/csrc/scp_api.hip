@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/scp_mi355x.h"
+#include "audit_kernel.hpp"
 #include "discretize_kernel.hpp"
 #include "ipm_kernel.hpp"
 #include "ipm2_kernel.hpp"
@@ -66,6 +67,9 @@ struct scp_problem {
     struct StarshipGuessState* sg = nullptr;   // device-side reference guess of the Starship model (starship_guess.hpp), lazily built
     int guess_failures = 0;                   // instances of the last scp_guess_batch_host call that fell back to the straight line
     long long* prof = nullptr;
+    // continuous-time audit (scp_audit_*): records [SCP_AUDIT_WIDTH cap], mask [cap], the host variant's pp [npp cap]; lazily built
+    double *d_audit = nullptr, *d_audit_pp = nullptr;
+    int* d_audit_mask = nullptr;
     // trajectories
     double *ref_xd = nullptr, *ref_ud = nullptr, *ref_p = nullptr;
     double *sol_xd = nullptr, *sol_ud = nullptr, *sol_p = nullptr;
@@ -1227,6 +1231,75 @@ extern "C" int scp_debug_get_stage_problem(scp_handle h, int b, double* buf, lon
 }
 
 #include "scp_generic.hpp"
+
+// ------------------------------------------------------------------------------------------
+// continuous-time audit (audit_kernel.hpp; the kernels live in audit_api.hip)
+// ------------------------------------------------------------------------------------------
+
+// what every audit entry point refuses, and the O(B) buffers of the call
+static int audit_begin(scp_problem* h, int res, const double* audit)
+{
+    if (!h) return SCP_ERR_BAD_ARGUMENT;
+    if (h->method != SCP_FOH) { h->err = "audit: FOH handles only (an IMPULSE solution has no continuous input to fly)"; return SCP_ERR_UNSUPPORTED; }
+    if (h->info.np_node > 0) {
+        h->err = "audit: models with node parameters are not supported (a row of X at node k reads that node's own slack; between the nodes there is none)";
+        return SCP_ERR_UNSUPPORTED;
+    }
+    if (res < 2 || !audit) { h->err = "audit: res >= 2 and an output array are required"; return SCP_ERR_BAD_ARGUMENT; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!h->d_audit) TRY(dalloc(h, &h->d_audit, (size_t)SCP_AUDIT_WIDTH * h->cap));
+    if (!h->d_audit_mask) TRY(dalloc(h, &h->d_audit_mask, (size_t)h->cap));
+    if (!h->d_audit_pp) TRY(dalloc(h, &h->d_audit_pp, (size_t)(h->info.npp > 0 ? h->info.npp : 1) * h->cap));
+    return SCP_OK;
+}
+
+// the kernel between the handle's two events, the records to the host, the device time
+static int audit_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, int res, double viol_tol,
+                     double* audit, double* seconds)
+{
+    AuditArgs a;
+    a.B = B; a.N = h->N; a.res = res; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p; a.pp = d_pp; a.Sx = h->d_Sx;
+    a.mask = mask; a.audit = h->d_audit;
+    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    const int rc = audit_launch(h->model_id, h->par.data(), a, h->stream);
+    if (rc != SCP_OK) { h->err = "audit: kernel launch failed"; return rc; }
+    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(audit, h->d_audit, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    stamps_collect(h);
+    return elapsed_out(h, seconds);
+}
+
+extern "C" int scp_audit_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
+                                    int res, double viol_tol, double* audit, double* seconds)
+{
+    TRY(audit_begin(h, res, audit));
+    if (B < 1 || !xd || !ud || (h->npt > 0 && !p) || (h->info.npp > 0 && !pp)) { h->err = "audit: missing input"; return SCP_ERR_BAD_ARGUMENT; }
+    if (B > h->cap) { h->err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
+    TRY(upload_traj(h, B, xd, ud, p, h->sol_xd, h->sol_ud, h->sol_p));
+    if (h->info.npp > 0)
+        HIP_TRY(h, hipMemcpyAsync(h->d_audit_pp, pp, sizeof(double) * h->info.npp * (size_t)B, hipMemcpyHostToDevice, h->stream));
+    return audit_run(h, B, traj_sol(h), h->d_audit_pp, nullptr, res, viol_tol, audit, seconds);
+}
+
+extern "C" int scp_audit_resident(scp_handle h, int res, double viol_tol, double* audit, double* seconds)
+{
+    TRY(audit_begin(h, res, audit));
+    const scp_sub* s = h->run.sub;
+    if (h->run.kind == RUN_NONE || (h->run.kind != RUN_PTR && !s)) {
+        h->err = "scp_audit_resident: no run owns the handle's trajectory buffers; start one with its init";
+        return SCP_ERR_BAD_ARGUMENT;
+    }
+    // what the owning run's get_host returns: structured PTR the last solution; the generic loops the reference until the first iteration
+    const bool ptr = h->run.kind == RUN_PTR;
+    const int B = ptr ? h->B : s->B;
+    const Traj tr = (ptr || s->iter > 0) ? traj_sol(h) : traj_ref(h);
+    if (audit_mask_from_status(ptr ? h->scp_status : s->status, h->d_audit_mask, B, h->stream) != SCP_OK) {
+        h->err = "audit: kernel launch failed";
+        return SCP_ERR_HIP;
+    }
+    return audit_run(h, B, tr, ptr ? h->d_pp : s->d_pp, h->d_audit_mask, res, viol_tol, audit, seconds);
+}
 
 
 // =====================================================================================================================

@@ -196,6 +196,7 @@ def run_loop(pbm, sub, fns, head, guess, pp, cost_shape, hist_width, all_reduce=
     xd, ud, p = guess
     B, iter_max = pp.shape[0], pbm.pars.iter_max
     sub._check(init(sub._h, *head, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np else None, _ptr(pp) if pbm.info.npp else None))
+    pbm.resident_B = B      # size of the batch the run on this handle holds (audit_resident)
     na = ctypes.c_int(1)
     k, n = 0, 1
     while k < iter_max and n > 0:

@@ -227,6 +227,7 @@ def upload(pbm, pp=None, warm=None, device_guess=False):
         xd, ud, p = stack_guesses(pbm, pp, warm)
         rc = L.scp_ptr_init_host(pbm.handle, B, ctypes.byref(cp), _vp(xd), _vp(ud), _vp(p) if pbm.np else None, _vp(pp))
     _lib.check(rc, pbm.handle)
+    pbm.resident_B = B      # size of the batch the run on this handle holds (audit_resident)
     return B
 
 

@@ -230,6 +230,95 @@ def continuous_time(sol, pbm):
     return tc, xc, sol.uc
 
 
+AUDIT_WIDTH = 16      # SCP_AUDIT_WIDTH
+_AUDIT_FIELDS = ("s_max", "t_s", "lin_max", "t_lin", "soc_max", "t_soc", "par_max", "bc_tc", "drift", "cost", "n_viol", "nonfinite")
+
+
+class AuditBatch:
+    """The records of the continuous-time audit (scp_audit_batch_host / scp_audit_resident, include/scp_mi355x.h) of a batch as
+    named arrays [B]: s_max / lin_max / soc_max = the worst value over the samples of the non-convex constraints s, of the linear
+    rows and of the second-order cones of X and U (t_s / t_lin / t_soc: the sample time where it is attained), par_max = the
+    parameter-only rows, bc_tc = the open-loop residual of the terminal condition, drift = the scaled distance of the flown end
+    point from the discrete one, cost = the cost flown, n_viol = samples above viol_tol, nonfinite = 1 where something was not
+    finite.  Problems that were skipped (failed) hold NaN everywhere.  `raw` is the [B, 16] array itself."""
+
+    def __init__(self, raw, res, viol_tol):
+        self.raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1, AUDIT_WIDTH)
+        self.res, self.viol_tol = int(res), float(viol_tol)
+        for j, name in enumerate(_AUDIT_FIELDS):
+            setattr(self, name, self.raw[:, j])
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    @property
+    def skipped(self):
+        return np.isnan(self.raw[:, 12])
+
+    def summary(self, tol_con, tol_bc):
+        """counts of instances per criterion: constraints (all four families <= tol_con over the whole flight), arrival
+        (bc_tc <= tol_bc), both, and the instances that were skipped or not finite"""
+        live = ~self.skipped & (self.nonfinite == 0)
+        with np.errstate(invalid="ignore"):
+            con = live & (np.maximum.reduce([self.s_max, self.lin_max, self.soc_max, self.par_max]) <= tol_con)
+            bc = live & (self.bc_tc <= tol_bc)
+        n = len(self)
+        return dict(total=n, skipped=int(self.skipped.sum()), nonfinite=int((~self.skipped & (self.nonfinite != 0)).sum()),
+                    constraints_pass=int(con.sum()), constraints_fail=int((live & ~con).sum()),
+                    arrival_pass=int(bc.sum()), arrival_fail=int((live & ~bc).sum()),
+                    all_pass=int((con & bc).sum()), any_fail=int((live & ~(con & bc)).sum()))
+
+
+def _audit_res(pbm, res):
+    return 2 * pbm.pars.Nsub * (pbm.pars.N - 1) if res is None else int(res)      # the rule of SCPSolution(history), scp.jl:227
+
+
+def audit(sol, pbm, pp=None, res=None, viol_tol=0.0):
+    """Continuous-time audit of the batch solution `sol` (xd[B,N,nx], ud[B,N,nu], p[B,np]; pp[B,npp] the per-problem data,
+    None = the nominal problem) on the device, fused into the propagation (scp_audit_batch_host): no sample of xc comes back.
+    The C entry point takes no mask: every trajectory given is flown, and the records of failed problems (a `status` that is
+    not SCP_SOLVED, as in `continuous_time`) are set to NaN HERE, after the call -- drop them from `sol` beforehand to save
+    their time (`audit_resident` skips them in the kernel).  Like `propagate` the call stages its input in the handle's
+    solution buffers.  Returns an AuditBatch."""
+    L = _lib.lib()
+    xd = np.ascontiguousarray(sol.xd, dtype=np.float64)
+    ud = np.ascontiguousarray(sol.ud, dtype=np.float64)
+    p = np.ascontiguousarray(sol.p, dtype=np.float64)
+    B = xd.shape[0]
+    pp = np.ascontiguousarray(np.tile(pbm.traj.mdl.nominal_pp()[None], (B, 1)) if pp is None else pp, dtype=np.float64)
+    assert pp.shape[0] == B
+    res = _audit_res(pbm, res)
+    out = np.zeros((B, AUDIT_WIDTH))
+    sec = ctypes.c_double(0.0)
+    rc = L.scp_audit_batch_host(pbm.handle, B, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np > 0 else None,
+                                _ptr(pp) if pbm.info.npp > 0 else None, res, float(viol_tol), _ptr(out), ctypes.byref(sec))
+    _lib.check(rc, pbm.handle)
+    status = getattr(sol, "status", None)
+    if status is not None:
+        out[~np.array([str(st).startswith("SCP_SOLVED") for st in status])] = np.nan
+    a = AuditBatch(out, res, viol_tol)
+    a.seconds = sec.value
+    return a
+
+
+def audit_resident(pbm, res=None, viol_tol=0.0):
+    """The same for the batch RESIDENT in the handle after (or during) a run of any loop family (scp_audit_resident): the
+    trajectories that run's get_host would return, its own pp, failed problems skipped by the kernel; 16 doubles per problem
+    come back and the run is left untouched.  The batch size is the one the run was started with through this package
+    (PTR.upload / PTR.solve, SCvx.solve, GuSTO.solve: `pbm.resident_B`).  Returns an AuditBatch."""
+    res = _audit_res(pbm, res)
+    B = getattr(pbm, "resident_B", None)
+    if B is None:
+        raise _lib.ScpError(1, "audit_resident: no run has been started on this problem")
+    # the library writes the records of ITS batch, at most batch_capacity of them: room for all, whatever this module believes
+    out = np.zeros((max(pbm.batch_capacity, B), AUDIT_WIDTH))
+    sec = ctypes.c_double(0.0)
+    _lib.check(_lib.lib().scp_audit_resident(pbm.handle, res, float(viol_tol), _ptr(out), ctypes.byref(sec)), pbm.handle)
+    a = AuditBatch(out[:B].copy(), res, viol_tol)
+    a.seconds = sec.value
+    return a
+
+
 def device_guess(pbm, pp):
     """`traj.guess(N)` for a Monte-Carlo batch evaluated on the device (scp_guess_batch_host): pp[B,npp] ->
     (xd[B,N,nx], ud[B,N,nu], p[B,np])."""
