@@ -260,6 +260,53 @@ int scp_audit_resident(scp_handle h, int res, double viol_tol, double *audit, do
 int scp_model_audit_host(int model_id, const double *model_par, int N, const double *xd, const double *ud,
                          const double *p, const double *pp, const double *Sx, int res, double viol_tol, double *audit);
 
+/*
+ * Interval-parallel audit (multiple shooting).  The single-shooting audit above accumulates its drift over the whole
+ * horizon; SCP's own feasibility criterion, the defect of discretize!, is per interval.  Here every interval k = 1 .. N-1 of
+ * the grid t_k = LinRange(0,1,N)[k] is flown from ITS OWN node over sub = max(2, ceil(res / (N - 1))) samples
+ * tc_j = LinRange(t_k, t_{k+1}, sub)[j] (the reference's subres, at least one RK4 step), one device thread per
+ * (problem, interval), and handles created with SCP_IMPULSE are audited too:
+ *   FOH      x0 = xd[:,k]; u(t) = c ud[:,k] + (1 - c) ud[:,k+1], c = (t_{k+1} - t) / (t_{k+1} - t_k), t clamped to the interval
+ *   IMPULSE  x0 = xd[:,k] + f(t_k, -k, xd[:,k], ud[:,k], p) as in scp_propagate_batch_host; the dynamics coast with u = 0; the
+ *            row families and Gamma see z_j = [xc_j; ud[:,k]], the impulse that opened the interval; ud[:,N] is never flown
+ * The model functions get the node index k at every sample but the last one, which gets k+1.  Sample 0 of an interval and
+ * the last sample of the interval before it are at the same time; both are evaluated and both count.
+ *
+ * Per-interval record intervals[SCP_AUDIT_INTERVAL_WIDTH, N-1, B]:
+ *   [0], [1]   max over the interval's samples and rows of s, and the tc_j where it is attained (first sample wins; no
+ *              rows: -Inf, 0);  [2], [3] the same for the linear rows of X and U;  [4], [5] for the cones, ||z_1..3|| - z_0
+ *   [6]        the defect ||Sx^-1 (x(t_{k+1}) - xd[:,k+1])||_inf of the flown end state
+ *   [7]        trapz of Gamma over the interval's samples
+ *   [8]        samples of this interval at which any family exceeds viol_tol
+ *   [9]        1 if anything of this interval was not finite
+ *   [10], [11] in the record of interval N-1 only: ||g_tc(x_end, p, pp)||_inf and phi(x_end, p); 0 elsewhere
+ *   [12..15]   0
+ * Summary record audit[SCP_AUDIT_WIDTH, B], the fold of the interval records IN INTERVAL ORDER (so that both outputs are
+ * independent of B, of the place of a problem in the batch and of the launch geometry), in the layout of the record above:
+ *   [0..5] the maxima with their times (strict >: the earliest interval wins a tie), [6] the parameter-only rows, [7] = [10] of
+ *   the last interval, [8] the LARGEST DEFECT over the intervals, [9] phi + (((I_1 + I_2) + ...) + I_{N-1}), [10] the sum of
+ *   the counts, [11] the OR of the flags (and of a non-finite [6] or [9]), [12] the 1-based interval of the largest defect (the first
+ *   wins), [13] 1.0 = a multiple-shooting record (single-shooting records hold 0 there), [14] sub, [15] 0.
+ * mask / failed problems: the summary and all interval records of the problem are NaN.
+ *
+ * `intervals` may be NULL: then only SCP_AUDIT_WIDTH * B doubles come back (the interval records are 128 (N-1) B bytes).
+ * Staging, ownership, masking and the error codes are those of scp_audit_batch_host / scp_audit_resident, except that IMPULSE
+ * handles are accepted; *seconds = device time of the two kernels without the copies.
+ */
+#define SCP_AUDIT_INTERVAL_WIDTH 16
+int scp_audit_intervals_batch_host(scp_handle h, int B, const double *xd, const double *ud, const double *p, const double *pp,
+                                   int res, double viol_tol, double *audit, double *intervals /* may be NULL */, double *seconds);
+int scp_audit_intervals_resident(scp_handle h, int res, double viol_tol, double *audit, double *intervals /* may be NULL */,
+                                 double *seconds);
+/*
+ * The same two outputs for ONE problem on the host by the same code: audit[SCP_AUDIT_WIDTH], intervals[SCP_AUDIT_INTERVAL_WIDTH,
+ * N-1] or NULL.  disc_method = SCP_FOH or SCP_IMPULSE; SCP_ERR_UNSUPPORTED for SCP_IMPULSE with a model without an
+ * impulsive-input form and for models with node parameters.
+ */
+int scp_model_audit_intervals_host(int model_id, const double *model_par, int N, int disc_method, const double *xd, const double *ud,
+                                   const double *p, const double *pp, const double *Sx, int res, double viol_tol,
+                                   double *audit, double *intervals /* [16, N-1] or NULL */);
+
 /* ------------------------------------------------------------------------ */
 /* PTR: solve_subproblem! and the outer loop                                  */
 /* ------------------------------------------------------------------------ */

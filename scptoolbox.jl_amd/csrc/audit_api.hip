@@ -1,6 +1,9 @@
-// The continuous-time audit's own translation unit: the four instantiations of audit_foh_kernel (audit_kernel.hpp), their
-// launch for the handle-level entry points of scp_api.hip, and the pure-host twin scp_model_audit_host.
+// The continuous-time audit's own translation unit: the four instantiations of audit_foh_kernel and the six of
+// audit_interval_kernel with their fold (audit_kernel.hpp), their launches for the handle-level entry points of scp_api.hip,
+// and the pure-host twins scp_model_audit_host and scp_model_audit_intervals_host.
 #include <hip/hip_runtime.h>
+
+#include <vector>
 
 #include "../../include/scp_mi355x.h"
 #include "audit_kernel.hpp"
@@ -46,6 +49,24 @@ int audit_launch(int model_id, const double* model_par, const AuditArgs& a, hipS
     });
 }
 
+int audit_intervals_launch(int model_id, const double* model_par, int disc_method, const AuditIntervalArgs& a, hipStream_t stream)
+{
+    return with_audit_model(model_id, [&](auto m) -> int {
+        using M = decltype(m);
+        const typename M::Params par = M::make_params(model_par);
+        const dim3 grid((unsigned)(((long)a.B * (a.N - 1) + 63) / 64)), block(64);
+        if (disc_method == SCP_IMPULSE) {
+            if constexpr (M::has_impulse) hipLaunchKernelGGL((audit_interval_kernel<M, true>), grid, block, 0, stream, a, par);
+            else return (int)SCP_ERR_UNSUPPORTED;
+        } else {
+            hipLaunchKernelGGL((audit_interval_kernel<M, false>), grid, block, 0, stream, a, par);
+        }
+        if (hipGetLastError() != hipSuccess) return (int)SCP_ERR_HIP;
+        hipLaunchKernelGGL(audit_interval_fold_kernel<M>, dim3((a.B + 63) / 64), block, 0, stream, a, par);
+        return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+    });
+}
+
 }  // namespace scp
 
 extern "C" int scp_model_audit_host(int model_id, const double* model_par, int N, const double* xd, const double* ud,
@@ -57,6 +78,32 @@ extern "C" int scp_model_audit_host(int model_id, const double* model_par, int N
         using M = decltype(m);
         if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
         scp::audit_one<M>(M::make_params(model_par), N, res, viol_tol, xd, ud, p, pp, Sx, audit);
+        return (int)SCP_OK;
+    });
+}
+
+extern "C" int scp_model_audit_intervals_host(int model_id, const double* model_par, int N, int disc_method, const double* xd,
+                                              const double* ud, const double* p, const double* pp, const double* Sx, int res,
+                                              double viol_tol, double* audit, double* intervals)
+{
+    if (!model_par || N < 2 || !xd || !ud || !Sx || !audit || res < 2) return SCP_ERR_BAD_ARGUMENT;
+    if (disc_method != SCP_FOH && disc_method != SCP_IMPULSE) return SCP_ERR_BAD_ARGUMENT;
+    return scp::with_audit_model(model_id, [&](auto m) -> int {
+        using M = decltype(m);
+        if (disc_method == SCP_IMPULSE && !M::has_impulse) return (int)SCP_ERR_UNSUPPORTED;
+        if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
+        const typename M::Params par = M::make_params(model_par);
+        const int sub = scp::audit_interval_sub(N, res);
+        std::vector<double> own;
+        if (!intervals) { own.resize((size_t)SCP_AUDIT_INTERVAL_WIDTH * (N - 1)); intervals = own.data(); }
+        for (int k0 = 0; k0 < N - 1; k0++) {
+            double* rec = intervals + (size_t)k0 * SCP_AUDIT_INTERVAL_WIDTH;
+            if constexpr (M::has_impulse) {
+                if (disc_method == SCP_IMPULSE) { scp::audit_interval_one<M, true>(par, N, sub, k0, viol_tol, xd, ud, p, pp, Sx, rec); continue; }
+            }
+            scp::audit_interval_one<M, false>(par, N, sub, k0, viol_tol, xd, ud, p, pp, Sx, rec);
+        }
+        scp::audit_interval_fold(N, sub, intervals, scp::audit_par_max<M>(par, p), M::ng > 0, audit);
         return (int)SCP_OK;
     });
 }

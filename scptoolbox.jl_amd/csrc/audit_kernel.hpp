@@ -46,16 +46,142 @@ SCP_DEV double audit_linrange(double a, double b, int n, int j)
     return (1.0 - tt) * a + tt * b;
 }
 
+// what the samples of one flight (audit_one) or of one interval (audit_interval_one) accumulate
+struct AuditAcc {
+    double s_max = -INFINITY, t_s = 0.0, l_max = -INFINITY, t_l = 0.0, c_max = -INFINITY, t_c = 0.0, n_viol = 0.0;
+    bool bad = false;
+};
+
+// Everything that is evaluated AT a sample: the three row families of z = [x; u] with the model functions called at (t, k),
+// folded into `acc`; returns the running cost Gamma(x, u) there.  The one body of both audits.
+template <class M>
+SCP_DEV double audit_sample(const typename M::Params& par, double t, int k, const double (&x)[M::nx], const double (&u)[M::nu],
+                            const double* pb, double viol_tol, const double (&Qu)[M::nu], const double (&lu)[M::nu],
+                            const double (&lx)[M::nx], AuditAcc& acc)
+{
+    constexpr int nx = M::nx, nu = M::nu, nz = nx + nu, np = M::np, npa = np > 0 ? np : 1;
+    constexpr int ns = M::ns, nsa = ns > 0 ? ns : 1, nl = M::nl, nla = nl > 0 ? nl : 1, nsoc = M::nsoc, nsoca = nsoc > 0 ? nsoc : 1;
+    const double ninf = -INFINITY;
+    bool bad = acc.bad;
+    double z[nz];
+#pragma unroll
+    for (int i = 0; i < nx; i++) z[i] = x[i];
+#pragma unroll
+    for (int i = 0; i < nu; i++) z[nx + i] = u[i];
+#pragma unroll
+    for (int i = 0; i < nz; i++) bad = bad || !__builtin_isfinite(z[i]);
+    double vs = ninf, vl = ninf, vc = ninf;
+    if constexpr (ns > 0) {
+        double s[nsa], C[nsa * nx], Dm[nsa * nu], G[nsa * npa];
+        M::s_eval(par, t, k, x, u, pb, s, C, Dm, G);       // only s survives dead-code elimination
+#pragma unroll
+        for (int i = 0; i < ns; i++) { bad = bad || !__builtin_isfinite(s[i]); vs = s[i] > vs ? s[i] : vs; }
+    }
+    if constexpr (nl > 0) {
+        double L[nla * nz], Lp[nla * npa], l[nla];
+#pragma unroll
+        for (int i = 0; i < nl * npa; i++) Lp[i] = 0.0;
+        M::lin_rows(par, t, k, L, Lp, l);
+#pragma unroll
+        for (int i = 0; i < nl; i++) {
+            double a = l[i];
+#pragma unroll
+            for (int j = 0; j < nz; j++) a += L[i * nz + j] * z[j];
+#pragma unroll
+            for (int j = 0; j < np; j++) a += Lp[i * npa + j] * pb[j];
+            bad = bad || !__builtin_isfinite(a);
+            vl = a > vl ? a : vl;
+        }
+    }
+    if constexpr (nsoc > 0) {
+        double Mm[nsoca * 4 * nz], m[nsoca * 4];
+        M::soc_rows(par, t, k, Mm, m);
+#pragma unroll
+        for (int c = 0; c < nsoc; c++) {
+            double w[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                double a = m[4 * c + r];
+#pragma unroll
+                for (int j = 0; j < nz; j++) a += Mm[(4 * c + r) * nz + j] * z[j];
+                w[r] = a;
+            }
+            const double q = sqrt(w[1] * w[1] + w[2] * w[2] + w[3] * w[3]) - w[0];
+            bad = bad || !__builtin_isfinite(q);
+            vc = q > vc ? q : vc;
+        }
+    }
+    acc.bad = bad;
+    if (vs > acc.s_max) { acc.s_max = vs; acc.t_s = t; }      // strict: on ties the first sample wins
+    if (vl > acc.l_max) { acc.l_max = vl; acc.t_l = t; }
+    if (vc > acc.c_max) { acc.c_max = vc; acc.t_c = t; }
+    if (vs > viol_tol || vl > viol_tol || vc > viol_tol) acc.n_viol += 1.0;
+    double gam = 0.0;
+#pragma unroll
+    for (int i = 0; i < nu; i++) gam += Qu[i] * u[i] * u[i] + lu[i] * u[i];
+#pragma unroll
+    for (int i = 0; i < nx; i++) gam += lx[i] * x[i];
+    return gam;
+}
+
+// max_i (Lg p + lg)_i, the parameter-only rows (-Inf without rows)
+template <class M>
+SCP_DEV double audit_par_max(const typename M::Params& par, const double* pb)
+{
+    constexpr int np = M::np, npa = np > 0 ? np : 1, ng = M::ng, nga = ng > 0 ? ng : 1;
+    double par_max = -INFINITY;
+    if constexpr (ng > 0) {
+        double Lg[nga * npa], lg[nga];
+        M::glin_rows(par, Lg, lg);
+#pragma unroll
+        for (int i = 0; i < ng; i++) {
+            double a = lg[i];
+#pragma unroll
+            for (int j = 0; j < np; j++) a += Lg[i * np + j] * pb[j];
+            par_max = a > par_max ? a : par_max;
+        }
+    }
+    return par_max;
+}
+
+// ||g_tc(x, p, pp)||_inf of a flown end state
+template <class M>
+SCP_DEV double audit_bc_tc(const typename M::Params& par, const double (&x)[M::nx], const double* pb, const double* pp, bool& bad)
+{
+    constexpr int nx = M::nx, np = M::np, npa = np > 0 ? np : 1, ntc = M::ntc, ntca = ntc > 0 ? ntc : 1;
+    double bc = 0.0;
+    if constexpr (ntc > 0) {
+        double g[ntca], H[ntca * nx], K[ntca * npa];
+        M::bc_tc(par, x, pb, pp, g, H, K);               // only g survives dead-code elimination
+#pragma unroll
+        for (int i = 0; i < ntc; i++) bc = fmax(bc, fabs(g[i]));
+        // fmax drops a NaN operand: the flag must see it
+#pragma unroll
+        for (int i = 0; i < ntc; i++) bad = bad || !__builtin_isfinite(g[i]);
+    }
+    return bc;
+}
+
+// the terminal cost phi(x, p) of a flown end state
+template <class M>
+SCP_DEV double audit_phi(const double (&x)[M::nx], const double* pb, const double (&tx)[M::nx], const double (&ctp)[M::np > 0 ? M::np : 1],
+                         const double (&cQp)[M::np > 0 ? M::np : 1])
+{
+    double phi = 0.0;
+#pragma unroll
+    for (int i = 0; i < M::nx; i++) phi += tx[i] * x[i];
+#pragma unroll
+    for (int j = 0; j < M::np; j++) phi += ctp[j] * pb[j] + cQp[j] * pb[j] * pb[j];
+    return phi;
+}
+
 // xd[nx,N], ud[nu,N], p[np], pp[npp], Sx[nx] of ONE problem -> out[SCP_AUDIT_WIDTH]
 template <class M>
 SCP_DEV void audit_one(const typename M::Params& par, int N, int res, double viol_tol, const double* xd, const double* ub,
                        const double* pb, const double* pp, const double* Sx, double* out)
 {
     static_assert(M::np_node == 0, "a row of node k would read that node's own parameters: undefined between the nodes");
-    constexpr int nx = M::nx, nu = M::nu, nz = nx + nu, np = M::np, npa = np > 0 ? np : 1, npF = M::npF, npFa = npF > 0 ? npF : 1;
-    constexpr int ns = M::ns, nsa = ns > 0 ? ns : 1, nl = M::nl, nla = nl > 0 ? nl : 1, nsoc = M::nsoc, nsoca = nsoc > 0 ? nsoc : 1;
-    constexpr int ng = M::ng, nga = ng > 0 ? ng : 1, ntc = M::ntc, ntca = ntc > 0 ? ntc : 1;
-    const double ninf = -INFINITY;
+    constexpr int nx = M::nx, nu = M::nu, np = M::np, npa = np > 0 ? np : 1, npF = M::npF, npFa = npF > 0 ? npF : 1, ng = M::ng;
 
     double x[nx];
 #pragma unroll
@@ -85,9 +211,8 @@ SCP_DEV void audit_one(const typename M::Params& par, int N, int res, double vio
     for (int i = 0; i < npa; i++) { ctp[i] = 0.0; cQp[i] = 0.0; }
     M::cost_terms(par, Qu, lu, lx, tx, ctp, cQp);
 
-    double s_max = ninf, t_s = 0.0, l_max = ninf, t_l = 0.0, c_max = ninf, t_c = 0.0;
-    double n_viol = 0.0, gam_prev = 0.0, cost_int = 0.0;
-    bool bad = false;
+    AuditAcc acc;
+    double gam_prev = 0.0, cost_int = 0.0;
 
     // everything that is evaluated AT a sample (t, x): returns the running cost Gamma there
     auto sample = [&](double t) -> double {
@@ -96,65 +221,9 @@ SCP_DEV void audit_one(const typename M::Params& par, int N, int res, double vio
         k = k < 1 ? 1 : (k > N ? N : k);
         while (k < N && !(audit_linrange(0.0, 1.0, N, k) > t)) k++;
         while (k > 1 && audit_linrange(0.0, 1.0, N, k - 1) > t) k--;
-        double z[nz], u[nu];
+        double u[nu];
         input(t, u);
-#pragma unroll
-        for (int i = 0; i < nx; i++) z[i] = x[i];
-#pragma unroll
-        for (int i = 0; i < nu; i++) z[nx + i] = u[i];
-#pragma unroll
-        for (int i = 0; i < nz; i++) bad = bad || !__builtin_isfinite(z[i]);
-        double vs = ninf, vl = ninf, vc = ninf;
-        if constexpr (ns > 0) {
-            double s[nsa], C[nsa * nx], Dm[nsa * nu], G[nsa * npa];
-            M::s_eval(par, t, k, x, u, pb, s, C, Dm, G);       // only s survives dead-code elimination
-#pragma unroll
-            for (int i = 0; i < ns; i++) { bad = bad || !__builtin_isfinite(s[i]); vs = s[i] > vs ? s[i] : vs; }
-        }
-        if constexpr (nl > 0) {
-            double L[nla * nz], Lp[nla * npa], l[nla];
-#pragma unroll
-            for (int i = 0; i < nl * npa; i++) Lp[i] = 0.0;
-            M::lin_rows(par, t, k, L, Lp, l);
-#pragma unroll
-            for (int i = 0; i < nl; i++) {
-                double a = l[i];
-#pragma unroll
-                for (int j = 0; j < nz; j++) a += L[i * nz + j] * z[j];
-#pragma unroll
-                for (int j = 0; j < np; j++) a += Lp[i * npa + j] * pb[j];
-                bad = bad || !__builtin_isfinite(a);
-                vl = a > vl ? a : vl;
-            }
-        }
-        if constexpr (nsoc > 0) {
-            double Mm[nsoca * 4 * nz], m[nsoca * 4];
-            M::soc_rows(par, t, k, Mm, m);
-#pragma unroll
-            for (int c = 0; c < nsoc; c++) {
-                double w[4];
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    double a = m[4 * c + r];
-#pragma unroll
-                    for (int j = 0; j < nz; j++) a += Mm[(4 * c + r) * nz + j] * z[j];
-                    w[r] = a;
-                }
-                const double q = sqrt(w[1] * w[1] + w[2] * w[2] + w[3] * w[3]) - w[0];
-                bad = bad || !__builtin_isfinite(q);
-                vc = q > vc ? q : vc;
-            }
-        }
-        if (vs > s_max) { s_max = vs; t_s = t; }      // strict: on ties the first sample wins
-        if (vl > l_max) { l_max = vl; t_l = t; }
-        if (vc > c_max) { c_max = vc; t_c = t; }
-        if (vs > viol_tol || vl > viol_tol || vc > viol_tol) n_viol += 1.0;
-        double gam = 0.0;
-#pragma unroll
-        for (int i = 0; i < nu; i++) gam += Qu[i] * u[i] * u[i] + lu[i] * u[i];
-#pragma unroll
-        for (int i = 0; i < nx; i++) gam += lx[i] * x[i];
-        return gam;
+        return audit_sample<M>(par, t, k, x, u, pb, viol_tol, Qu, lu, lx, acc);
     };
 
     gam_prev = sample(audit_linrange(0.0, 1.0, res, 0));
@@ -180,45 +249,21 @@ SCP_DEV void audit_one(const typename M::Params& par, int N, int res, double vio
     }
 
     // ---- quantities of the end point and of the parameters alone ----
-    double par_max = ninf;
-    if constexpr (ng > 0) {
-        double Lg[nga * npa], lg[nga];
-        M::glin_rows(par, Lg, lg);
-#pragma unroll
-        for (int i = 0; i < ng; i++) {
-            double a = lg[i];
-#pragma unroll
-            for (int j = 0; j < np; j++) a += Lg[i * np + j] * pb[j];
-            par_max = a > par_max ? a : par_max;
-        }
-    }
-    double bc = 0.0;
-    if constexpr (ntc > 0) {
-        double g[ntca], H[ntca * nx], K[ntca * npa];
-        M::bc_tc(par, x, pb, pp, g, H, K);               // only g survives dead-code elimination
-#pragma unroll
-        for (int i = 0; i < ntc; i++) bc = fmax(bc, fabs(g[i]));
-        // fmax drops a NaN operand: the flag below must see it
-#pragma unroll
-        for (int i = 0; i < ntc; i++) bad = bad || !__builtin_isfinite(g[i]);
-    }
+    const double par_max = audit_par_max<M>(par, pb);
+    const double bc = audit_bc_tc<M>(par, x, pb, pp, acc.bad);
     double drift = 0.0;
 #pragma unroll
     for (int i = 0; i < nx; i++) {
         const double d = (x[i] - xd[(long)(N - 1) * nx + i]) / Sx[i];
-        bad = bad || !__builtin_isfinite(d);
+        acc.bad = acc.bad || !__builtin_isfinite(d);
         drift = fmax(drift, fabs(d));
     }
-    double phi = 0.0;
-#pragma unroll
-    for (int i = 0; i < nx; i++) phi += tx[i] * x[i];
-#pragma unroll
-    for (int j = 0; j < np; j++) phi += ctp[j] * pb[j] + cQp[j] * pb[j] * pb[j];
+    const double phi = audit_phi<M>(x, pb, tx, ctp, cQp);
     const double cost = phi + cost_int;
-    bad = bad || !__builtin_isfinite(cost) || (ng > 0 && !__builtin_isfinite(par_max));
+    acc.bad = acc.bad || !__builtin_isfinite(cost) || (ng > 0 && !__builtin_isfinite(par_max));
 
-    out[0] = s_max; out[1] = t_s; out[2] = l_max; out[3] = t_l; out[4] = c_max; out[5] = t_c;
-    out[6] = par_max; out[7] = bc; out[8] = drift; out[9] = cost; out[10] = n_viol; out[11] = bad ? 1.0 : 0.0;
+    out[0] = acc.s_max; out[1] = acc.t_s; out[2] = acc.l_max; out[3] = acc.t_l; out[4] = acc.c_max; out[5] = acc.t_c;
+    out[6] = par_max; out[7] = bc; out[8] = drift; out[9] = cost; out[10] = acc.n_viol; out[11] = acc.bad ? 1.0 : 0.0;
 #pragma unroll
     for (int i = 12; i < SCP_AUDIT_WIDTH; i++) out[i] = 0.0;
 }
@@ -237,6 +282,196 @@ __global__ __launch_bounds__(64) void audit_foh_kernel(AuditArgs a, typename M::
     }
     audit_one<M>(par, a.N, a.res, a.viol_tol, a.xd + (long)b * a.N * M::nx, a.ud + (long)b * a.N * M::nu,
                  a.p + (long)b * np_total<M>(a.N), a.pp + (long)b * M::npp, a.Sx, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Interval-parallel audit (multiple shooting; scp_audit_intervals_*): every interval k = 1 .. N-1 is flown from ITS OWN node
+// over LinRange(t_k, t_{k+1}, sub), sub = max(2, ceil(res / (N - 1))), and reduced to one record of SCP_AUDIT_INTERVAL_WIDTH
+// doubles; the records of a problem are then folded IN INTERVAL ORDER into the summary record, so that neither output
+// depends on the batch size, on the place of a problem in the batch or on the launch geometry.
+//   FOH      x0 = xd[:,k], u(t) = the first-order hold of ud[:,k], ud[:,k+1] alone (t clamped to the interval): no search
+//   IMPULSE  x0 = xd[:,k] + M::impulse(t_k, k, xd[:,k], ud[:,k], p) as in propagate_impulse_kernel, the dynamics coast with
+//            u = 0, and the row families and Gamma see z = [x; ud[:,k]], the impulse that opened the interval
+// The model functions get the node index k at every sample but the last, which is node k+1 (decided by index).
+// ------------------------------------------------------------------------------------------------
+struct AuditIntervalArgs {
+    int B, N, sub;
+    double viol_tol;
+    const double* xd;   // [nx,N,B]
+    const double* ud;   // [nu,N,B]
+    const double* p;    // [np,B]
+    const double* pp;   // [npp,B]
+    const double* Sx;   // [nx]
+    const int* mask;    // optional [B]: problems with mask[b] == 0 are skipped, all their records are NaN
+    double* intervals;  // [SCP_AUDIT_INTERVAL_WIDTH,N-1,B]
+    double* audit;      // [SCP_AUDIT_WIDTH,B]
+};
+
+// audit_api.hip: audit_interval_kernel<M, IMP> then audit_interval_fold_kernel<M> on `stream`
+int audit_intervals_launch(int model_id, const double* model_par, int disc_method, const AuditIntervalArgs& a, hipStream_t stream);
+
+SCP_DEV int audit_interval_sub(int N, int res)
+{
+    const int sub = (res + (N - 1) - 1) / (N - 1);        // the reference's subres (discretization.jl:544) ...
+    return sub < 2 ? 2 : sub;                             // ... but at least one step per interval
+}
+
+// interval k0 (0-based) of ONE problem: xd[nx,N], ud[nu,N], p[np], pp[npp], Sx[nx] -> rec[SCP_AUDIT_INTERVAL_WIDTH]
+template <class M, bool IMP>
+SCP_DEV void audit_interval_one(const typename M::Params& par, int N, int sub, int k0, double viol_tol, const double* xd,
+                                const double* ud, const double* pb, const double* pp, const double* Sx, double* rec)
+{
+    static_assert(M::np_node == 0, "a row of node k would read that node's own parameters: undefined between the nodes");
+    static_assert(!IMP || M::has_impulse, "the model has no impulsive-input form");
+    constexpr int nx = M::nx, nu = M::nu, np = M::np, npa = np > 0 ? np : 1, npF = M::npF, npFa = npF > 0 ? npF : 1;
+    const double t0 = audit_linrange(0.0, 1.0, N, k0), t1 = audit_linrange(0.0, 1.0, N, k0 + 1);
+
+    double x[nx], ua[nu], ub[nu];
+#pragma unroll
+    for (int i = 0; i < nx; i++) x[i] = xd[(long)k0 * nx + i];
+#pragma unroll
+    for (int i = 0; i < nu; i++) { ua[i] = ud[(long)k0 * nu + i]; ub[i] = IMP ? 0.0 : ud[(long)(k0 + 1) * nu + i]; }
+    if constexpr (IMP) {
+        double dx[nx], Bi[nx * nu];
+        M::impulse(par, t0, k0 + 1, x, ua, pb, dx, Bi);
+#pragma unroll
+        for (int i = 0; i < nx; i++) x[i] += dx[i];
+    }
+    // the input the dynamics see, and the input the rows and the running cost see
+    auto input = [&](double t, double (&u)[nu]) {
+        if constexpr (IMP) {
+#pragma unroll
+            for (int i = 0; i < nu; i++) u[i] = 0.0;
+        } else {
+            t = fmax(t0, fmin(t1, t));
+            const double c = (t1 - t) / (t1 - t0);
+#pragma unroll
+            for (int i = 0; i < nu; i++) u[i] = c * ua[i] + (1.0 - c) * ub[i];
+        }
+    };
+    auto f = [&](double t, const double (&xs)[nx], double (&fx)[nx]) {
+        double u[nu], Am[nx * nx], Bmat[nx * nu], Fc[nx * npFa];
+        input(t, u);
+        M::dyn(par, t, N, xs, u, pb, fx, Am, Bmat, Fc);   // only f survives dead-code elimination
+    };
+
+    double Qu[nu], lu[nu], lx[nx], tx[nx], ctp[npa], cQp[npa];
+#pragma unroll
+    for (int i = 0; i < npa; i++) { ctp[i] = 0.0; cQp[i] = 0.0; }
+    M::cost_terms(par, Qu, lu, lx, tx, ctp, cQp);
+
+    AuditAcc acc;
+    auto sample = [&](double t, int k) -> double {
+        double u[nu];
+        if constexpr (IMP) {
+#pragma unroll
+            for (int i = 0; i < nu; i++) u[i] = ua[i];
+        } else {
+            input(t, u);
+        }
+        return audit_sample<M>(par, t, k, x, u, pb, viol_tol, Qu, lu, lx, acc);
+    };
+
+    double gam_prev = sample(audit_linrange(t0, t1, sub, 0), k0 + 1), cost_int = 0.0;
+    for (int j = 1; j < sub; j++) {
+        const double t = audit_linrange(t0, t1, sub, j - 1), tp = audit_linrange(t0, t1, sub, j), h = tp - t;
+        double k1[nx], k2[nx], k3[nx], k4[nx], tmp[nx];
+        f(t, x, k1);
+#pragma unroll
+        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h / 2 * k1[i];
+        f(t + h / 2, tmp, k2);
+#pragma unroll
+        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h / 2 * k2[i];
+        f(t + h / 2, tmp, k3);
+#pragma unroll
+        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h * k3[i];
+        f(t + h, tmp, k4);
+#pragma unroll
+        for (int i = 0; i < nx; i++) x[i] = x[i] + h / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+        M::action(x);
+        const double gam = sample(tp, j == sub - 1 ? k0 + 2 : k0 + 1);
+        cost_int += 0.5 * h * (gam + gam_prev);
+        gam_prev = gam;
+    }
+
+    double defect = 0.0;
+#pragma unroll
+    for (int i = 0; i < nx; i++) {
+        const double d = (x[i] - xd[(long)(k0 + 1) * nx + i]) / Sx[i];
+        acc.bad = acc.bad || !__builtin_isfinite(d);
+        defect = fmax(defect, fabs(d));
+    }
+    double bc = 0.0, phi = 0.0;
+    if (k0 == N - 2) {                                    // the end of the horizon: the last interval carries it
+        bc = audit_bc_tc<M>(par, x, pb, pp, acc.bad);
+        phi = audit_phi<M>(x, pb, tx, ctp, cQp);
+    }
+    acc.bad = acc.bad || !__builtin_isfinite(cost_int) || !__builtin_isfinite(phi);
+
+    rec[0] = acc.s_max; rec[1] = acc.t_s; rec[2] = acc.l_max; rec[3] = acc.t_l; rec[4] = acc.c_max; rec[5] = acc.t_c;
+    rec[6] = defect; rec[7] = cost_int; rec[8] = acc.n_viol; rec[9] = acc.bad ? 1.0 : 0.0; rec[10] = bc; rec[11] = phi;
+#pragma unroll
+    for (int i = 12; i < SCP_AUDIT_INTERVAL_WIDTH; i++) rec[i] = 0.0;
+}
+
+// The ordered fold of the N-1 interval records recs[SCP_AUDIT_INTERVAL_WIDTH, N-1] of ONE problem into out[SCP_AUDIT_WIDTH]
+// (the layout of the single-shooting record).  Strict comparisons: the earliest interval wins a tie.  The cost is
+// phi + (((I_1 + I_2) + ...) + I_{N-1}); the flag also covers a non-finite par_max where the model has such rows.
+SCP_DEV void audit_interval_fold(int N, int sub, const double* recs, double par_max, bool has_par_rows, double* out)
+{
+    double vmax[3] = {-INFINITY, -INFINITY, -INFINITY}, tmax[3] = {0.0, 0.0, 0.0};
+    double dmax = -INFINITY, kmax = 0.0, integral = 0.0, n_viol = 0.0;
+    bool bad = has_par_rows && !__builtin_isfinite(par_max);
+    for (int k = 0; k < N - 1; k++) {
+        const double* r = recs + (long)k * SCP_AUDIT_INTERVAL_WIDTH;
+#pragma unroll
+        for (int f = 0; f < 3; f++)
+            if (r[2 * f] > vmax[f]) { vmax[f] = r[2 * f]; tmax[f] = r[2 * f + 1]; }
+        if (r[6] > dmax) { dmax = r[6]; kmax = (double)(k + 1); }
+        integral += r[7];
+        n_viol += r[8];
+        bad = bad || r[9] != 0.0;
+    }
+    const double* last = recs + (long)(N - 2) * SCP_AUDIT_INTERVAL_WIDTH;
+    const double cost = last[11] + integral;
+    bad = bad || !__builtin_isfinite(cost);
+    out[0] = vmax[0]; out[1] = tmax[0]; out[2] = vmax[1]; out[3] = tmax[1]; out[4] = vmax[2]; out[5] = tmax[2];
+    out[6] = par_max; out[7] = last[10]; out[8] = dmax; out[9] = cost; out[10] = n_viol; out[11] = bad ? 1.0 : 0.0;
+    out[12] = kmax; out[13] = 1.0; out[14] = (double)sub; out[15] = 0.0;
+}
+
+// one thread per (problem, interval), gid = b (N-1) + k0, blocks of one wavefront like propagate_impulse_kernel: neighbouring
+// lanes fly neighbouring intervals of the same problem, all with the same trip count
+template <class M, bool IMP>
+__global__ __launch_bounds__(64) void audit_interval_kernel(AuditIntervalArgs a, typename M::Params par)
+{
+    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    if (gid >= (long)a.B * (a.N - 1)) return;
+    const int b = (int)(gid / (a.N - 1)), k0 = (int)(gid % (a.N - 1));
+    double* rec = a.intervals + gid * SCP_AUDIT_INTERVAL_WIDTH;
+    if (a.mask != nullptr && a.mask[b] == 0) {
+#pragma unroll
+        for (int i = 0; i < SCP_AUDIT_INTERVAL_WIDTH; i++) rec[i] = NAN;
+        return;
+    }
+    audit_interval_one<M, IMP>(par, a.N, a.sub, k0, a.viol_tol, a.xd + (long)b * a.N * M::nx, a.ud + (long)b * a.N * M::nu,
+                               a.p + (long)b * np_total<M>(a.N), a.pp + (long)b * M::npp, a.Sx, rec);
+}
+
+// one thread per problem: its N-1 records in interval order -> the summary record
+template <class M>
+__global__ __launch_bounds__(64) void audit_interval_fold_kernel(AuditIntervalArgs a, typename M::Params par)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.B) return;
+    double* out = a.audit + (long)b * SCP_AUDIT_WIDTH;
+    if (a.mask != nullptr && a.mask[b] == 0) {
+#pragma unroll
+        for (int i = 0; i < SCP_AUDIT_WIDTH; i++) out[i] = NAN;
+        return;
+    }
+    audit_interval_fold(a.N, a.sub, a.intervals + (long)b * (a.N - 1) * SCP_AUDIT_INTERVAL_WIDTH,
+                        audit_par_max<M>(par, a.p + (long)b * np_total<M>(a.N)), M::ng > 0, out);
 }
 
 }  // namespace scp

@@ -69,6 +69,7 @@ struct scp_problem {
     long long* prof = nullptr;
     // continuous-time audit (scp_audit_*): records [SCP_AUDIT_WIDTH cap], mask [cap], the host variant's pp [npp cap]; lazily built
     double *d_audit = nullptr, *d_audit_pp = nullptr;
+    double* d_audit_intervals = nullptr;   // [SCP_AUDIT_INTERVAL_WIDTH (N-1) cap], scp_audit_intervals_*; lazily built
     int* d_audit_mask = nullptr;
     // trajectories
     double *ref_xd = nullptr, *ref_ud = nullptr, *ref_p = nullptr;
@@ -1236,11 +1237,11 @@ extern "C" int scp_debug_get_stage_problem(scp_handle h, int b, double* buf, lon
 // continuous-time audit (audit_kernel.hpp; the kernels live in audit_api.hip)
 // ------------------------------------------------------------------------------------------
 
-// what every audit entry point refuses, and the O(B) buffers of the call
-static int audit_begin(scp_problem* h, int res, const double* audit)
+// what every audit entry point refuses, and the O(B) buffers of the call; the interval audit flies IMPULSE handles too
+static int audit_begin(scp_problem* h, int res, const double* audit, bool foh_only = true)
 {
     if (!h) return SCP_ERR_BAD_ARGUMENT;
-    if (h->method != SCP_FOH) { h->err = "audit: FOH handles only (an IMPULSE solution has no continuous input to fly)"; return SCP_ERR_UNSUPPORTED; }
+    if (foh_only && h->method != SCP_FOH) { h->err = "audit: FOH handles only (an IMPULSE solution has no continuous input to fly)"; return SCP_ERR_UNSUPPORTED; }
     if (h->info.np_node > 0) {
         h->err = "audit: models with node parameters are not supported (a row of X at node k reads that node's own slack; between the nodes there is none)";
         return SCP_ERR_UNSUPPORTED;
@@ -1270,35 +1271,90 @@ static int audit_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, 
     return elapsed_out(h, seconds);
 }
 
-extern "C" int scp_audit_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
-                                    int res, double viol_tol, double* audit, double* seconds)
+// the host variants' input: trajectories into the solution buffers, pp into the audit's own buffer (the run's pp is left alone)
+static int audit_stage_host(scp_problem* h, int B, const double* xd, const double* ud, const double* p, const double* pp)
 {
-    TRY(audit_begin(h, res, audit));
     if (B < 1 || !xd || !ud || (h->npt > 0 && !p) || (h->info.npp > 0 && !pp)) { h->err = "audit: missing input"; return SCP_ERR_BAD_ARGUMENT; }
     if (B > h->cap) { h->err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
     TRY(upload_traj(h, B, xd, ud, p, h->sol_xd, h->sol_ud, h->sol_p));
     if (h->info.npp > 0)
         HIP_TRY(h, hipMemcpyAsync(h->d_audit_pp, pp, sizeof(double) * h->info.npp * (size_t)B, hipMemcpyHostToDevice, h->stream));
+    return SCP_OK;
+}
+
+extern "C" int scp_audit_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
+                                    int res, double viol_tol, double* audit, double* seconds)
+{
+    TRY(audit_begin(h, res, audit));
+    TRY(audit_stage_host(h, B, xd, ud, p, pp));
     return audit_run(h, B, traj_sol(h), h->d_audit_pp, nullptr, res, viol_tol, audit, seconds);
+}
+
+// the batch a resident audit flies: what the owning run's get_host returns (structured PTR: the last solution; the generic loops:
+// the reference until the first iteration), that run's pp, and in d_audit_mask its solved instances
+struct AuditSource { int B; Traj tr; const double* d_pp; };
+static int audit_resident_source(scp_problem* h, const char* no_run, AuditSource* src)
+{
+    const scp_sub* s = h->run.sub;
+    if (h->run.kind == RUN_NONE || (h->run.kind != RUN_PTR && !s)) { h->err = no_run; return SCP_ERR_BAD_ARGUMENT; }
+    const bool ptr = h->run.kind == RUN_PTR;
+    src->B = ptr ? h->B : s->B;
+    src->tr = (ptr || s->iter > 0) ? traj_sol(h) : traj_ref(h);
+    src->d_pp = ptr ? h->d_pp : s->d_pp;
+    if (audit_mask_from_status(ptr ? h->scp_status : s->status, h->d_audit_mask, src->B, h->stream) != SCP_OK) {
+        h->err = "audit: kernel launch failed";
+        return SCP_ERR_HIP;
+    }
+    return SCP_OK;
 }
 
 extern "C" int scp_audit_resident(scp_handle h, int res, double viol_tol, double* audit, double* seconds)
 {
     TRY(audit_begin(h, res, audit));
-    const scp_sub* s = h->run.sub;
-    if (h->run.kind == RUN_NONE || (h->run.kind != RUN_PTR && !s)) {
-        h->err = "scp_audit_resident: no run owns the handle's trajectory buffers; start one with its init";
-        return SCP_ERR_BAD_ARGUMENT;
+    AuditSource src;
+    TRY(audit_resident_source(h, "scp_audit_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
+    return audit_run(h, src.B, src.tr, src.d_pp, h->d_audit_mask, res, viol_tol, audit, seconds);
+}
+
+// interval-parallel audit: the flight kernel and the ordered fold between the handle's two events, then the copies
+static int audit_intervals_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, int res, double viol_tol,
+                               double* audit, double* intervals, double* seconds)
+{
+    const size_t nrec = (size_t)SCP_AUDIT_INTERVAL_WIDTH * (h->N - 1);
+    if (!h->d_audit_intervals) TRY(dalloc(h, &h->d_audit_intervals, nrec * h->cap));
+    AuditIntervalArgs a;
+    a.B = B; a.N = h->N; a.sub = audit_interval_sub(h->N, res); a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
+    a.pp = d_pp; a.Sx = h->d_Sx; a.mask = mask; a.intervals = h->d_audit_intervals; a.audit = h->d_audit;
+    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    const int rc = audit_intervals_launch(h->model_id, h->par.data(), (int)h->method, a, h->stream);
+    if (rc != SCP_OK) {
+        h->err = rc == SCP_ERR_HIP ? "audit: kernel launch failed" : "audit: IMPULSE handle of a model without an impulsive-input form";
+        return rc;
     }
-    // what the owning run's get_host returns: structured PTR the last solution; the generic loops the reference until the first iteration
-    const bool ptr = h->run.kind == RUN_PTR;
-    const int B = ptr ? h->B : s->B;
-    const Traj tr = (ptr || s->iter > 0) ? traj_sol(h) : traj_ref(h);
-    if (audit_mask_from_status(ptr ? h->scp_status : s->status, h->d_audit_mask, B, h->stream) != SCP_OK) {
-        h->err = "audit: kernel launch failed";
-        return SCP_ERR_HIP;
-    }
-    return audit_run(h, B, tr, ptr ? h->d_pp : s->d_pp, h->d_audit_mask, res, viol_tol, audit, seconds);
+    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(audit, h->d_audit, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    if (intervals)
+        HIP_TRY(h, hipMemcpyAsync(intervals, h->d_audit_intervals, sizeof(double) * nrec * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    stamps_collect(h);
+    return elapsed_out(h, seconds);
+}
+
+extern "C" int scp_audit_intervals_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p,
+                                              const double* pp, int res, double viol_tol, double* audit, double* intervals,
+                                              double* seconds)
+{
+    TRY(audit_begin(h, res, audit, false));
+    TRY(audit_stage_host(h, B, xd, ud, p, pp));
+    return audit_intervals_run(h, B, traj_sol(h), h->d_audit_pp, nullptr, res, viol_tol, audit, intervals, seconds);
+}
+
+extern "C" int scp_audit_intervals_resident(scp_handle h, int res, double viol_tol, double* audit, double* intervals, double* seconds)
+{
+    TRY(audit_begin(h, res, audit, false));
+    AuditSource src;
+    TRY(audit_resident_source(h, "scp_audit_intervals_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
+    return audit_intervals_run(h, src.B, src.tr, src.d_pp, h->d_audit_mask, res, viol_tol, audit, intervals, seconds);
 }
 
 

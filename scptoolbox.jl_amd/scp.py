@@ -319,6 +319,78 @@ def audit_resident(pbm, res=None, viol_tol=0.0):
     return a
 
 
+AUDIT_INTERVAL_WIDTH = 16      # SCP_AUDIT_INTERVAL_WIDTH
+
+
+class IntervalAuditBatch(AuditBatch):
+    """The interval-parallel (multiple-shooting) audit of a batch (scp_audit_intervals_batch_host / scp_audit_intervals_resident):
+    every interval flown from its own node.  An AuditBatch of the summary records -- there `drift` holds the LARGEST per-interval
+    defect, also available as `defect` -- plus `intervals` [B, N-1, 16], the per-interval records (None when they were not
+    asked for), `worst_interval` [B] = the 1-based interval of the largest defect (-1 for skipped problems) and `sub`, the
+    samples per interval."""
+
+    def __init__(self, raw, res, viol_tol, sub, intervals=None):
+        super().__init__(raw, res, viol_tol)
+        self.sub = int(sub)
+        self.intervals = None if intervals is None else np.ascontiguousarray(intervals, dtype=np.float64)
+        self.defect = self.raw[:, 8]
+        self.worst_interval = np.where(np.isnan(self.raw[:, 12]), -1.0, self.raw[:, 12]).astype(np.int64)
+
+
+def _interval_sub(N, res):
+    return max(2, -(-int(res) // (N - 1)))
+
+
+def audit_intervals(sol, pbm, pp=None, res=None, viol_tol=0.0, intervals=True):
+    """Interval-parallel audit of the batch solution `sol` (scp_audit_intervals_batch_host): like `audit`, but every interval
+    restarts from its own node (FOH and IMPULSE handles), one device thread per (problem, interval).  `intervals=False` leaves
+    the per-interval records on the device (128 (N-1) bytes per problem).  `sol.status` masks as in `audit`.  Returns an
+    IntervalAuditBatch."""
+    L = _lib.lib()
+    xd = np.ascontiguousarray(sol.xd, dtype=np.float64)
+    ud = np.ascontiguousarray(sol.ud, dtype=np.float64)
+    p = np.ascontiguousarray(sol.p, dtype=np.float64)
+    B, N = xd.shape[0], pbm.pars.N
+    pp = np.ascontiguousarray(np.tile(pbm.traj.mdl.nominal_pp()[None], (B, 1)) if pp is None else pp, dtype=np.float64)
+    assert pp.shape[0] == B
+    res = _audit_res(pbm, res)
+    out = np.zeros((B, AUDIT_WIDTH))
+    recs = np.zeros((B, N - 1, AUDIT_INTERVAL_WIDTH)) if intervals else None
+    sec = ctypes.c_double(0.0)
+    rc = L.scp_audit_intervals_batch_host(pbm.handle, B, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np > 0 else None,
+                                          _ptr(pp) if pbm.info.npp > 0 else None, res, float(viol_tol), _ptr(out),
+                                          _ptr(recs) if intervals else None, ctypes.byref(sec))
+    _lib.check(rc, pbm.handle)
+    status = getattr(sol, "status", None)
+    if status is not None:
+        bad = ~np.array([str(st).startswith("SCP_SOLVED") for st in status])
+        out[bad] = np.nan
+        if intervals:
+            recs[bad] = np.nan
+    a = IntervalAuditBatch(out, res, viol_tol, _interval_sub(N, res), recs)
+    a.seconds = sec.value
+    return a
+
+
+def audit_intervals_resident(pbm, res=None, viol_tol=0.0, intervals=True):
+    """The same for the batch RESIDENT in the handle (scp_audit_intervals_resident): the trajectories the owning run's get_host
+    would return, its own pp, failed problems skipped by the kernels; the run is left untouched.  Returns an
+    IntervalAuditBatch."""
+    res = _audit_res(pbm, res)
+    B, N = getattr(pbm, "resident_B", None), pbm.pars.N
+    if B is None:
+        raise _lib.ScpError(1, "audit_intervals_resident: no run has been started on this problem")
+    cap = max(pbm.batch_capacity, B)      # room for the library's own batch, whatever this module believes
+    out = np.zeros((cap, AUDIT_WIDTH))
+    recs = np.zeros((cap, N - 1, AUDIT_INTERVAL_WIDTH)) if intervals else None
+    sec = ctypes.c_double(0.0)
+    _lib.check(_lib.lib().scp_audit_intervals_resident(pbm.handle, res, float(viol_tol), _ptr(out), _ptr(recs) if intervals else None,
+                                                       ctypes.byref(sec)), pbm.handle)
+    a = IntervalAuditBatch(out[:B].copy(), res, viol_tol, _interval_sub(N, res), recs[:B].copy() if intervals else None)
+    a.seconds = sec.value
+    return a
+
+
 def device_guess(pbm, pp):
     """`traj.guess(N)` for a Monte-Carlo batch evaluated on the device (scp_guess_batch_host): pp[B,npp] ->
     (xd[B,N,nx], ud[B,N,nu], p[B,np])."""
