@@ -60,7 +60,8 @@ typedef enum {
     SCP_MODEL_QUADROTOR = 1,         /* test/examples/quadrotor              */
     SCP_MODEL_ROCKET_LANDING = 2,    /* builder-defined over rocket_landing  */
     SCP_MODEL_STARSHIP = 3,          /* test/examples/starship_flip          */
-    SCP_MODEL_FREEFLYER = 4          /* test/examples/freeflyer: p = [t_f; delta(6, N)] (np = 1 global + np_node = 6) */
+    SCP_MODEL_FREEFLYER = 4,         /* test/examples/freeflyer: p = [t_f; delta(6, N)] (np = 1 global + np_node = 6) */
+    SCP_MODEL_OSCILLATOR = 5         /* test/examples/oscillator: actuator deadband, p = l1r(N) (np = 0, np_node = 1), ntc = 0 */
 } scp_model_id;
 
 /* DiscretizationType, src/parser/problem.jl:52 */
@@ -69,8 +70,9 @@ typedef enum { SCP_FOH = 0, SCP_IMPULSE = 1 } scp_disc_method;
 /* Static description of a model (dimensions the caller needs to size buffers).
  *
  * PARAMETER VECTOR.  p = [global parameters (np); node parameters (np_node, N) column-major]: its length is
- * np + np_node * N.  Only the free-flyer has node parameters (p = [t_f; delta(6, N)], one room-SDF slack per room and node,
- * test/examples/freeflyer/parameters.jl:121-128).  Dynamics, boundary conditions and parameter-only rows see the
+ * np + np_node * N.  Two models have node parameters: the free-flyer (p = [t_f; delta(6, N)], one room-SDF slack per room and
+ * node, test/examples/freeflyer/parameters.jl:121-128) and the oscillator (p = l1r(N), one position one-norm slack
+ * per node, test/examples/oscillator/parameters.jl:79, whose slacks also enter the running cost).  Dynamics, boundary conditions and parameter-only rows see the
  * global parameters; the constraints of node k (X rows, s) additionally see that node's own np_node parameters, and their
  * parameter Jacobians are COMPACT: np + np_node columns, column j < np = global parameter j, column np + i = entry
  * np + np_node (k - 1) + i of p. */
@@ -87,7 +89,7 @@ typedef struct {
                       /* through the generic conic path only (scp_sub_*, scp_scvx_*, scp_gusto_*)                  */
     int has_subproblem; /* 0: only discretize! / propagate / the initial guess exist; the subproblem entry points return
                            SCP_ERR_UNSUPPORTED (no such model at present) */
-    int np_node;      /* parameters per node (see above); 0 for every model but the free-flyer                      */
+    int np_node;      /* parameters per node (see above): free-flyer 6, oscillator 1, every other model 0           */
     int global_rows_in_X; /* 1: the parameter-only rows are members of the convex STATE set X (soft under GuSTO and repeated
                            at every node, freeflyer/definition.jl:318-331), 0: of the input set U (hard, kept once)   */
     int linf_groups, linf_rows; /* the first linf_groups * linf_rows linear rows are LINF cones lowered to rows (MOI's
@@ -117,6 +119,21 @@ typedef struct {
 } scp_problem_desc;
 
 int scp_model_query(int model_id, scp_model_info *info);
+
+/*
+ * Model constants that may change after scp_problem_create.  The reference keeps the model as mutable user data (traj.mdl) and
+ * its homotopy examples change one constant between warm-started solves of ONE problem object (oscillator/tests.jl:60-77:
+ * mdl.traj.kappa1).  Here a model marks the entries of its parameter blob that enter device-evaluated closures only (dynamics, s,
+ * boundary conditions): mask[npar], 1 = may change.  Entries the host formulation froze into a template, the scaling or the cost
+ * constant are never marked.  Oscillator: kappa1 (index 5); every other model: none.
+ *
+ * scp_problem_set_model_par replaces the handle's copy of the blob.  It returns SCP_ERR_BAD_ARGUMENT (message in scp_last_error)
+ * and changes nothing if an unmarked entry differs from the handle's.  Every kernel receives the model constants BY VALUE at its
+ * launch, so the new values hold for everything enqueued after the call and the change is ordered with the handle's stream: no
+ * synchronisation is needed, before or after.
+ */
+int scp_model_par_mutable(int model_id, int *mask /* [npar], 1 = may change after create */);
+int scp_problem_set_model_par(scp_handle h, const double *model_par /* [npar] */);
 
 /*
  * Host-side evaluation of a compiled model's convex path constraints and cost at node k (1-based, t_k =
@@ -634,6 +651,16 @@ int scp_ptr_generic_init_host(scp_sub_handle sub, int B, const scp_ptr_generic_p
 int scp_ptr_generic_iterate(scp_sub_handle sub, int *n_active);
 int scp_ptr_generic_get_host(scp_sub_handle sub, double *xd, double *ud, double *p, int32_t *status, int32_t *iterations,
                              double *cost, uint8_t *feas, double *defect, double *hist);
+/*
+ * Device-resident continuation: what PTR.solve(pbm, warm) does with warm = the run's own last solutions (ptr.jl:448-466,
+ * scp.jl:532-539), without the batch leaving the device.  Every instance's last solution -- of the last iteration it ran,
+ * failed instances included -- becomes its reference; status, iteration count, history and cost records are cleared, J_aug of
+ * the reference is NaN and every instance is active again; the reference is discretised under the handle's CURRENT model
+ * constants (scp_problem_set_model_par).  pars: the parameters of the new stage, or NULL to keep the run's.  iterate / get_host
+ * work afterwards as after init and get_host reports the current stage.  SCP_ERR_BAD_ARGUMENT unless a generic PTR run of `sub`
+ * owns the problem handle.
+ */
+int scp_ptr_generic_continue(scp_sub_handle sub, const scp_ptr_generic_params *pars /* NULL: as before */);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Multi-GPU behind the boundary (reference: the sequential Monte-Carlo loop `for trial = 1:num_trials`,

@@ -11,6 +11,8 @@ from .scp import FOH, IMPULSE, DLTV, SCPProblem, SCPScaling, SubproblemSolutionB
 from .problem import TrajectoryProblem  # noqa: F401
 from . import ptr as PTR  # noqa: F401
 from . import dist  # noqa: F401
+from . import homotopy  # noqa: F401
+from .homotopy import Homotopy  # noqa: F401
 from . import conic  # noqa: F401
 from . import affine, subproblem, generic  # noqa: F401
 from . import scvx as SCvx  # noqa: F401

@@ -103,6 +103,7 @@ SCVX_HIST_WIDTH = 16
 
 # every symbol include/scp_mi355x.h declares
 EXPORTS = [
+    "scp_model_par_mutable", "scp_problem_set_model_par", "scp_ptr_generic_continue",
     "scp_model_query", "scp_model_rows", "scp_model_state_indicators", "scp_model_eval_host", "scp_problem_create", "scp_problem_destroy", "scp_sync", "scp_last_error", "scp_set_stream_priority",
     "scp_discretize_batch_host", "scp_discretize_batch_dev", "scp_set_discretize_precision",
     "scp_ptr_init_host", "scp_ptr_iterate", "scp_ptr_get_host", "scp_ptr_solve_batch_host",
@@ -204,6 +205,9 @@ def lib():
         L.scp_ptr_generic_init_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ScpPtrGenericParams)] + [ctypes.c_void_p] * 4
         L.scp_ptr_generic_iterate.argtypes = [ctypes.c_void_p, c_int_p]
         L.scp_ptr_generic_get_host.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
+        L.scp_ptr_generic_continue.argtypes = [ctypes.c_void_p, ctypes.POINTER(ScpPtrGenericParams)]
+        L.scp_model_par_mutable.argtypes = [ctypes.c_int, c_int_p]
+        L.scp_problem_set_model_par.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.scp_comm_unique_id.argtypes = [ctypes.c_void_p]
         L.scp_comm_preflight.argtypes = [ctypes.c_int]
         L.scp_comm_create.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]

@@ -14,7 +14,8 @@
 
 namespace scp {
 
-// the models the audit is defined for: FOH, no node parameters (the free-flyer's X rows read the slacks of their own node)
+// the models the audit is defined for: FOH, no node parameters (the X rows of the free-flyer and of the oscillator read the
+// slacks of their own node)
 template <class Fn>
 static int with_audit_model(int model_id, Fn&& fn)
 {
@@ -24,6 +25,7 @@ static int with_audit_model(int model_id, Fn&& fn)
         case SCP_MODEL_ROCKET_LANDING: return fn(RocketLanding{});
         case SCP_MODEL_STARSHIP: return fn(Starship{});
         case SCP_MODEL_FREEFLYER: return (int)SCP_ERR_UNSUPPORTED;
+        case SCP_MODEL_OSCILLATOR: return (int)SCP_ERR_UNSUPPORTED;
         default: return (int)SCP_ERR_UNKNOWN_MODEL;
     }
 }

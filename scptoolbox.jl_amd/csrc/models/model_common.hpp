@@ -24,6 +24,13 @@ SCP_DEV void zero(double (&a)[N])
 // np + np_node (k - 1) + i of p.
 struct ModelDefaults {
     static constexpr int np_node = 0;
+    // the node entries of cost_terms' tp / Qp are coefficients of the RUNNING cost Gamma: node k's term carries the trapezoid
+    // weight w_k (oscillator/definition.jl:116-142).  false: terminal-style terms, summed unweighted (free-flyer)
+    static constexpr bool node_par_in_running_cost = false;
+    // entry i of the model parameter blob may change after scp_problem_create (scp_problem_set_model_par): true only for
+    // constants that enter device-evaluated closures alone (dynamics, s, boundary conditions) -- never for what the host
+    // formulation froze into a template, the scaling or cost_const
+    static constexpr bool par_mutable(int) { return false; }
     // the parameter-only rows (glin_rows) are members of the convex STATE set X (soft under GuSTO, repeated at every
     // node: freeflyer/definition.jl:318-331) instead of the input set U (hard, kept once: quadrotor/definition.jl:223-250)
     static constexpr bool global_rows_in_X = false;

@@ -22,6 +22,7 @@
 #include "models/rocket_landing.hpp"
 #include "models/starship.hpp"
 #include "models/freeflyer.hpp"
+#include "models/oscillator.hpp"
 #include "ptr_kernels.hpp"
 #include "sharded_loop.hpp"
 #include "starship_guess.hpp"
@@ -150,6 +151,7 @@ static int with_model(int model_id, Fn&& fn)
         case SCP_MODEL_ROCKET_LANDING: return fn(RocketLanding{});
         case SCP_MODEL_STARSHIP: return fn(Starship{});
         case SCP_MODEL_FREEFLYER: return fn(Freeflyer{});
+        case SCP_MODEL_OSCILLATOR: return fn(Oscillator{});
         default: return SCP_ERR_UNKNOWN_MODEL;
     }
 }
@@ -269,6 +271,17 @@ extern "C" int scp_model_eval_host(int model_id, const double* model_par, int N,
         int n = 0;
         for_each_x_indicator<M>(P, t, k, x, p, N, [&](double v) { if (q) q[n] = v; n++; });
         if (nq) *nq = n;
+        return (int)SCP_OK;
+    });
+}
+
+// Which entries of a model's parameter blob may change after scp_problem_create (M::par_mutable, model_common.hpp)
+extern "C" int scp_model_par_mutable(int model_id, int* mask)
+{
+    if (!mask) return SCP_ERR_BAD_ARGUMENT;
+    return with_model(model_id, [&](auto m) {
+        using M = decltype(m);
+        for (int i = 0; i < M::npar; i++) mask[i] = M::par_mutable(i) ? 1 : 0;
         return (int)SCP_OK;
     });
 }
@@ -422,6 +435,25 @@ extern "C" int scp_problem_create(const scp_problem_desc* d, scp_handle* out)
         HIP_TRY(h, hipMemcpy(h->d_Sp, h->Sp.data(), (size_t)npt * D, hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(h->d_cp, h->cp.data(), (size_t)npt * D, hipMemcpyHostToDevice));
     }
+    return SCP_OK;
+}
+
+// Replace the handle's copy of the model constants.  Every kernel takes M::Params BY VALUE at its launch (make_params(h->par)),
+// so the change applies to the launches enqueued after this call and is ordered with the handle's stream by construction: no
+// synchronisation, nothing on the device to update.  Only the entries the model marks mutable may differ.
+extern "C" int scp_problem_set_model_par(scp_handle h, const double* model_par)
+{
+    if (!h) return SCP_ERR_BAD_ARGUMENT;
+    if (!model_par) { h->err = "scp_problem_set_model_par: model_par is required"; return SCP_ERR_BAD_ARGUMENT; }
+    std::vector<int> mask((size_t)h->info.npar, 0);
+    TRY(scp_model_par_mutable(h->model_id, mask.data()));
+    for (int i = 0; i < h->info.npar; i++)
+        if (!mask[i] && std::memcmp(&model_par[i], &h->par[i], sizeof(double)) != 0) {
+            h->err = "scp_problem_set_model_par: entry " + std::to_string(i) + " of the model parameter blob is frozen into the handle "
+                     "(host formulation, scaling or cost constant); only the entries scp_model_par_mutable marks may change";
+            return SCP_ERR_BAD_ARGUMENT;
+        }
+    h->par.assign(model_par, model_par + h->info.npar);
     return SCP_OK;
 }
 

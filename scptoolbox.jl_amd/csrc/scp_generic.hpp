@@ -206,8 +206,13 @@ __global__ __launch_bounds__(64) void gen_post_kernel(PostArgs a, typename M::Pa
         for (int i = 0; i < nu; i++) gam += Qu[i] * uk[i] * uk[i] + lu[i] * uk[i];
         for (int i = 0; i < nx; i++) gam += lx[i] * xk[i];
         L += w * gam;
-        // terminal-cost terms of this node's own parameters (free-flyer: -eps_sdf sum(delta), definition.jl:172-184)
-        for (int i = 0; i < M::np_node; i++) { const double v = pr[np + M::np_node * k + i]; L += tp[np + i] * v + Qp[np + i] * v * v; }
+        if constexpr (M::node_par_in_running_cost) {
+            // running-cost terms of this node's own parameters (oscillator: l1r_k / r_nrml, definition.jl:116-142): trapezoid-weighted
+            for (int i = 0; i < M::np_node; i++) { const double v = pr[np + M::np_node * k + i]; L += w * (tp[np + i] * v + Qp[np + i] * v * v); }
+        } else {
+            // terminal-cost terms of this node's own parameters (free-flyer: -eps_sdf sum(delta), definition.jl:172-184)
+            for (int i = 0; i < M::np_node; i++) { const double v = pr[np + M::np_node * k + i]; L += tp[np + i] * v + Qp[np + i] * v * v; }
+        }
         double pk = 0.0;
         if (k < N - 1) for (int i = 0; i < nx; i++) pk += fabs(a.defect[((long)b * (N - 1) + k) * nx + i]);
         if (ns > 0) {
@@ -1152,16 +1157,56 @@ __global__ void ptrg_update_kernel(PtrgUpdateArgs a)
     atomicAdd(a.n_active, 1);
 }
 
+// Continuation of a run on its own solutions (`PTR.solve(pbm, warm)` with warm = the previous solve's SCPSolution, ptr.jl:448-466 and
+// scp.jl:532-539): every instance's LAST solution -- the one of the last iteration it ran, failed instances included, as the
+// reference passes sols[end] whatever its status -- becomes its reference, and its run state is that of a fresh init: status,
+// iteration count, history rows, cost record, J_aug = NaN (ptr.jl:350), active.  One block per instance.
+struct PtrgContinueArgs {
+    int B, iter_max;
+    long nxN, nuN, npt;
+    const double *sol_xd, *sol_ud, *sol_p;
+    double *ref_xd, *ref_ud, *ref_p;
+    double *J_ref, *cost, *hist;
+    int *active, *status, *iters_done;
+};
+__global__ __launch_bounds__(256) void ptrg_continue_kernel(PtrgContinueArgs a)
+{
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= a.B) return;
+    const bool ran = a.iters_done[b] > 0;     // before the first iteration the reference is already what get_host returns
+    __syncthreads();                          // every thread has read the count before thread 0 clears it
+    if (ran) {
+        for (long i = t; i < a.nxN; i += 256) a.ref_xd[(long)b * a.nxN + i] = a.sol_xd[(long)b * a.nxN + i];
+        for (long i = t; i < a.nuN; i += 256) a.ref_ud[(long)b * a.nuN + i] = a.sol_ud[(long)b * a.nuN + i];
+        for (long i = t; i < a.npt; i += 256) a.ref_p[(long)b * a.npt + i] = a.sol_p[(long)b * a.npt + i];
+    }
+    for (long e = t; e < (long)a.iter_max * SCP_HIST_WIDTH; e += 256)
+        a.hist[((e / SCP_HIST_WIDTH) * a.B + b) * SCP_HIST_WIDTH + e % SCP_HIST_WIDTH] = 0.0;
+    if (t < 4) a.cost[(long)b * 4 + t] = 0.0;
+    if (t == 0) {
+        a.J_ref[b] = __longlong_as_double(0x7ff8000000000000LL);
+        a.active[b] = 1; a.status[b] = 0; a.iters_done[b] = 0;
+    }
+}
+
 }  // namespace scp
+
+// what scp_ptr_generic_init_host and scp_ptr_generic_continue refuse in the loop's parameters
+static int ptrg_check_pars(scp_sub* s, const scp_ptr_generic_params* pars)
+{
+    if (pars->iter_max < 1 || s->nscal > 1 || s->nfun < 2) { s->err = "not a PTR template (nscal <= 1 and unused, fun[0] = virtual-control penalty, fun[1] = trust-region penalty)"; return SCP_ERR_BAD_ARGUMENT; }
+    if (!(pars->q_exit >= 1.0)) { s->err = "q_exit must be >= 1 (or Inf)"; return SCP_ERR_BAD_ARGUMENT; }
+    return SCP_OK;
+}
 
 extern "C" int scp_ptr_generic_init_host(scp_sub_handle s, int B, const scp_ptr_generic_params* pars, const double* xd,
                                          const double* ud, const double* p, const double* pp)
 {
     if (!s || !pars || B < 1 || !xd || !ud) return SCP_ERR_BAD_ARGUMENT;
-    if (pars->iter_max < 1 || s->nscal > 1 || s->nfun < 2) { s->err = "not a PTR template (nscal <= 1 and unused, fun[0] = virtual-control penalty, fun[1] = trust-region penalty)"; return SCP_ERR_BAD_ARGUMENT; }
-    if (!(pars->q_exit >= 1.0)) { s->err = "q_exit must be >= 1 (or Inf)"; return SCP_ERR_BAD_ARGUMENT; }
+    int rc = ptrg_check_pars(s, pars);
+    if (rc != SCP_OK) return rc;
     // generate_initial_guess: discretize!(guess) (ptr.jl:548-555)
-    int rc = loop_begin(s, nullptr, RUN_PTR_GENERIC, B, pars->iter_max, pars->solver, pars->q_exit, pars->q_exit, xd, ud, p, pp);
+    rc = loop_begin(s, nullptr, RUN_PTR_GENERIC, B, pars->iter_max, pars->solver, pars->q_exit, pars->q_exit, xd, ud, p, pp);
     if (rc != SCP_OK) return rc;
     s->pg = *pars;
     // J_aug of the guess is NaN (ptr.jl:350)
@@ -1194,4 +1239,29 @@ extern "C" int scp_ptr_generic_get_host(scp_sub_handle s, double* xd, double* ud
         SUB_TRY(hipStreamSynchronize(s->h->stream));
     }
     return SCP_OK;
+}
+
+extern "C" int scp_ptr_generic_continue(scp_sub_handle s, const scp_ptr_generic_params* pars)
+{
+    if (!s) return SCP_ERR_BAD_ARGUMENT;
+    scp_problem* h = s->h;
+    SUB_CALL(check_run(h, RUN_PTR_GENERIC, s, "continue"));
+    int rc;
+    if (pars && (rc = ptrg_check_pars(s, pars)) != SCP_OK) return rc;
+    SUB_TRY(hipSetDevice(h->device));
+    if (pars) {
+        if ((rc = sub_loop_state(s, pars->iter_max)) != SCP_OK) return rc;
+        s->pg = *pars; s->iter_max = pars->iter_max; s->opts = sub_opts(&pars->solver); s->q_exit = s->q_tr = pars->q_exit;
+    }
+    const int B = s->B;
+    scp::PtrgContinueArgs a;
+    a.B = B; a.iter_max = s->iter_max; a.nxN = (long)h->info.nx * h->N; a.nuN = (long)h->info.nu * h->N; a.npt = h->npt;
+    a.sol_xd = h->sol_xd; a.sol_ud = h->sol_ud; a.sol_p = h->sol_p; a.ref_xd = h->ref_xd; a.ref_ud = h->ref_ud; a.ref_p = h->ref_p;
+    a.J_ref = s->J_ref; a.cost = s->post2; a.hist = s->hist; a.active = s->active; a.status = s->status; a.iters_done = s->iters_done;
+    hipLaunchKernelGGL(scp::ptrg_continue_kernel, dim3(B), dim3(256), 0, h->stream, a);
+    SUB_TRY(hipGetLastError());
+    s->iter = 0;
+    // the loop's first discretize! (generate_initial_guess, ptr.jl:548-555) under the handle's CURRENT model constants
+    SUB_CALL(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
+    return loop_begun(s);
 }

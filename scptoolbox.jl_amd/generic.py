@@ -187,22 +187,34 @@ def stack_guesses(pbm, pp, guess=None):
     return tuple(np.ascontiguousarray(a, np.float64) for a in guess)
 
 
-def run_loop(pbm, sub, fns, head, guess, pp, cost_shape, hist_width, all_reduce=None):
+def run_loop(pbm, sub, fns, head, guess, pp, cost_shape, hist_width, all_reduce=None, summary_only=False):
     """One run of a device-resident loop on `sub`: fns = its (init, iterate, get_host) of the C ABI; `head` = the arguments of
     init between the handle and the guess (projection handle, B, parameter struct).  all_reduce: n -> global n (the
     per-iteration convergence all-reduce of a batch sharded over GPUs, dist.py; identity on one GPU).  Returns every output of
     get_host: xd, ud, p, status, iterations, cost[cost_shape], feas, defect, hist[iter_max, B, hist_width]."""
     init, iterate, get_host = fns
     xd, ud, p = guess
-    B, iter_max = pp.shape[0], pbm.pars.iter_max
+    B = pp.shape[0]
     sub._check(init(sub._h, *head, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np else None, _ptr(pp) if pbm.info.npp else None))
     pbm.resident_B = B      # size of the batch the run on this handle holds (audit_resident)
+    return iterate_and_read(pbm, sub, iterate, get_host, B, cost_shape, hist_width, all_reduce, summary_only)
+
+
+def iterate_and_read(pbm, sub, iterate, get_host, B, cost_shape, hist_width, all_reduce=None, summary_only=False):
+    """The iterations of a run that has been started (by its init, or by scp_ptr_generic_continue) and its get_host.
+    summary_only: get_host copies status, iterations and cost only (every other pointer NULL); the other fields are None."""
+    iter_max = pbm.pars.iter_max
     na = ctypes.c_int(1)
     k, n = 0, 1
     while k < iter_max and n > 0:
         sub._check(iterate(sub._h, ctypes.byref(na)))
         n = na.value if all_reduce is None else all_reduce(na.value)
         k += 1
+    if summary_only:
+        r = SimpleNamespace(xd=None, ud=None, p=None, status=np.zeros(B, np.int32), iterations=np.zeros(B, np.int32),
+                            cost=np.zeros(cost_shape), feas=None, defect=None, hist=None)
+        sub._check(get_host(sub._h, None, None, None, _ptr(r.status), _ptr(r.iterations), _ptr(r.cost), None, None, None))
+        return r
     rc, r = read_result(pbm, B, get_host, sub._h, cost_shape, hist_width)
     sub._check(rc)
     return r

@@ -9,7 +9,7 @@ happens in the HIP library.
 """
 import numpy as np
 
-MODEL_IDS = {"double_integrator": 0, "quadrotor": 1, "rocket_landing": 2, "starship": 3, "freeflyer": 4}
+MODEL_IDS = {"double_integrator": 0, "quadrotor": 1, "rocket_landing": 2, "starship": 3, "freeflyer": 4, "oscillator": 5}
 
 
 def linrange(a, b, n):
@@ -35,6 +35,10 @@ class NativeModel:
 
     name = None
     OVERRIDES = None     # names a subclass accepts as keyword overrides of its constants (None: unchecked)
+    PAR_NAMES = None     # names of the entries of par(), for SCPProblem.set_model_par (None: the model has no mutable constant)
+    # the node entries of the cost terms tp / Qp are coefficients of the RUNNING cost: node k's term carries the trapezoid weight
+    # (M::node_par_in_running_cost of the compiled model, csrc/models/model_common.hpp)
+    node_par_in_running_cost = False
 
     def __init__(self, **overrides):
         if self.OVERRIDES is not None:
@@ -411,4 +415,64 @@ class FreeflyerModel(NativeModel):
         return x, np.zeros((N, 6)), np.concatenate([[T], delta.reshape(-1)])
 
 
-REGISTRY = {m.name: m for m in (DoubleIntegratorModel, QuadrotorModel, RocketLandingModel, StarshipModel, FreeflyerModel)}
+class OscillatorModel(NativeModel):
+    """test/examples/oscillator/{parameters,definition}.jl: forced harmonic oscillator whose actuator has a deadband, x = [r, v],
+    u = [aa, ar, l1aa, l1adiff], p = l1r(N) -- no global parameter and ONE node parameter, the position one-norm slack, which sits
+    in the running cost (definition.jl:116-142).  Per-problem data pp = [r0, v0].  Constants (parameters.jl:69-115): zeta, w0, a_db,
+    a_max, tf, kappa1 (the sharpness of the smooth deadband, swept by PTR.solve_homotopy), alpha, gamma, and r_nrml = the
+    reference's traj.r0 in the cost normalisation and the scaling advice (a constant of the batch)."""
+    name = "oscillator"
+    nx, nu = 2, 4
+    np_glob, np_node = 0, 1
+    node_par_in_running_cost = True
+    PAR_NAMES = ("zeta", "w0", "a_db", "a_max", "tf", "kappa1", "alpha", "gamma", "r_nrml")
+    DEFAULTS = dict(zeta=0.5, w0=1.0, a_db=0.05, a_max=0.3, tf=10.0, kappa1=1.0, alpha=0.06, gamma=1e-1, r_nrml=1.0)
+    OVERRIDES = PAR_NAMES + ("N",)
+
+    def __init__(self, **overrides):
+        super().__init__(**overrides)
+        self.N = overrides.get("N")
+        for k, v in self.DEFAULTS.items():
+            setattr(self, k, float(self.opts.get(k, v)))
+
+    def bind(self, pars):
+        self.N = int(pars.N)
+
+    @property
+    def np(self):
+        if self.N is None:
+            raise RuntimeError("oscillator: the parameter vector has N entries; create the SCP problem first (or pass N=...)")
+        return self.np_glob + self.np_node * self.N
+
+    def par(self):
+        return np.array([getattr(self, k) for k in self.PAR_NAMES], dtype=float)
+
+    def nominal_pp(self):
+        return np.array([1.0, 0.0])      # [r0, v0], parameters.jl:102-103
+
+    def scale_advice(self):
+        # set_scale!, definition.jl:47-69, from the nominal r0 (= r_nrml) and v0 = 0: the zero-width velocity box scales to 1
+        # (the sqrt(eps) rule of scp.jl:388)
+        r0, v0, a = self.r_nrml, 0.0, self.a_max
+        return (np.array([[-r0, r0], [-v0, v0]]), np.array([[-a, a], [-a, a], [0.0, a], [0.0, 2 * a]]),
+                np.tile([[0.0, r0]], (self.np, 1)))
+
+    def guess(self, N, pp):
+        """definition.jl:71-114: the free response from [r0, v0] by RK4 on LinRange(0, 1, 1000) (helper.jl:411-424), sampled
+        linearly at the N nodes (linterp with get_interval, helper.jl:84-118); idle inputs; l1r_k = |r_k|."""
+        A = self.tf * np.array([[0.0, 1.0], [-self.w0 ** 2, -2.0 * self.zeta * self.w0]])
+        tg = linrange(0.0, 1.0, 1000)
+        X = np.zeros((1000, 2)); X[0] = np.asarray(pp, float)[:2]
+        for i in range(999):
+            h, x = tg[i + 1] - tg[i], X[i]
+            k1 = A @ x; k2 = A @ (x + h / 2 * k1); k3 = A @ (x + h / 2 * k2); k4 = A @ (x + h * k3)
+            X[i + 1] = x + h / 6 * (k1 + 2 * k2 + 2 * k3 + k4)
+        x = np.zeros((N, 2))
+        for k, tau in enumerate(linrange(0.0, 1.0, N)):
+            i = max(int((tau > tg).sum()), 1) - 1
+            c = (tg[i + 1] - tau) / (tg[i + 1] - tg[i])
+            x[k] = c * X[i] + (1.0 - c) * X[i + 1]
+        return x, np.zeros((N, 4)), np.abs(x[:, 0]).copy()
+
+
+REGISTRY = {m.name: m for m in (DoubleIntegratorModel, QuadrotorModel, RocketLandingModel, StarshipModel, FreeflyerModel, OscillatorModel)}

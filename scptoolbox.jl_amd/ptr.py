@@ -10,8 +10,8 @@ import numpy as np
 
 from . import _lib
 from .conic import default_options
-from .generic import GenericSubproblem, _ptr as _vp, read_result, run_loop, stack_guesses
-from .scp import FOH, SCPProblem
+from .generic import GenericSubproblem, _ptr as _vp, iterate_and_read, read_result, run_loop, stack_guesses
+from .scp import FOH, SCPProblem, device_guess as _device_guess
 from .subproblem import ModelRows, build_ptr
 
 SOLVER_STATUS = {0: "OPTIMAL", 1: "ALMOST_OPTIMAL", 2: "ITERATION_LIMIT", 3: "NUMERICAL_ERROR"}
@@ -205,13 +205,69 @@ def _solve_generic(pbm, pp, warm=None, all_reduce=None):
     L = _lib.lib()
     sub = _generic_sub(pbm)
     B = pp.shape[0]
+    cp = _generic_params(pbm, sub)
+    r = run_loop(pbm, sub, (L.scp_ptr_generic_init_host, L.scp_ptr_generic_iterate, L.scp_ptr_generic_get_host),
+                 (B, ctypes.byref(cp)), stack_guesses(pbm, pp, warm), pp, (B, 4), _lib.HIST_WIDTH, all_reduce)
+    return _result(pbm, "PTR (backend: MI355X generic conic IPM)", r)
+
+
+def _generic_params(pbm, sub):
+    """scp_ptr_generic_params of this problem's PTR.Parameters"""
+    pars = pbm.pars
     cp = _lib.ScpPtrGenericParams()
     cp.iter_max, cp.wvc, cp.wtr, cp.eps_abs, cp.eps_rel, cp.q_exit = pars.iter_max, pars.wvc, pars.wtr, pars.eps_abs, pars.eps_rel, pars.q_exit
     cp.cost_const = sub.T.cost_const
     cp.solver = default_options(**generic_solver_options(pars.solver_opts))
-    r = run_loop(pbm, sub, (L.scp_ptr_generic_init_host, L.scp_ptr_generic_iterate, L.scp_ptr_generic_get_host),
-                 (B, ctypes.byref(cp)), stack_guesses(pbm, pp, warm), pp, (B, 4), _lib.HIST_WIDTH, all_reduce)
-    return _result(pbm, "PTR (backend: MI355X generic conic IPM)", r)
+    return cp
+
+
+def solve_homotopy(pbm, name, values, pp=None, all_reduce=None, keep=False):
+    """A homotopy of warm-started solves on ONE problem (oscillator/tests.jl:60-77): for every value of the model constant
+    `name`, `mdl.<name> = value; PTR.solve(pbm, warm = the previous solution)`.  The first stage is an ordinary generic run from
+    the model's guess, made on the device (scp_guess_batch_host: a host guess per instance does not scale to a Monte-Carlo
+    batch); every later stage is set_model_par + scp_ptr_generic_continue + the iterations.  No trajectory is uploaded after
+    the first stage, and an intermediate stage reads back only its status, iteration counts, feasibility flags and costs
+    (3 x 4 + 32 = 44 bytes per instance) unless keep=True; the last stage's full result is read once.
+
+    Returns (sol, hist, summary): the LAST stage's (SCPSolutionBatch, SCPHistoryBatch) and summary = dict of status[S, B]
+    (0 = SCP_SOLVED), iterations[S, B], J[S, B] per stage.  keep=True: sol and hist are the lists of every stage's pair.
+    Refuses a constant the model does not mark mutable and problems that run on the stage-structured fast path."""
+    pars = pbm.pars
+    values = [float(v) for v in values]
+    if not values:
+        raise _lib.ScpError(1, "solve_homotopy: no homotopy value given")
+    if pars.q_tr == math.inf and pars.q_exit == math.inf and pbm.info.structured:
+        raise _lib.ScpError(7, "solve_homotopy: model '%s' runs on the stage-structured fast path, whose run cannot be continued "
+                               "(scp_ptr_generic_continue belongs to the generic PTR loop)" % pbm.traj.mdl.name)
+    if name not in pbm.mutable_model_par():
+        raise _lib.ScpError(1, "solve_homotopy: model '%s' does not mark the constant %r as changeable after create (mutable: %s)"
+                            % (pbm.traj.mdl.name, name, list(pbm.mutable_model_par())))
+    if not pars.q_exit >= 1:
+        raise _lib.ScpError(1, "q_exit must be >= 1 or Inf")
+    L = _lib.lib()
+    pp = _batch_pp(pbm, pp)
+    B, S = pp.shape[0], len(values)
+    pbm.set_model_par(**{name: values[0]})
+    sub = _generic_sub(pbm)
+    cp = _generic_params(pbm, sub)
+    fns = (L.scp_ptr_generic_init_host, L.scp_ptr_generic_iterate, L.scp_ptr_generic_get_host)
+    algo = "PTR (backend: MI355X generic conic IPM)"
+    summary = dict(status=np.zeros((S, B), np.int32), iterations=np.zeros((S, B), np.int32), J=np.zeros((S, B)))
+    stages = []
+    light = lambda i: not keep and i < S - 1      # an intermediate stage nobody asked for: status, iterations, cost only
+    for i, v in enumerate(values):
+        if i == 0:
+            r = run_loop(pbm, sub, fns, (B, ctypes.byref(cp)), _device_guess(pbm, pp), pp, (B, 4), _lib.HIST_WIDTH, all_reduce, summary_only=light(i))
+        else:
+            pbm.set_model_par(**{name: v})
+            sub._check(L.scp_ptr_generic_continue(sub._h, None))
+            r = iterate_and_read(pbm, sub, fns[1], fns[2], B, (B, 4), _lib.HIST_WIDTH, all_reduce, summary_only=light(i))
+        summary["status"][i], summary["iterations"][i], summary["J"][i] = r.status, r.iterations, r.cost[:, 0]
+        if keep or i == S - 1:
+            stages.append(_result(pbm, algo, r))
+    if keep:
+        return [s for s, _ in stages], [h for _, h in stages], summary
+    return stages[-1][0], stages[-1][1], summary
 
 
 def upload(pbm, pp=None, warm=None, device_guess=False):

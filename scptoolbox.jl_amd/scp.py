@@ -8,6 +8,7 @@ Julia Array{Float64,3} of size (nx, N, B).  Matrices therefore appear
 transposed: dyn.A[b, k] is the column-major nx-by-nx block, `dyn.A[b, k].T` is
 the math matrix A_k.
 """
+import copy
 import ctypes
 import math
 
@@ -105,6 +106,40 @@ class SCPProblem:
     def set_discretize_precision(self, bits):
         """arithmetic of discretize! on this handle: 64 (reference) or 32 (tolerance-check variant of K1; Starship, FOH)."""
         _lib.check(_lib.lib().scp_set_discretize_precision(self.handle, int(bits)), self.handle)
+
+    def mutable_model_par(self):
+        """names of the model constants that may change after `create` (scp_model_par_mutable)"""
+        names = self.traj.mdl.PAR_NAMES
+        mask = (ctypes.c_int * self.info.npar)()
+        _lib.check(_lib.lib().scp_model_par_mutable(MODEL_IDS[self.traj.mdl.name], mask))
+        return tuple(names[i] for i in range(self.info.npar) if mask[i]) if names is not None else ()
+
+    def set_model_par(self, **values):
+        """Change model constants of this problem after `create` -- the reference's `mdl.traj.kappa1 = ...` between two solves of
+        one problem object (oscillator/tests.jl:60-77) -- through scp_problem_set_model_par: SCPProblem.set_model_par(kappa1=...).
+        Only constants the compiled model marks mutable may change (they enter device-evaluated closures alone); anything else
+        raises ScpError(SCP_ERR_BAD_ARGUMENT) and leaves the problem as it was.  Takes effect for every launch after the call.
+        The problem's description of the model follows the handle (self.traj.mdl.par() == the handle's blob); it is this
+        problem's OWN copy from the first change on, so another SCPProblem created from the same TrajectoryProblem keeps the
+        constants its handle was created with."""
+        mdl = self.traj.mdl
+        names = mdl.PAR_NAMES or ()
+        unknown = sorted(set(values) - set(names))
+        if unknown:
+            raise _lib.ScpError(1, "%s: unknown model constant(s) %s; known: %s" % (mdl.name, unknown, sorted(names)))
+        par = self._par.copy()
+        for k, v in values.items():
+            par[names.index(k)] = float(v)
+        _lib.check(_lib.lib().scp_problem_set_model_par(self.handle, _ptr(par)), self.handle)
+        self._par = par
+        if not getattr(self, "_own_model", False):
+            self.traj = copy.copy(self.traj)
+            self.traj.mdl = mdl = copy.copy(mdl)
+            mdl.opts = dict(mdl.opts)
+            self._own_model = True
+        for k, v in values.items():
+            mdl.opts[k] = float(v)
+            setattr(mdl, k, float(v))
 
     def close(self):
         # dependants (generic subproblem handles, scp_sub_*) hold a pointer to this handle: destroy them first

@@ -55,6 +55,7 @@ class ModelRows:
         self.ns, self.nic, self.ntc = info.ns, info.nic, info.ntc
         self.nl, self.nsoc, self.ng = info.nl, info.nsoc, info.ng
         self.global_rows_in_X = bool(info.global_rows_in_X)
+        self.node_par_in_running_cost = bool(getattr(mdl, "node_par_in_running_cost", False))
         self.gusto_ok = bool(info.s_input_free)
         self.par = np.ascontiguousarray(mdl.par(), np.float64)
         assert self.par.size == info.npar, "model parameter blob: %d values, the library expects %d" % (self.par.size, info.npar)
@@ -114,7 +115,10 @@ class ModelRows:
         _lib.check(_lib.lib().scp_model_rows(self.model_id, p(self.par), N, 1, None, None, None, None, None, None, None, p(c)))
         nu, nx, npc, g = self.nu, self.nx, self.npc, self.np_glob
         o = np.cumsum([0, nu, nu, nx, nx, npc, npc])
-        full = lambda v: np.concatenate([v[:g], np.tile(v[g:], N)])      # node entries apply to the parameters of every node
+        # node entries apply to the parameters of every node: unweighted (terminal-style terms: free-flyer), or as coefficients of
+        # the running cost with node k's trapezoid weight w_k (node_par_in_running_cost: oscillator)
+        w = trapz_weights(N) if self.node_par_in_running_cost else np.ones(N)
+        full = lambda v: np.concatenate([v[:g], (w[:, None] * v[g:][None, :]).reshape(-1)])
         return dict(Qu=c[o[0]:o[1]], lu=c[o[1]:o[2]], lx=c[o[2]:o[3]], tx=c[o[3]:o[4]], tp=full(c[o[4]:o[5]]), Qp=full(c[o[5]:o[6]]))
 
 
