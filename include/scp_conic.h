@@ -16,6 +16,9 @@
  *           Limit: the method is an infeasible-start one without ECOS's self-dual embedding; a program whose exponential cone can
  *           only be entered against its curvature (a CONSTANT x row >= ~1.5 y) ends ITERATION_LIMIT instead of OPTIMAL
  *           (tests/test_oracle_exp_cone.py pins this).  The softplus cones have the penalty variable in the x row and are not of that kind.
+ *           Same class of limit, any cone: DUAL_INFEASIBLE is reported once the iterates have diverged far enough along a ray for
+ *           |Gx + s| / (-c'x) to fall under feastol, and not every unbounded program gets that far -- such a run ends NUMERICAL_ERROR
+ *           or ITERATION_LIMIT (never OPTIMAL, ALMOST_OPTIMAL or INFEASIBLE; tests/test_conic_families_cpu.py pins this).
  *
  * (P = 0 in ECOS; the quadratic term is accepted natively here instead of going through MOI's quadratic->SOC
  * bridge).  The entry points mirror the shape of ECOS's C API -- sparse matrices in compressed-column form, cone

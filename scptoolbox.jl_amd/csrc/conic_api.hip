@@ -236,6 +236,12 @@ int Engine::create(int n, int p, int m, int l, const std::vector<int>& q_in, con
                    const int* perm, int capacity, int dev)
 {
     if (capacity < 1) { err = "batch_capacity < 1"; return SCP_ERR_BAD_ARGUMENT; }
+    // launch_one has the instantiations SUB = 1, 4, 16, 64 only and sizes its grid with 64 / sub: any other width would leave
+    // most of a batch unsolved without a word (SCP_CONIC_SUB = 2: one problem in 32)
+    if (sub_workers > 0 && sub_workers != 1 && sub_workers != 4 && sub_workers != 16 && sub_workers != 64) {
+        err = "SCP_CONIC_SUB = " + std::to_string(sub_workers) + ": sub-workers per wave must be 1, 4, 16 or 64 (unset or <= 0: by batch size)";
+        return SCP_ERR_BAD_ARGUMENT;
+    }
     // q[c] > 0: second-order cone of that dimension; q[c] = -3: exponential cone (include/scp_conic.h).  For the symbolic
     // analysis an exponential cone is a dense 3-row block like a second-order cone of dimension 3.
     std::vector<int> q(q_in), ctype(q_in.size(), 0), cexp(q_in.size(), -1);

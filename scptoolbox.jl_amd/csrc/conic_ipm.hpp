@@ -1169,6 +1169,13 @@ struct Solver {
         if (!fok && !done) { R.status = ST_NUMERR; done = true; }
         double best_merit = 1e300;
         int best_it = 0;
+        // The counters a problem reports are those it had when IT stopped: at the exit tests, or at the end of the iteration that
+        // stopped it half way -- where a single-worker run leaves the loop.  A finished problem of a shared workgroup runs along for as
+        // long as its neighbours iterate and its factorisations and refinements go on counting: reported as they stood at the end of
+        // run(), dyn_regs / refinements of a problem depended on the other problems of its workgroup.
+        int nreg_out = 0, nrefine_out = 0;
+        bool counted = false;
+        auto freeze_counters = [&]() { if (done && !counted) { nreg_out = nreg; nrefine_out = nrefine; counted = true; } };
 
         for (int it = 0; it <= O.max_iter; it++) {
             if (!cx.any(!done)) break;
@@ -1257,6 +1264,7 @@ struct Solver {
                     else if (it == O.max_iter) done = true;
                 }
             }
+            freeze_counters();
             if (!cx.any(!done)) break;
             // ---- scaling + factorisation (finished problems run along; their state is frozen below) ----
             const long long ts_ = CPROF_T();
@@ -1371,8 +1379,10 @@ struct Solver {
                 pfor_nb(0, p, [&](int r) { Q.y[r] += a * Q.sol[n + r]; });
                 pfor_nb(0, m, [&](int r) { Q.z[r] += a * Q.dz[r]; Q.s[r] += a * Q.ds[r]; });
             }
+            freeze_counters();
             cx.barrier();
         }
+        if (!counted) { nreg_out = nreg; nrefine_out = nrefine; }
         if (R.status == ST_ITERLIM || R.status == ST_NUMERR) {
             // ECOS's reduced tolerances (feastol_inacc 1e-4, abstol_inacc = reltol_inacc = 5e-5): what the reference receives as
             // ALMOST_OPTIMAL from JuMP and treats as a safe solution (scp.jl:965-980)
@@ -1388,7 +1398,7 @@ struct Solver {
             pfor_nb(0, m, [&](int r) { Q.z[r] *= back; });
         }
         cx.barrier();
-        R.nreg = (int)cx.sum((double)nreg); R.nrefine = nrefine;
+        R.nreg = (int)cx.sum((double)nreg_out); R.nrefine = nrefine_out;
         return R;
     }
 };
