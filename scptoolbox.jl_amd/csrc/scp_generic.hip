@@ -1,4 +1,4 @@
-// Generic SCP subproblem pipeline on the device (included at the end of scp_api.hip): `solve_subproblem!` for ANY
+// Generic SCP subproblem pipeline on the device (its own translation unit; the handle is scp_handle.hpp): `solve_subproblem!` for ANY
 // subproblem the host formulated as a conic template (scptoolbox.jl_amd/subproblem.py: PTR with q_tr in {1, 2, 4, Inf},
 // SCvx, correct_convex!, ...) -- the reference's per-iteration JuMP formulation (src/solvers/ptr.jl:213-293,
 // scvx.jl:225-303, scp.jl:657-895) becomes ONE gather kernel:
@@ -18,10 +18,19 @@
 //   xref(nx,N) uref(nu,N) pref(np + np_node N) A(nx,nx,N-1) Bm(nx,nu,N-1) Bp(nx,nu,N-1) F(nx,npF,N-1) r(nx,N-1) E(nx,nx,N-1)
 //   C(ns,nx,N) D(ns,nu,N) Gs(ns,np + np_node,N) rs(ns,N) H0(nic,nx) K0(nic,np) l0(nic) Hf(ntc,nx) Kf(ntc,np) lf(ntc) scal(nscal)
 // (np = global parameters, np_node = parameters of one node: Gs holds the compact parameter Jacobian of s at its node)
-#pragma once
+#include <algorithm>
+#include <limits>
+#include <new>
+#include <string>
+#include <vector>
 
 #include "../../include/scp_conic.h"
+#include "scp_handle.hpp"
 #include "conic_engine.hpp"
+#include "ipm_kernel.hpp"      // wave_sum, wave_max
+#include "stage_problem.hpp"   // trapz_w
+
+using namespace scp;
 
 namespace scp {
 
@@ -350,6 +359,8 @@ extern "C" int scp_sub_source_layout(scp_handle h, int nscal, int* offsets, int*
     return SCP_OK;
 }
 
+scp::SubRun scp::sub_run(const scp_sub* s) { return {s->B, s->iter > 0, s->d_pp, s->status}; }
+
 extern "C" const char* scp_sub_last_error(scp_sub_handle s) { return s ? s->err.c_str() : "null handle"; }
 
 // statistics of the subproblem's conic engine: the layout of scp_conic_stats (include/scp_conic.h)
@@ -435,7 +446,7 @@ extern "C" int scp_sub_create(scp_handle h, const scp_sub_template* T, scp_sub_h
     return SCP_OK;
 }
 
-// fill the source vector from the resident reference (h->ref_*), its discretisation and the linearisations
+// fill the source vector from the resident reference (h->traj.ref_*), its discretisation and the linearisations
 static int sub_fill_sources(scp_sub* s, int B, const int* active)
 {
     scp_problem* h = s->h;
@@ -446,12 +457,12 @@ static int sub_fill_sources(scp_sub* s, int B, const int* active)
         return scp::conic::transpose_to_interleaved(h->stream, src, s->src + L.off[seg] * BS, len, B, (int)BS);
     };
     int rc;
-    const DynBuf& d = h->ref_dyn;
-    const double* const resident[] = {h->ref_xd, h->ref_ud, h->ref_p, d.A, d.Bm, d.Bp, d.F, d.r, d.E};   // SEG_XREF ... SEG_E
+    const DynBuf& d = h->traj.ref_dyn;
+    const double* const resident[] = {h->traj.ref_xd, h->traj.ref_ud, h->traj.ref_p, d.A, d.Bm, d.Bp, d.F, d.r, d.E};   // SEG_XREF ... SEG_E
     for (int seg = scp::SEG_XREF; seg <= scp::SEG_E; seg++)
         if ((rc = tr(resident[seg], seg)) != SCP_OK) return rc;
     scp::GenLinArgs a;
-    a.B = B; a.N = h->N; a.BS = BS; a.xd = h->ref_xd; a.ud = h->ref_ud; a.p = h->ref_p; a.pp = s->d_pp; a.src = s->src;
+    a.B = B; a.N = h->N; a.BS = BS; a.xd = h->traj.ref_xd; a.ud = h->traj.ref_ud; a.p = h->traj.ref_p; a.pp = s->d_pp; a.src = s->src;
     a.oC = L.off[scp::SEG_C]; a.oD = L.off[scp::SEG_D]; a.oG = L.off[scp::SEG_GS]; a.oRS = L.off[scp::SEG_RS];
     a.oH0 = L.off[scp::SEG_H0]; a.oK0 = L.off[scp::SEG_K0]; a.oL0 = L.off[scp::SEG_L0];
     a.oHF = L.off[scp::SEG_HF]; a.oKF = L.off[scp::SEG_KF]; a.oLF = L.off[scp::SEG_LF];
@@ -468,7 +479,7 @@ static int sub_fill_sources(scp_sub* s, int B, const int* active)
     return SCP_OK;
 }
 
-// gather the conic values, solve, read x / u / p out into h->sol_*, discretise the new point
+// gather the conic values, solve, read x / u / p out into h->traj.sol_*, discretise the new point
 static int sub_solve_dev(scp_sub* s, int B, const scp::conic::Opts& o, const int* active)
 {
     scp_problem* h = s->h;
@@ -496,9 +507,9 @@ static int sub_solve_dev(scp_sub* s, int B, const scp::conic::Opts& o, const int
         r.B = B; r.len = len; r.dim = dim; r.BS = BS; r.idx = idx; r.S = S; r.c = c; r.x = E.x; r.out = out; r.active = active;
         hipLaunchKernelGGL(scp::gen_readout_kernel, dim3((B + 63) / 64, (len + 3) / 4), dim3(256), 0, h->stream, r);
     };
-    ro(s->ix, nx * N, nx, h->d_Sx, h->d_cx, h->sol_xd);
-    ro(s->iu, nu * N, nu, h->d_Su, h->d_cu, h->sol_ud);
-    ro(s->ip, np, np > 0 ? np : 1, h->d_Sp, h->d_cp, h->sol_p);
+    ro(s->ix, nx * N, nx, h->d_Sx, h->d_cx, h->traj.sol_xd);
+    ro(s->iu, nu * N, nu, h->d_Su, h->d_cu, h->traj.sol_ud);
+    ro(s->ip, np, np > 0 ? np : 1, h->d_Sp, h->d_cp, h->traj.sol_p);
     if (s->nfun > 0) {
         scp::GatherArgs g;
         g.B = B; g.len = s->nfun; g.BS = BS; g.val0 = s->fun.val0; g.ptr = s->fun.ptr; g.sidx = s->fun.sidx; g.coef = s->fun.coef;
@@ -506,10 +517,9 @@ static int sub_solve_dev(scp_sub* s, int B, const scp::conic::Opts& o, const int
         hipLaunchKernelGGL(scp::gen_gather_kernel, dim3((B + 63) / 64, (s->nfun + 3) / 4), dim3(256), 0, h->stream, g);
     }
     SUB_TRY(hipGetLastError());
-    SUB_CALL(discretize_dev(h, B, h->sol_xd, h->sol_ud, h->sol_p, h->sol_dyn, h->d_feas_new, active));
+    SUB_CALL(discretize_dev(h, B, h->traj.sol_xd, h->traj.sol_ud, h->traj.sol_p, h->traj.sol_dyn, h->traj.d_feas_new, active));
     // d_feas keeps the flag of every problem's LAST solution (d_feas_new is only meaningful for the problems of this launch)
-    hipLaunchKernelGGL(merge_feas_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, B, active, h->d_feas_new, h->d_feas);
-    SUB_TRY(hipGetLastError());
+    SUB_CALL(merge_feas_dev(h, B, active));
     return SCP_OK;
 }
 
@@ -554,19 +564,19 @@ extern "C" int scp_sub_solve_batch_host(scp_sub_handle s, int B, const double* x
     if ((h->npt > 0 && !p_ref) || (h->info.npp > 0 && !pp) || (s->nscal > 0 && !scal)) { s->err = "missing input"; return SCP_ERR_BAD_ARGUMENT; }
     SUB_TRY(hipSetDevice(h->device));
     h->run = Run{};   // a stand-alone solve reuses the trajectory buffers: any run on the problem handle ends here
-    SUB_CALL(upload_traj(h, B, xd_ref, ud_ref, p_ref, h->ref_xd, h->ref_ud, h->ref_p));
+    SUB_CALL(upload_traj(h, B, xd_ref, ud_ref, p_ref, h->traj.ref_xd, h->traj.ref_ud, h->traj.ref_p));
     if (h->info.npp > 0) SUB_TRY(hipMemcpyAsync(s->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
-    SUB_TRY(hipEventRecord(h->ev0, h->stream));
-    SUB_CALL(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
+    SUB_TRY(hipEventRecord(h->timing.ev0, h->stream));
+    SUB_CALL(discretize_dev(h, B, h->traj.ref_xd, h->traj.ref_ud, h->traj.ref_p, h->traj.ref_dyn, h->traj.d_feas, nullptr));
     int rc;
     if ((rc = sub_fill_sources(s, B, nullptr)) != SCP_OK) return rc;
     if ((rc = sub_put_scal(s, B, scal)) != SCP_OK) return rc;
     if ((rc = sub_solve_dev(s, B, sub_opts(opts), nullptr)) != SCP_OK) return rc;
-    SUB_TRY(hipEventRecord(h->ev1, h->stream));
+    SUB_TRY(hipEventRecord(h->timing.ev1, h->stream));
     SUB_CALL(download_traj(h, B, true, x, u, p, defect));
     if (status) SUB_TRY(hipMemcpyAsync(status, s->eng.status, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
     if (iters) SUB_TRY(hipMemcpyAsync(iters, s->eng.iters, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-    SUB_CALL(feas_out(h, B, h->d_feas_new, feas));
+    SUB_CALL(feas_out(h, B, h->traj.d_feas_new, feas));
     if ((rc = sub_get_il(s, B, s->funv, s->nfun, fun)) != SCP_OK) return rc;
     if ((rc = sub_get_il(s, B, s->eng.x, s->eng.sched.n, xconic)) != SCP_OK) return rc;
     if ((rc = sub_get_il(s, B, s->eng.info, 8, info)) != SCP_OK) return rc;
@@ -682,9 +692,9 @@ static int sub_masked_copy_all(scp_sub* s, int B, const int* mask)
         return SCP_OK;
     };
     SUB_CALL(copy_traj(h, traj_ref(h), traj_sol(h), cp));
-    cp(h->ref_dyn.A, h->sol_dyn.A, nx * nx * M); cp(h->ref_dyn.Bm, h->sol_dyn.Bm, nx * nu * M); cp(h->ref_dyn.Bp, h->sol_dyn.Bp, nx * nu * M);
-    cp(h->ref_dyn.F, h->sol_dyn.F, nx * npF * M); cp(h->ref_dyn.r, h->sol_dyn.r, nx * M); cp(h->ref_dyn.E, h->sol_dyn.E, nx * nx * M);
-    cp(h->ref_dyn.defect, h->sol_dyn.defect, nx * M);
+    cp(h->traj.ref_dyn.A, h->traj.sol_dyn.A, nx * nx * M); cp(h->traj.ref_dyn.Bm, h->traj.sol_dyn.Bm, nx * nu * M); cp(h->traj.ref_dyn.Bp, h->traj.sol_dyn.Bp, nx * nu * M);
+    cp(h->traj.ref_dyn.F, h->traj.sol_dyn.F, nx * npF * M); cp(h->traj.ref_dyn.r, h->traj.sol_dyn.r, nx * M); cp(h->traj.ref_dyn.E, h->traj.sol_dyn.E, nx * nx * M);
+    cp(h->traj.ref_dyn.defect, h->traj.sol_dyn.defect, nx * M);
     SUB_TRY(hipGetLastError());
     return SCP_OK;
 }
@@ -694,7 +704,7 @@ static int sub_post(scp_sub* s, int B, const double* xd, const double* ud, const
     scp_problem* h = s->h;
     scp::PostArgs a;
     a.q_exit = s->q_exit; a.q_tr = s->q_tr;
-    a.B = B; a.N = h->N; a.xd = xd; a.ud = ud; a.p = p; a.pp = s->d_pp; a.defect = defect; a.rxd = h->ref_xd; a.rp = h->ref_p;
+    a.B = B; a.N = h->N; a.xd = xd; a.ud = ud; a.p = p; a.pp = s->d_pp; a.defect = defect; a.rxd = h->traj.ref_xd; a.rp = h->traj.ref_p;
     a.Sx = h->d_Sx; a.Sp = h->d_Sp; a.post = s->post; a.active = active;
     int rc = with_model(h->model_id, [&](auto m) -> int {
         using M = decltype(m);
@@ -744,7 +754,7 @@ static int loop_begin(scp_sub* s, scp_sub* proj, RunKind loop, int B, int iter_m
     if ((rc = sub_loop_state(s, iter_max)) != SCP_OK) return rc;
     h->run = Run{loop, s};   // takes the trajectory buffers over; the projection below (sub_solve_dev) leaves that alone
     s->B = B; s->iter = 0; s->iter_max = iter_max; s->opts = sub_opts(&solver); s->q_exit = q_exit; s->q_tr = q_tr;
-    SUB_CALL(upload_traj(h, B, xd, ud, p, h->ref_xd, h->ref_ud, h->ref_p));
+    SUB_CALL(upload_traj(h, B, xd, ud, p, h->traj.ref_xd, h->traj.ref_ud, h->traj.ref_p));
     if (h->info.npp > 0) {
         SUB_TRY(hipMemcpyAsync(s->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
         if (proj) SUB_TRY(hipMemcpyAsync(proj->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
@@ -755,14 +765,14 @@ static int loop_begin(scp_sub* s, scp_sub* proj, RunKind loop, int B, int iter_m
     if (loop == RUN_PTR_GENERIC) SUB_TRY(hipMemsetAsync(s->post2, 0, sizeof(double) * 4 * (size_t)B, h->stream));   // its cost[B][4]
     SUB_CALL(set_active_all(h, s->active, B));
     if (proj) {
-        SUB_CALL(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
+        SUB_CALL(discretize_dev(h, B, h->traj.ref_xd, h->traj.ref_ud, h->traj.ref_p, h->traj.ref_dyn, h->traj.d_feas, nullptr));
         if ((rc = sub_fill_sources(proj, B, nullptr)) != SCP_OK) { s->err = proj->err; return rc; }
         if ((rc = sub_solve_dev(proj, B, s->opts, nullptr)) != SCP_OK) { s->err = proj->err; return rc; }
         hipLaunchKernelGGL(scp::proj_status_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, proj->eng.status, s->active,
                            s->status, s->accept, B);
         if ((rc = sub_masked_copy_all(s, B, s->accept)) != SCP_OK) return rc;   // x_ref .= value(opti.x) (scp.jl:346-349)
     }
-    SUB_CALL(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
+    SUB_CALL(discretize_dev(h, B, h->traj.ref_xd, h->traj.ref_ud, h->traj.ref_p, h->traj.ref_dyn, h->traj.d_feas, nullptr));
     return SCP_OK;
 }
 // the end of every init, behind the kernels that seed the loop scalars
@@ -791,7 +801,7 @@ static int loop_step(scp_sub* s, RunKind loop, int* n_active, Update&& update)
     SUB_TRY(hipMemsetAsync(s->n_active, 0, sizeof(int), h->stream));
     if ((rc = sub_fill_sources(s, B, s->active)) != SCP_OK) return rc;
     if ((rc = sub_solve_dev(s, B, s->opts, s->active)) != SCP_OK) return rc;
-    if ((rc = sub_post(s, B, h->sol_xd, h->sol_ud, h->sol_p, h->sol_dyn.defect, s->active)) != SCP_OK) return rc;
+    if ((rc = sub_post(s, B, h->traj.sol_xd, h->traj.sol_ud, h->traj.sol_p, h->traj.sol_dyn.defect, s->active)) != SCP_OK) return rc;
     if ((rc = update()) != SCP_OK) return rc;
     SUB_TRY(hipGetLastError());
     if ((rc = sub_masked_copy_all(s, B, s->accept)) != SCP_OK) return rc;    // ref = sol for the accepted steps
@@ -821,7 +831,7 @@ static int loop_get(scp_sub* s, RunKind loop, double* xd, double* ud, double* p,
         SUB_TRY(hipMemcpyAsync(cost + b, s->J_ref + h->cap, D * b, hipMemcpyDeviceToHost, h->stream));
     }
     if (hist) SUB_TRY(hipMemcpyAsync(hist, s->hist, D * (size_t)s->iter_max * b * SCP_SCVX_HIST_WIDTH, hipMemcpyDeviceToHost, h->stream));
-    SUB_CALL(feas_out(h, s->B, h->d_feas, feas));
+    SUB_CALL(feas_out(h, s->B, h->traj.d_feas, feas));
     return SCP_OK;
 }
 
@@ -836,7 +846,7 @@ extern "C" int scp_scvx_init_host(scp_sub_handle s, scp_sub_handle proj, int B, 
     s->sp = *pars;
     scp_problem* h = s->h;
     // nonlinear cost of the initial reference (solution_cost!(ref, :nonlinear), scvx.jl:724)
-    if ((rc = sub_post(s, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn.defect, nullptr)) != SCP_OK) return rc;
+    if ((rc = sub_post(s, B, h->traj.ref_xd, h->traj.ref_ud, h->traj.ref_p, h->traj.ref_dyn.defect, nullptr)) != SCP_OK) return rc;
     hipLaunchKernelGGL(scp::jref_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, s->post, pars->lam, s->J_ref, B);
     hipLaunchKernelGGL(scp::fill_strided_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream,
                        s->src + s->lay.off[scp::SEG_SCAL] * s->eng.BS, pars->eta_init, B);
@@ -849,7 +859,7 @@ extern "C" int scp_scvx_iterate(scp_sub_handle s, int* n_active)
         scp_problem* h = s->h;
         const int B = s->B;
         scp::ScvxUpdateArgs a;
-        a.B = B; a.iter = s->iter; a.BS = s->eng.BS; a.sp = s->sp; a.post = s->post; a.fun = s->funv; a.feas = h->d_feas_new;
+        a.B = B; a.iter = s->iter; a.BS = s->eng.BS; a.sp = s->sp; a.post = s->post; a.fun = s->funv; a.feas = h->traj.d_feas_new;
         a.ipm_status = s->eng.status; a.ipm_iters = s->eng.iters; a.J_ref = s->J_ref; a.J_last = s->J_ref + h->cap;
         a.eta = s->src + s->lay.off[scp::SEG_SCAL] * s->eng.BS; a.active = s->active; a.accept = s->accept; a.scp_status = s->status;
         a.iters_done = s->iters_done; a.hist = s->hist; a.n_active = s->n_active;
@@ -1075,8 +1085,8 @@ extern "C" int scp_gusto_iterate(scp_sub_handle s, int* n_active)
         scp_problem* h = s->h;
         const int B = s->B;
         scp::GustoPostArgs pa;
-        pa.B = B; pa.N = h->N; pa.xd = h->sol_xd; pa.ud = h->sol_ud; pa.p = h->sol_p; pa.rxd = h->ref_xd; pa.rud = h->ref_ud;
-        pa.rp = h->ref_p; pa.post2 = s->post2; pa.active = s->active; pa.pen = s->gp.pen; pa.hom = s->gp.hom;
+        pa.B = B; pa.N = h->N; pa.xd = h->traj.sol_xd; pa.ud = h->traj.sol_ud; pa.p = h->traj.sol_p; pa.rxd = h->traj.ref_xd; pa.rud = h->traj.ref_ud;
+        pa.rp = h->traj.ref_p; pa.post2 = s->post2; pa.active = s->active; pa.pen = s->gp.pen; pa.hom = s->gp.hom;
         int rc = with_model(h->model_id, [&](auto m) -> int {
             using M = decltype(m);
             typename M::Params P = M::make_params(h->par.data());
@@ -1086,7 +1096,7 @@ extern "C" int scp_gusto_iterate(scp_sub_handle s, int* n_active)
         if (rc != SCP_OK) return rc;
         scp::GustoUpdateArgs a;
         a.B = B; a.iter = s->iter; a.N = h->N; a.nst = s->gp.nst; a.BS = s->eng.BS; a.gp = s->gp; a.post = s->post; a.post2 = s->post2;
-        a.fun = s->funv; a.feas = h->d_feas_new; a.ipm_status = s->eng.status; a.ipm_iters = s->eng.iters; a.J_ref = s->J_ref;
+        a.fun = s->funv; a.feas = h->traj.d_feas_new; a.ipm_status = s->eng.status; a.ipm_iters = s->eng.iters; a.J_ref = s->J_ref;
         a.J_last = s->J_ref + h->cap; a.scal = s->src + s->lay.off[scp::SEG_SCAL] * s->eng.BS; a.active = s->active;
         a.accept = s->accept; a.scp_status = s->status; a.iters_done = s->iters_done; a.hist = s->hist; a.n_active = s->n_active;
         hipLaunchKernelGGL(scp::gusto_update_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, a);
@@ -1221,7 +1231,7 @@ extern "C" int scp_ptr_generic_iterate(scp_sub_handle s, int* n_active)
         const int B = s->B;
         scp::PtrgUpdateArgs a;
         a.B = B; a.iter = s->iter; a.BS = s->eng.BS; a.pp = s->pg; a.post = s->post; a.fun = s->funv; a.info = s->eng.info;
-        a.feas = h->d_feas_new; a.ipm_status = s->eng.status; a.ipm_iters = s->eng.iters; a.J_ref = s->J_ref; a.cost = s->post2;
+        a.feas = h->traj.d_feas_new; a.ipm_status = s->eng.status; a.ipm_iters = s->eng.iters; a.J_ref = s->J_ref; a.cost = s->post2;
         a.active = s->active; a.accept = s->accept; a.scp_status = s->status; a.iters_done = s->iters_done; a.hist = s->hist;
         a.n_active = s->n_active;
         hipLaunchKernelGGL(scp::ptrg_update_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, a);
@@ -1256,12 +1266,12 @@ extern "C" int scp_ptr_generic_continue(scp_sub_handle s, const scp_ptr_generic_
     const int B = s->B;
     scp::PtrgContinueArgs a;
     a.B = B; a.iter_max = s->iter_max; a.nxN = (long)h->info.nx * h->N; a.nuN = (long)h->info.nu * h->N; a.npt = h->npt;
-    a.sol_xd = h->sol_xd; a.sol_ud = h->sol_ud; a.sol_p = h->sol_p; a.ref_xd = h->ref_xd; a.ref_ud = h->ref_ud; a.ref_p = h->ref_p;
+    a.sol_xd = h->traj.sol_xd; a.sol_ud = h->traj.sol_ud; a.sol_p = h->traj.sol_p; a.ref_xd = h->traj.ref_xd; a.ref_ud = h->traj.ref_ud; a.ref_p = h->traj.ref_p;
     a.J_ref = s->J_ref; a.cost = s->post2; a.hist = s->hist; a.active = s->active; a.status = s->status; a.iters_done = s->iters_done;
     hipLaunchKernelGGL(scp::ptrg_continue_kernel, dim3(B), dim3(256), 0, h->stream, a);
     SUB_TRY(hipGetLastError());
     s->iter = 0;
     // the loop's first discretize! (generate_initial_guess, ptr.jl:548-555) under the handle's CURRENT model constants
-    SUB_CALL(discretize_dev(h, B, h->ref_xd, h->ref_ud, h->ref_p, h->ref_dyn, h->d_feas, nullptr));
+    SUB_CALL(discretize_dev(h, B, h->traj.ref_xd, h->traj.ref_ud, h->traj.ref_p, h->traj.ref_dyn, h->traj.d_feas, nullptr));
     return loop_begun(s);
 }

@@ -10,7 +10,7 @@
 //   then     the first feasible duration of every instance is taken and theta, T, omega, m of phase 2 are reconstructed from
 //            the thrust vectors (:423-440) -- `starship_reconstruct_kernel`.
 // Host-side numpy twin: scptoolbox.jl_amd/starship_guess.py (the golden fixtures are generated with it through the oracle's
-// solver); this file is what scp_guess_batch_host runs for the Starship model.  Included by scp_api.hip.
+// solver); this file is what scp_guess_batch_host runs for the Starship model.  Included by guess_api.hip.
 #pragma once
 #include <algorithm>
 #include <cmath>

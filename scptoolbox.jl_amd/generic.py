@@ -166,7 +166,7 @@ class GenericSubproblem:
         return out
 
 
-# ---- what the device-resident outer loops (SCvx, GuSTO, PTR on the generic path; csrc/scp_generic.hpp) share on the host ----
+# ---- what the device-resident outer loops (SCvx, GuSTO, PTR on the generic path; csrc/scp_generic.hip) share on the host ----
 class LoopProblem(SCPProblem):
     """An SCPProblem that owns its subproblem template `sub` and its guess projection `proj` (SCvx, GuSTO)."""
 

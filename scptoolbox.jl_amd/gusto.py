@@ -11,7 +11,7 @@ constraints and on the trust-region excess, gusto.jl:534-550, 725-995, 1056-1170
 per-problem scalars (eta, lambda) as sources -- lambda weights the diagonal of P, so the quadratic cost VALUES are per
 problem while the pattern and the symbolic factorisation are shared.  The loop (discretize!, formulate, solve, the
 solution costs :391-407, check_stopping_criterion! :1203-1230, update_trust_region! :1245-1427) runs on the device
-(csrc/scp_generic.hpp).  Both penalties of the reference: `pen = "quad"` and, since round 4, `pen = "softplus"` (exponential cones in the
+(csrc/scp_generic.hip).  Both penalties of the reference: `pen = "quad"` and, since round 4, `pen = "softplus"` (exponential cones in the
 conic solver, gusto.jl:996-1031).  Restriction (subproblem.build_gusto): s(t, k, x, p) independent of the input."""
 import numpy as np
 

@@ -65,7 +65,7 @@ class Parameters:
         # run; the mid level saves ~10 iterations in the launch after the last large move.  Same optima (levels and bounds swept on
         # the CPU twin, oracle/cpu_ptr.cpp -- the sweep switches are in its git history -- then on the 4096 batch).
         # The fine level is this module's to set (the library has no default for it); 0 = the library's default for the others:
-        # mu 1e-1 / 1e-5 / 1e-10 for coarse / mid / very fine, deviation bounds 1e-1 / 1e-6 for mid / very fine (warm_levels, scp_api.hip)
+        # mu 1e-1 / 1e-5 / 1e-10 for coarse / mid / very fine, deviation bounds 1e-1 / 1e-6 for mid / very fine (warm_levels, ptr_api.hip)
         c.ipm_warm_mu = float(o.get("warm_mu", 1e-8))
         c.ipm_warm_dev = float(o.get("warm_dev", 1e-3))
         c.ipm_warm_min_cold = int(o.get("warm_min_cold", 25))   # gates the COARSE level only

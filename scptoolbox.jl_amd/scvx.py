@@ -8,7 +8,7 @@
 The subproblem (hard trust region ||dx||_q + ||du||_q + ||dp||_q <= eta, scvx.jl:578-678; cost L + lambda (trapz P +
 sum Pf), :804-901) and the guess projection `correct_convex!` (scp.jl:275-361) are formulated once as conic templates
 (subproblem.py); the whole loop -- discretize!, formulate, solve, check_stopping_criterion! (:711-734),
-update_trust_region! (:753-769, 1000-1045) -- runs on the device (csrc/scp_generic.hpp)."""
+update_trust_region! (:753-769, 1000-1045) -- runs on the device (csrc/scp_generic.hip)."""
 import numpy as np
 
 from . import _lib

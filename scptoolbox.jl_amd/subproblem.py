@@ -123,7 +123,7 @@ class ModelRows:
 
 
 def standard_sources(mr, N, nscal):
-    """The source vector layout shared with csrc/scp_generic.hip (scp_gen_source_layout): order and shapes."""
+    """The source vector layout shared with csrc/scp_generic.hip (scp_sub_source_layout): order and shapes."""
     S = Sources()
     nx, nu, np_, ns = mr.nx, mr.nu, mr.np, mr.ns
     S.add("xref", (nx, N)); S.add("uref", (nu, N)); S.add("pref", (np_,))

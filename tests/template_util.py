@@ -1,5 +1,5 @@
 """Shared by the template tests: the per-problem SOURCE VECTOR of a conic template (scptoolbox.jl_amd/subproblem.py)
-built from ORACLE data (oracle discretize! + the oracle's model Jacobians), i.e. what csrc/scp_generic.hpp fills on the
+built from ORACLE data (oracle discretize! + the oracle's model Jacobians), i.e. what csrc/scp_generic.hip fills on the
 device -- so that a template can be checked against the oracle's literal conic program on the CPU."""
 import numpy as np
 import scipy.sparse as sp

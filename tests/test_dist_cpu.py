@@ -260,7 +260,7 @@ def _shipped_loop_worker(rank, world, port, q):
 
 
 def test_shipped_sharded_window_loop_with_two_gloo_ranks():
-    """VERDICT r05 next 7: the pipelining logic that SHIPS (csrc/sharded_loop.hpp, included by scp_api.hip::scp_ptr_run_sharded) is the logic
+    """VERDICT r05 next 7: the pipelining logic that SHIPS (csrc/sharded_loop.hpp, included by comm_api.hip::scp_ptr_run_sharded) is the logic
     tested with more than one rank: both ranks enqueue the same number of windows, stop together after the slowest problem anywhere, a count is
     read only with the next window already enqueued, a fixed-iteration run (eps = 0) stops at iter_max, uneven shards (all of one rank's
     problems stop early) keep the collectives matched."""

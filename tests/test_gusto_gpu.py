@@ -1,4 +1,4 @@
-"""GuSTO on the MI355X (-m gpu): the device loop (csrc/scp_generic.hpp: gusto_post_kernel, gusto_update_kernel) against the
+"""GuSTO on the MI355X (-m gpu): the device loop (csrc/scp_generic.hip: gusto_post_kernel, gusto_update_kernel) against the
 oracle's literal restatement of src/solvers/gusto.jl (oracle/gusto_ref.py), at the reference's own quadrotor test
 parameters (test/examples/quadrotor/tests.jl:86-130)."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""Life cycle of the three device-resident outer loops of the generic conic path (csrc/scp_generic.hpp: SCvx, GuSTO, PTR)
+"""Life cycle of the three device-resident outer loops of the generic conic path (csrc/scp_generic.hip: SCvx, GuSTO, PTR)
 through the C ABI (-m gpu): what get_host answers before any iteration, an iterate past iter_max, a second init on the same
 handle, and calls of another loop's entry points on a handle.  Quadrotor, N = 12, Nsub = 8, iter_max = 3; a batch of 3 on a
 handle of capacity 4, i.e. smaller than the interleave stride.  No projection handle: the reference is the uploaded guess."""

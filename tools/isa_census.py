@@ -1,6 +1,6 @@
 """Static instruction census of one function of a gfx950 assembly listing (hipcc -S --cuda-device-only): per loop (a label that is the
 target of a backward branch ... that branch) the instruction counts by class.  CPU only.
-python tools/isa_census.py /tmp/scp_api.s _ZN3scp14ipm2_ph_factorINS_13RocketLandingELi2EEEvPKdPdidS4_ [min_loop_size]"""
+python tools/isa_census.py /tmp/ptr_api.s _ZN3scp14ipm2_ph_factorINS_13RocketLandingELi2EEEvPKdPdidS4_ [min_loop_size]"""
 import re, sys, collections
 path, fn = sys.argv[1], sys.argv[2]
 minsz = int(sys.argv[3]) if len(sys.argv) > 3 else 200
