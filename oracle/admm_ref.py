@@ -14,10 +14,12 @@ the virtual controls vd, vs, vic, vtc are eliminated analytically,
 leaving   min_z 1/2 z'Qz + q'z + sum_j g_j(K_j z + c_j)   over z = (xh, uh, ph)
 with prox-friendly g_j (weighted L1, L_inf norm, hinge, cone indicators).  This
 file builds that reduced problem from the *oracle's* model definitions with
-generic sparse algebra and runs the same OSQP-style ADMM iteration the GPU
-kernels implement with block-tridiagonal structure.  tests/ use it (a) to show
-the reduction is exact (same optimum as the literal conic form solved by
-oracle/ipm.py) and (b) to check the HIP kernels step by step.
+generic sparse algebra and runs the OSQP-style ADMM iteration that the earlier
+GPU kernels implemented with block-tridiagonal structure.  No test runs it: it
+is kept as the evidence DESIGN.md section 2.1 cites for choosing the
+interior-point method.  That the reduction is exact (same optimum as the
+literal conic form solved by oracle/ipm.py) is shown by oracle/ipm_struct.py in
+tests/test_oracle_ipm.py.
 """
 import numpy as np
 import scipy.sparse as sp

@@ -7,7 +7,8 @@
 //   formulate          the product's stage-form assembly ptr_assemble_entry<M> (csrc/stage_problem.hpp, __host__
 //                      __device__) and model definitions (csrc/models/*.hpp) compiled for the host: both solvers see
 //                      bit-identical subproblem data
-//   solve_subproblem!  the structured primal-dual interior-point method of oracle/ipm_struct.py / csrc/ipm2_*.hpp
+//   solve_subproblem!  the structured primal-dual interior-point method of csrc/ipm2_*.hpp (oracle/ipm_struct.py states
+//                      the reduced Newton system and its plain cold solve in numpy, for the algebra; THIS file is the mirror)
 //                      (Mehrotra predictor-corrector, NT scaling, quasi-definite block sweep + arrow column, static
 //                      regularisation + one refinement step) in scalar C++ with small dense blocks, warm-started from
 //                      snapshots of the previous solve and repeated on failure exactly as the device does
@@ -874,7 +875,8 @@ struct CpuIpm {
         for (long i = 0; i < XI; i++) xi[i] += alpha * dxi[i];
     }
 
-    // ---- one run (oracle/ipm_struct.py::solve; the body of the device's attempt loop): from the snapshot of `level`, or cold (level < 0:
+    // ---- one run (the body of the device's attempt loop; a cold run without the snapshots and the escalation is what
+    // oracle/ipm_struct.py::solve states in numpy, step names as here): from the snapshot of `level`, or cold (level < 0:
     // iteration -1 builds the initial point through the same factor / solve path); robust: refinement on from the first iteration ----
     IpmResult run(int level, bool robust, std::vector<double>& best)
     {

@@ -1,20 +1,24 @@
-"""CPU MIRROR of the product's stage-structured interior-point subproblem solver
+"""Numpy statement of the reduced PTR subproblem that the product's structured interior-point solver K3 works on
 (test infrastructure; NOT product code, NOT reference-derived).  Parity status of the oracle family:
 "parity unpinned" (no golden vectors in the reference, see oracle/ptr_ref.py).
 
-The HIP solver (scptoolbox.jl_amd/csrc/ipm2_kernel.hpp, ipm2_newton.hpp, ipm2_run.hpp) solves the *reduced* PTR
-subproblem (see oracle/admm_ref.py for the reduction and its proof-by-test of
-equivalence with the reference's literal conic program) with the same
-Mehrotra/NT primal-dual method as oracle/ipm.py, but exploiting the time-staged
-structure: all constraints are inequalities, the epigraph variables are
-eliminated analytically from the Newton system, and what remains is a
-symmetric positive definite block-tridiagonal + arrow system in
-(z_1..z_N, p), z_k = (xh_k, uh_k), solved by a block Cholesky sweep.
+K3 is stated three times, each for one purpose:
+  * scptoolbox.jl_amd/csrc/ipm2_kernel.hpp, ipm2_newton.hpp, ipm2_run.hpp: the device kernels, the product;
+  * this file: (a) `build_stage_problem`, the independent numpy ASSEMBLY of the stage form from the oracle's model
+    definitions -- the GPU tests compare the arrays of the assembly kernel K2 with it -- and (b) `solve`, the plain COLD
+    solve of the reduced Newton system, which shows that the reduction has the optimum of the reference's literal conic
+    program (tests/test_oracle_ipm.py; its results are pinned by tests/golden/ipm_struct_pins.npz).  No test compares
+    iterates with it;
+  * oracle/cpu_ptr.cpp: the exact MIRROR of the device, with everything `solve` leaves out -- the warm start from
+    snapshots, the attempt ladder, the escalation of the regularisation, triangular substitutions with the device's
+    operation order.  It is pinned and compared with the device per launch.
 
-This file holds (a) `StageProblem`: the canonical stage-form data layout the
-GPU assembly kernel produces, built here from the oracle's model definitions,
-and (b) `solve`: a numpy transliteration of the GPU algorithm.  Tests compare
-the GPU arrays and iterates against these.
+The reduction: all constraints are inequalities, the epigraph variables are eliminated analytically from the Newton
+system, and what remains is a symmetric quasi-definite block-tridiagonal + arrow system in (z_1..z_N, nu, p),
+z_k = (xh_k, uh_k), solved by a block LDL' sweep (`qd_factor` / `qd_solve` / `newton`).  The method around it is the
+Mehrotra / Nesterov-Todd primal-dual method of oracle/ipm.py.  The starting points, corrector schemes, centring rules and
+warm starts that were tried in this file and dropped are written up in DESIGN.md section 2.1; that code is in the git
+history.
 
 Row groups (all rows written as  a(zeta) <= 0  unless SOC):
   dyn_k   (type A, k<N-1): a = D_k z_k + E_k z_{k+1} + Fp_k p + c_k, |a_i| <= y_i, cost om_i y_i
@@ -159,14 +163,10 @@ def build_stage_problem(mdl, pars, scale, ref, pp):
     return P
 
 
+
 # ---------------------------------------------------------------------------------------------
 # structured IPM
 # ---------------------------------------------------------------------------------------------
-
-class State:
-    """primal (z, p, aux), slacks s and duals lam per row group.  Pair groups carry
-    index 0 for the '+a - aux <= 0' row and 1 for the '-a - aux <= 0' row."""
-
 
 def _rows_eval(P, z, p):
     """a(zeta) for every row group."""
@@ -181,6 +181,13 @@ def _rows_eval(P, z, p):
     a["ic"] = P.H0 @ z[0, :nx] + (P.K0 @ p if P.np else 0.0) + P.l0
     a["tc"] = P.Hf @ z[-1, :nx] + (P.Kf @ p if P.np else 0.0) + P.lf
     return a
+
+
+def _rows_eval_lin(P, z, p):
+    """linear part of the row functions (no constants)."""
+    a = _rows_eval(P, z, p)
+    c = _rows_eval(P, np.zeros_like(z), np.zeros_like(p))
+    return {g: a[g] - c[g] for g in a}
 
 
 def _rows_T(P, mu):
@@ -206,9 +213,8 @@ def _soc_split(P, v):
 
 
 def _nt(s, z):
-    """NT scaling of one SOC pair -> (W [4,4], lam = W z, W^-1, W^-2), all in closed form:
-    W = eta [w0 w1'; w1 I + w1 w1'/(1+w0)],  W^-1 = 1/eta [w0 -w1'; -w1 I + w1 w1'/(1+w0)],
-    W^-2 = (2 v v' - J)/eta^2 with v = (w0, -w1), J = diag(1,-1,-1,-1)."""
+    """NT scaling of one SOC pair -> (W [4,4], lam = W z, W^-1), all in closed form:
+    W = eta [w0 w1'; w1 I + w1 w1'/(1+w0)],  W^-1 = 1/eta [w0 -w1'; -w1 I + w1 w1'/(1+w0)]."""
     sres = np.sqrt(s[0] ** 2 - s[1:] @ s[1:]); zres = np.sqrt(z[0] ** 2 - z[1:] @ z[1:])
     sb, zb = s / sres, z / zres
     gamma = np.sqrt((1 + sb @ zb) / 2)
@@ -219,9 +225,7 @@ def _nt(s, z):
     Wi = W.copy(); Wi[0, 1:] = -wb[1:]; Wi[1:, 0] = -wb[1:]
     W = W * eta
     Wi = Wi / eta
-    v = np.concatenate([[wb[0]], -wb[1:]])
-    Wi2 = (2 * np.outer(v, v) - np.diag([1.0, -1.0, -1.0, -1.0])) / (eta * eta)
-    return W, W @ z, Wi, Wi2
+    return W, W @ z, Wi
 
 
 def _typeB_matrix(w1, w2):
@@ -269,39 +273,6 @@ def _soc_max_step(s, ds):
     return a
 
 
-def chol_solve_arrow(T, U, C, Dp, rz, rp):
-    """Solve [[T, C],[C', Dp]] [dz; dp] = [rz; rp]; T block tridiagonal with diagonal blocks
-    T[k] (nz x nz) and sub-diagonal blocks U[k] = T_{k+1,k}.  Block Cholesky sweep (what the GPU does)."""
-    N, nz = T.shape[0], T.shape[1]
-    npp = Dp.shape[0]
-    L = np.zeros_like(T); Lo = np.zeros_like(U)
-    V = np.zeros((N, nz, npp)); yh = np.zeros((N, nz))
-    for k in range(N):
-        Tk = T[k].copy()
-        rhs = rz[k].copy(); Ck = C[k].copy()
-        if k > 0:
-            Tk -= Lo[k - 1] @ Lo[k - 1].T
-            rhs -= Lo[k - 1] @ yh[k - 1]
-            Ck -= Lo[k - 1] @ V[k - 1]
-        L[k] = np.linalg.cholesky(Tk)
-        yh[k] = np.linalg.solve(L[k], rhs)
-        V[k] = np.linalg.solve(L[k], Ck)
-        if k < N - 1:
-            Lo[k] = np.linalg.solve(L[k], U[k].T).T   # L_{k+1,k} = U_k L_kk^-T
-    if npp:
-        S = Dp - np.einsum("kip,kiq->pq", V, V)
-        dp = np.linalg.solve(S, rp - np.einsum("kip,ki->p", V, yh))
-    else:
-        dp = np.zeros(0)
-    dz = np.zeros((N, nz))
-    for k in range(N - 1, -1, -1):
-        rhs = yh[k] - (V[k] @ dp if npp else 0.0)
-        if k < N - 1:
-            rhs = rhs - Lo[k].T @ dz[k + 1]
-        dz[k] = np.linalg.solve(L[k].T, rhs)
-    return dz, dp
-
-
 def qd_factor(H0, Dt, Et, kinv):
     """Block LDL' of the quasi-definite interleaved system (z_0, nu_0, z_1, nu_1, ..., z_{N-1}, nu_{N-1}):
          H0_k z_k + Dt_k' nu_k + Et_{k-1}' nu_{k-1}            = b_k
@@ -343,28 +314,44 @@ def qd_solve(Lz, Lnu, Dt, Et, b, t):
     return z, nu
 
 
-def solve(P, max_iter=100, feastol=1e-8, abstol=1e-8, reltol=1e-8, verbose=False, trace=None, debug=False, nref=1, stall=3, hook=None, reg=5e-11, ref_gap=1e-2, init="two", resid_scale=False, sigma_min=0.0, ref_affine=True, ref_tol=0.0, ref_log=None, split_step=None, warm=None, warm_delta=1e-2,
-          sigma_rule="ecos", nbhd=0.0, ncorr=0, step_frac=0.99, mu0=None, corr_delta=0.3, corr_accept=0.1, log=None, track_rz=False, probe=None):
-    """Structured primal-dual IPM.  Returns dict(status, z, p, iters, pcost, ...)."""
-    if split_step is None:   # separate primal / dual step lengths: optional (default off, like the device solver)
-        split_step = False
-    N, nx, nu, nz, npp = P.N, P.nx, P.nu, P.nz, P.np
-    ns, nl, nsoc = P.ns, P.nl, P.nsoc
-    o_soc = ns + nl
+LPG = ("dyn", "ic", "tc", "tr", "trp", "hinge", "lin", "glin")     # the row groups of the positive orthant; "soc" holds the cones
 
-    # ---- groups: pair groups have arrays [..., 2]; aux costs ----
-    groups_pair = {"dyn": (N - 1, nx), "ic": (P.nic,), "tc": (P.ntc,), "tr": (N, nz), "trp": (npp,), "hinge": (N, ns)}
-    aux_cost = {"dyn": P.om, "ic": P.bw0, "tc": P.bwf, "hinge": P.hw}
 
-    def zeros_like_rows():
-        d = {g: np.zeros(sh + (2,)) for g, sh in groups_pair.items()}
-        d["lin"] = np.zeros((N, nl)); d["glin"] = np.zeros(P.ng); d["soc"] = np.zeros((N, nsoc, 4))
+def _norm(vs):
+    return np.sqrt(sum((np.asarray(v) ** 2).sum() for v in vs))
+
+
+class _Ipm:
+    """The conic form  min 1/2 xi'P xi + c'xi  s.t.  G xi + s = h, s in K  of one stage problem, xi = (z, p, aux), and the steps of
+    the interior-point iteration on it, named as in the twin (oracle/cpu_ptr.cpp, CpuIpm).  Rows are dicts over LPG + ("soc",);
+    pair groups carry index 0 for the '+a - aux <= 0' row and 1 for the '-a - aux <= 0' row.  The object holds the problem's
+    constants only: every step is a function of the iterate it is given."""
+
+    def __init__(self, P, reg):
+        self.P, self.reg = P, reg
+        N, nx, nz, npp = P.N, P.nx, P.nz, P.np
+        self.o_soc = P.ns + P.nl
+        self.groups_pair = {"dyn": (N - 1, nx), "ic": (P.nic,), "tc": (P.ntc,), "tr": (N, nz), "trp": (npp,), "hinge": (N, P.ns)}
+        self.caux = {"dyn": P.om, "ic": P.bw0, "tc": P.bwf, "etax": P.ttr, "etau": P.ttr, "etap": P.ttrp if npp else 0.0,
+                     "v": P.hw}
+        self.h = h = self.h_vec()
+        self.nrm_h = max(1.0, np.sqrt(sum((h[g] ** 2).sum() for g in h)))
+        self.nrm_c = max(1.0, np.sqrt((P.q ** 2).sum() + (P.qp ** 2).sum() + sum(np.sum(np.asarray(v, float) ** 2) for v in
+                                                                                  (P.om, P.bw0, P.bwf, P.ttr, P.ttr, P.hw))
+                                      + (P.ttrp ** 2 if npp else 0.0)))
+        self.deg = sum(h[g].size for g in LPG) + N * P.nsoc
+
+    def zeros_like_rows(self):
+        P = self.P
+        d = {g: np.zeros(sh + (2,)) for g, sh in self.groups_pair.items()}
+        d["lin"] = np.zeros((P.N, P.nl)); d["glin"] = np.zeros(P.ng); d["soc"] = np.zeros((P.N, P.nsoc, 4))
         return d
 
-    def G_apply(z, p, aux):
+    def G_apply(self, z, p, aux):
         """G xi per row (xi = main + aux)."""
+        P, nx, ns, o_soc = self.P, self.P.nx, self.P.ns, self.o_soc
         a = _rows_eval_lin(P, z, p)
-        out = zeros_like_rows()
+        out = self.zeros_like_rows()
         for g in ("dyn", "ic", "tc"):
             out[g][..., 0] = a[g] - aux[g]; out[g][..., 1] = -a[g] - aux[g]
         out["tr"][:, :nx, 0] = a["tr"][:, :nx] - aux["etax"][:, None]; out["tr"][:, :nx, 1] = -a["tr"][:, :nx] - aux["etax"][:, None]
@@ -376,10 +363,11 @@ def solve(P, max_iter=100, feastol=1e-8, abstol=1e-8, reltol=1e-8, verbose=False
         out["soc"] = -_soc_split(P, a["loc"])    # G = -M for cone rows
         return out
 
-    def h_vec():
+    def h_vec(self):
         """h per row (G xi + s = h)."""
-        c = _rows_eval(P, np.zeros((N, nz)), np.zeros(npp))  # a(0) = constants
-        out = zeros_like_rows()
+        P, ns, o_soc = self.P, self.P.ns, self.o_soc
+        c = _rows_eval(P, np.zeros((P.N, P.nz)), np.zeros(P.np))  # a(0) = constants
+        out = self.zeros_like_rows()
         for g in ("dyn", "ic", "tc"):
             out[g][..., 0] = -c[g]; out[g][..., 1] = c[g]
         out["tr"][..., 0] = -c["tr"]; out["tr"][..., 1] = c["tr"]
@@ -389,8 +377,9 @@ def solve(P, max_iter=100, feastol=1e-8, abstol=1e-8, reltol=1e-8, verbose=False
         out["soc"] = _soc_split(P, c["loc"])
         return out
 
-    def GT_apply(lam):
+    def GT_apply(self, lam):
         """G' lam -> (gz, gp, gaux)."""
+        P, N, nx, npp, ns, o_soc = self.P, self.P.N, self.P.nx, self.P.np, self.P.ns, self.o_soc
         mu = {"dyn": lam["dyn"][..., 0] - lam["dyn"][..., 1], "ic": lam["ic"][..., 0] - lam["ic"][..., 1],
               "tc": lam["tc"][..., 0] - lam["tc"][..., 1], "tr": lam["tr"][..., 0] - lam["tr"][..., 1],
               "trp": lam["trp"][..., 0] - lam["trp"][..., 1], "glin": lam["glin"]}
@@ -404,22 +393,14 @@ def solve(P, max_iter=100, feastol=1e-8, abstol=1e-8, reltol=1e-8, verbose=False
                 "etap": -(lam["trp"].sum()) if npp else 0.0, "v": -(lam["hinge"][..., 0] + lam["hinge"][..., 1])}
         return gz, gp, gaux
 
-    caux = {"dyn": P.om, "ic": P.bw0, "tc": P.bwf, "etax": P.ttr, "etau": P.ttr, "etap": P.ttrp if npp else 0.0,
-            "v": P.hw}
-    LPG = ("dyn", "ic", "tc", "tr", "trp", "hinge", "lin", "glin")
-    h = h_vec()
-    nrm_h = max(1.0, np.sqrt(sum((h[g] ** 2).sum() for g in h)))
-    nrm_c = max(1.0, np.sqrt((P.q ** 2).sum() + (P.qp ** 2).sum() + sum(np.sum(np.asarray(v, float) ** 2) for v in
-                                                                         (P.om, P.bw0, P.bwf, P.ttr, P.ttr, P.hw))
-                             + (P.ttrp ** 2 if npp else 0.0)))
-    deg = sum(h[g].size for g in LPG) + N * nsoc
-
-    def newton(w, Wsoc_i, rtil, rx):
-        """Solve (P + G'W^-2 G) dxi = -rx - G'W^-2 rtil with aux elimination; returns dz, dp, daux.
-        w: LP row weights (lam/s) per group; Wsoc[N,nsoc,4,4]: NT W; rtil: per-row r~z; rx = (rxz, rxp, rxaux)."""
+    def newton(self, w, Wsoc_i, rtil, rx):
+        """Solve (P + G'W^-2 G) dxi = -rx - G'W^-2 rtil with aux elimination; returns dz, dp, daux, nus.
+        w: LP row weights (lam/s) per group; Wsoc_i[N,nsoc,4,4]: NT W^-1; rtil: per-row r~z; rx = (rxz, rxp, rxaux)."""
+        P, reg, o_soc = self.P, self.reg, self.o_soc
+        N, nx, nu, nz, npp, ns, nsoc = P.N, P.nx, P.nu, P.nz, P.np, P.ns, P.nsoc
         rxz, rxp, rxaux = rx
         rho = {g: w[g] * rtil[g] for g in LPG}
-        T = np.zeros((N, nz, nz)); U = np.zeros((max(N - 1, 0), nz, nz)); C = np.zeros((N, nz, npp)); Dp = np.diag(P.Qp.copy()) if npp else np.zeros((0, 0))
+        T = np.zeros((N, nz, nz)); C = np.zeros((N, nz, npp)); Dp = np.diag(P.Qp.copy()) if npp else np.zeros((0, 0))
         bz = -rxz.copy(); bp = -rxp.copy()
         T[:, np.arange(nz), np.arange(nz)] += P.Qd
         tau = {}
@@ -540,219 +521,181 @@ def solve(P, max_iter=100, feastol=1e-8, abstol=1e-8, reltol=1e-8, verbose=False
             daux["v"] = np.zeros((N, 0))
         return dz, dp, daux, nus
 
-    # ---------------- initial point: (P + G'G) xi = -c + G'h, lam = G xi - h, s = -lam, shift ----------------
-    w1 = {g: np.ones_like(h[g]) for g in LPG}
-    Wsoc = np.tile(np.eye(4), (N, nsoc, 1, 1)); Wsoc_i = Wsoc.copy(); Wsoc_i2 = Wsoc.copy()
-    rtil0 = {g: -h[g] for g in h}
-    rx0 = (P.q.copy(), P.qp.copy(), {k_: np.array(v, float) * 1.0 for k_, v in caux.items()})
-    z, p, aux, _ = newton(w1, Wsoc_i, rtil0, rx0)
-
-    def check_newton(w_, Wsoc_, rtil_, rx_, dz_, dp_, daux_):
-        """residual of the un-eliminated Newton system  P dxi + G'W^-2(G dxi + r~z) + rx = 0."""
-        Gd_ = G_apply(dz_, dp_, daux_)
-        lam_ = {g: w_[g] * (Gd_[g] + rtil_[g]) for g in LPG}
-        lam_["soc"] = np.zeros((N, nsoc, 4))
-        for k in range(N):
-            for j in range(nsoc):
-                lam_["soc"][k, j] = Wsoc_[k, j] @ (Wsoc_[k, j] @ (Gd_["soc"][k, j] + rtil_["soc"][k, j]))
-        gz_, gp_, gaux_ = GT_apply(lam_)
-        e = [np.abs(P.Qd * dz_ + gz_ + rx_[0]).max()]
-        if npp:
-            e.append(np.abs(P.Qp * dp_ + gp_ + rx_[1]).max())
-        for k_ in gaux_:
-            e.append(np.max(np.abs(np.asarray(gaux_[k_]) + np.asarray(rx_[2][k_]))) if np.size(gaux_[k_]) else 0.0)
-        return max(e)
-    if debug:
-        print("init newton residual", check_newton(w1, Wsoc_i, rtil0, rx0, z, p, aux))
-
-    def dlam_from(w_, Wi_, Gd_, rtil_, nus_, rxaux_):
+    def dlam_from(self, w, Wi, Gd, rtil, nus, rxaux):
         """dlam = W^-2 (G dxi + r~z); for the penalised pair rows (dyn, ic, tc, hinge) the multipliers are
         recovered from the augmented unknown nu and the aux dual-feasibility row instead, which avoids
         the amplification by w = lam/s ~ omega^2/mu:   type A: dl1 - dl2 = nu, dl1 + dl2 = rx_y;
         hinge: dl1 = nu, dl1 + dl2 = rx_v."""
-        out = {g: w_[g] * (Gd_[g] + rtil_[g]) for g in LPG}
+        P = self.P
+        out = {g: w[g] * (Gd[g] + rtil[g]) for g in LPG}
         for g in ("dyn", "ic", "tc"):
-            out[g] = np.stack([0.5 * (rxaux_[g] + nus_[g]), 0.5 * (rxaux_[g] - nus_[g])], axis=-1)
-        if ns:
-            out["hinge"] = np.stack([nus_["hinge"], rxaux_["v"] - nus_["hinge"]], axis=-1)
-        out["soc"] = np.zeros((N, nsoc, 4))
-        for k in range(N):
-            for j in range(nsoc):
-                out["soc"][k, j] = Wi_[k, j] @ (Wi_[k, j] @ (Gd_["soc"][k, j] + rtil_["soc"][k, j]))
+            out[g] = np.stack([0.5 * (rxaux[g] + nus[g]), 0.5 * (rxaux[g] - nus[g])], axis=-1)
+        if P.ns:
+            out["hinge"] = np.stack([nus["hinge"], rxaux["v"] - nus["hinge"]], axis=-1)
+        out["soc"] = np.zeros((P.N, P.nsoc, 4))
+        for k in range(P.N):
+            for j in range(P.nsoc):
+                out["soc"][k, j] = Wi[k, j] @ (Wi[k, j] @ (Gd["soc"][k, j] + rtil["soc"][k, j]))
         return out
 
-    def newton_refined(w_, W_, Wi_, rtil_, rx_, nref):
+    def newton_refined(self, w, W, Wi, rtil, rx, nref):
         """Newton step with iterative refinement in AUGMENTED form (dxi and dlam are both iterates):
              r1 = -rx - P dxi - G'dlam,   r2 = -r~z - G dxi + W^2 dlam   (O(1)-scaled residuals)
-           correction: H e = r1 + G'W^-2 r2,  elam = W^-2 (G e - r2)."""
-        dz_, dp_, daux_, nus_ = newton(w_, Wi_, rtil_, rx_)
-        Gd_ = G_apply(dz_, dp_, daux_)
-        dl_ = dlam_from(w_, Wi_, Gd_, rtil_, nus_, rx_[2])
+           correction: H e = r1 + G'W^-2 r2,  elam = W^-2 (G e - r2).
+           Returns (dz, dp, daux, dlam, G dxi)."""
+        P = self.P
+        dz, dp, daux, nus = self.newton(w, Wi, rtil, rx)
+        Gd = self.G_apply(dz, dp, daux)
+        dl = self.dlam_from(w, Wi, Gd, rtil, nus, rx[2])
         for _ in range(nref):
-            gz_, gp_, gaux_ = GT_apply(dl_)
-            r1 = (-(rx_[0] + P.Qd * dz_ + gz_), -(rx_[1] + P.Qp * dp_ + gp_),
-                  {k_: -(np.asarray(rx_[2][k_]) + np.asarray(gaux_[k_])) for k_ in gaux_})
-            r2 = {g: -rtil_[g] - Gd_[g] + dl_[g] / w_[g] for g in LPG}
-            r2["soc"] = np.zeros((N, nsoc, 4))
-            for k in range(N):
-                for j in range(nsoc):
-                    r2["soc"][k, j] = -rtil_["soc"][k, j] - Gd_["soc"][k, j] + W_[k, j] @ (W_[k, j] @ dl_["soc"][k, j])
-            if debug:
-                print("      refine: |r1z| %.2e |r1p| %.2e |r1aux| %.2e |r2| %.2e" % (
-                    np.abs(r1[0]).max(), np.abs(r1[1]).max() if npp else 0,
-                    max(np.max(np.abs(v)) if np.size(v) else 0 for v in r1[2].values()),
-                    max(np.max(np.abs(v)) if np.size(v) else 0 for v in r2.values())))
-            # adaptive: skip the correction solve when the residual of the computed direction is already tiny
-            # relative to the right-hand side it was computed for
-            r1n = max([np.abs(r1[0]).max(), np.abs(r1[1]).max() if npp else 0.0] + [np.max(np.abs(v)) if np.size(v) else 0.0 for v in r1[2].values()])
-            rxn = max([np.abs(rx_[0]).max(), np.abs(rx_[1]).max() if npp else 0.0] + [np.max(np.abs(v)) if np.size(v) else 0.0 for v in rx_[2].values()])
-            r2n = max(np.max(np.abs(v)) if np.size(v) else 0.0 for v in r2.values())
-            rtn = max(np.max(np.abs(v)) if np.size(v) else 0.0 for v in rtil_.values())
-            if ref_log is not None:
-                ref_log.append((r1n, rxn, r2n, rtn, np.sqrt(sum((np.asarray(v) ** 2).sum() for v in [r1[0], r1[1]] + list(r1[2].values()))) / nrm_c))
-            r1rel = np.sqrt(sum((np.asarray(v) ** 2).sum() for v in [r1[0], r1[1]] + list(r1[2].values()))) / nrm_c
-            r2rel = np.sqrt(sum((np.asarray(v) ** 2).sum() for v in r2.values())) / nrm_h
-            if r1rel <= ref_tol * feastol and r2rel <= ref_tol * feastol:
+            gz, gp, gaux = self.GT_apply(dl)
+            r1 = (-(rx[0] + P.Qd * dz + gz), -(rx[1] + P.Qp * dp + gp),
+                  {k_: -(np.asarray(rx[2][k_]) + np.asarray(gaux[k_])) for k_ in gaux})
+            r2 = {g: -rtil[g] - Gd[g] + dl[g] / w[g] for g in LPG}
+            r2["soc"] = np.zeros((P.N, P.nsoc, 4))
+            for k in range(P.N):
+                for j in range(P.nsoc):
+                    r2["soc"][k, j] = -rtil["soc"][k, j] - Gd["soc"][k, j] + W[k, j] @ (W[k, j] @ dl["soc"][k, j])
+            # the correction solve is skipped only where the computed direction has no residual at all
+            r1rel = _norm([r1[0], r1[1]] + list(r1[2].values())) / self.nrm_c
+            r2rel = _norm(r2.values()) / self.nrm_h
+            if r1rel == 0.0 and r2rel == 0.0:
                 break
             mr2 = {g: -r2[g] for g in r2}
             mr1aux = {k_: -r1[2][k_] for k_ in r1[2]}
-            ez, ep, eaux, enus = newton(w_, Wi_, mr2, (-r1[0], -r1[1], mr1aux))
-            Ge = G_apply(ez, ep, eaux)
-            el = dlam_from(w_, Wi_, Ge, mr2, enus, mr1aux)
-            dz_ = dz_ + ez; dp_ = dp_ + ep
-            daux_ = {k_: daux_[k_] + eaux[k_] for k_ in daux_}
-            dl_ = {g: dl_[g] + el[g] for g in dl_}
-            Gd_ = {g: Gd_[g] + Ge[g] for g in Gd_}
-        return dz_, dp_, daux_, dl_, Gd_
+            ez, ep, eaux, enus = self.newton(w, Wi, mr2, (-r1[0], -r1[1], mr1aux))
+            Ge = self.G_apply(ez, ep, eaux)
+            el = self.dlam_from(w, Wi, Ge, mr2, enus, mr1aux)
+            dz = dz + ez; dp = dp + ep
+            daux = {k_: daux[k_] + eaux[k_] for k_ in daux}
+            dl = {g: dl[g] + el[g] for g in dl}
+            Gd = {g: Gd[g] + Ge[g] for g in Gd}
+        return dz, dp, daux, dl, Gd
 
-    Gx = G_apply(z, p, aux)
-    lam = {g: Gx[g] - h[g] for g in h}
-    s = {g: -lam[g] for g in h}
-    if init == "two":
-        # ECOS-style: primal point from min |G xi - h|^2 (+ xi'P xi), dual point from min |lam|^2 s.t. dual feasibility
-        rx_zero = (np.zeros_like(P.q), np.zeros_like(P.qp), {k_: np.zeros_like(np.array(v, float)) for k_, v in caux.items()})
-        z, p, aux, _ = newton(w1, Wsoc_i, rtil0, rx_zero)
-        Gx = G_apply(z, p, aux)
-        s = {g: h[g] - Gx[g] for g in h}
-        rt_zero = {g: np.zeros_like(h[g]) for g in h}
-        zd, pd, auxd, _ = newton(w1, Wsoc_i, rt_zero, rx0)
-        lam = G_apply(zd, pd, auxd)
-
-    def min_margin(v):
+    def min_margin(self, v):
         m = min([v[g].min() for g in LPG if v[g].size] + [np.inf])
-        if nsoc:
+        if self.P.nsoc:
             m = min(m, (v["soc"][..., 0] - np.linalg.norm(v["soc"][..., 1:], axis=-1)).min())
         return m
 
-    def shift(v):
-        m = min_margin(v)
-        if m <= 0:
-            for g in LPG:
-                v[g] = v[g] + (1.0 - m)
-            if nsoc:
-                v["soc"][..., 0] += (1.0 - m)
-        return v
-    s = shift(s); lam = shift(lam)
-    if init == "mehrotra":
-        # Mehrotra's LP starting-point balancing on top of the two-solve point
-        def tot(v):
-            return sum(v[g].sum() for g in LPG) + (v["soc"][..., 0].sum() if nsoc else 0.0)
-        sl = sum((s[g] * lam[g]).sum() for g in h)
-        ds_ = 0.5 * sl / tot(lam); dl_ = 0.5 * sl / tot(s)
-        for g in LPG:
-            s[g] = s[g] + ds_; lam[g] = lam[g] + dl_
-        if nsoc:
-            s["soc"][..., 0] += ds_; lam["soc"][..., 0] += dl_
-    if init == "struct":
-        m0 = mu0 if mu0 is not None else 1e-3
-        z = P.zref.copy(); p = P.pref.copy()
-        a0 = _rows_eval(P, z, p)
-        aux = {}
-        def typeA(a_, om_):
-            om_ = np.maximum(om_, 1e-300)
-            return (m0 + np.sqrt(m0 * m0 + om_ * om_ * a_ * a_)) / om_
-        aux["dyn"] = typeA(a0["dyn"], P.om); aux["ic"] = typeA(a0["ic"], P.bw0); aux["tc"] = typeA(a0["tc"], P.bwf)
-        aux["etax"] = 2 * nx * m0 / P.ttr; aux["etau"] = 2 * nu * m0 / P.ttr
-        aux["etap"] = (2 * npp * m0 / P.ttrp) if npp else 0.0
-        if ns:
-            ah = a0["loc"][:, :ns]
-            # hinge: s1 = v - a, s2 = v, lam1 + lam2 = hw, s1 lam1 = s2 lam2 = m0 -> m0/(v-a) + m0/v = hw
-            # hw v^2 - (hw a + 2 m0) v + m0 a = 0
-            bq = P.hw * ah + 2 * m0
-            aux["v"] = (bq + np.sqrt(bq * bq - 4 * P.hw * m0 * ah)) / (2 * P.hw)
-        else:
-            aux["v"] = np.zeros((N, 0))
-        Gx = G_apply(z, p, aux)
+    def initial_point(self):
+        """ECOS's starting point, two solves with weights 1 and cones W = I: the primal point from min |G xi - h|^2 (+ xi'P xi),
+        the dual point from min |lam|^2 s.t. dual feasibility; s and lam are shifted into the cone where they are outside."""
+        P, h = self.P, self.h
+        w1 = {g: np.ones_like(h[g]) for g in LPG}
+        Wsoc_i = np.tile(np.eye(4), (P.N, P.nsoc, 1, 1))
+        rtil0 = {g: -h[g] for g in h}
+        rx0 = (P.q.copy(), P.qp.copy(), {k_: np.array(v, float) * 1.0 for k_, v in self.caux.items()})
+        rx_zero = (np.zeros_like(P.q), np.zeros_like(P.qp), {k_: np.zeros_like(np.array(v, float)) for k_, v in self.caux.items()})
+        z, p, aux, _ = self.newton(w1, Wsoc_i, rtil0, rx_zero)
+        Gx = self.G_apply(z, p, aux)
         s = {g: h[g] - Gx[g] for g in h}
-        # non-epigraph rows: floor the slack
-        fl = np.sqrt(m0)
-        for g in ("lin", "glin"):
-            s[g] = np.maximum(s[g], fl)
-        if nsoc:
-            marg = s["soc"][..., 0] - np.linalg.norm(s["soc"][..., 1:], axis=-1)
-            s["soc"][..., 0] += np.maximum(fl - marg, 0.0)
-        lam = {g: m0 / s[g] for g in LPG}
-        if nsoc:
-            # lam = m0 * s^-1 (Jordan inverse): s o lam = m0 e
-            lam["soc"] = np.zeros_like(s["soc"])
-            for k in range(N):
-                for j in range(nsoc):
-                    sv = s["soc"][k, j]; det = sv[0] ** 2 - sv[1:] @ sv[1:]
-                    lam["soc"][k, j] = m0 * np.concatenate([[sv[0]], -sv[1:]]) / det
-    if warm is not None:
-        # warm start from the previous subproblem's iterate: keep (xi, s, lam) but push the complementarity pairs
-        # back into the interior (s, lam) <- (s, lam) + delta * (cold-start scale)
-        z = warm["z"].copy(); p = warm["p"].copy(); aux = {k_: np.array(v, float).copy() for k_, v in warm["aux"].items()}
-        for g in h:
-            if g == "soc":
-                continue
-            ds_ = warm_delta * np.maximum(1.0, np.abs(warm["s"][g]).max() if warm["s"][g].size else 1.0)
-            s[g] = warm["s"][g] + warm_delta * max(1.0, float(np.mean(s[g]))) if s[g].size else s[g]
-            lam[g] = warm["lam"][g] + warm_delta * max(1.0, float(np.mean(lam[g]))) if lam[g].size else lam[g]
-        if nsoc:
-            s["soc"] = warm["s"]["soc"].copy(); lam["soc"] = warm["lam"]["soc"].copy()
-            s["soc"][..., 0] += warm_delta * max(1.0, float(np.mean(np.abs(s["soc"][..., 0]))))
-            lam["soc"][..., 0] += warm_delta * max(1.0, float(np.mean(np.abs(lam["soc"][..., 0]))))
+        rt_zero = {g: np.zeros_like(h[g]) for g in h}
+        zd, pd, auxd, _ = self.newton(w1, Wsoc_i, rt_zero, rx0)
+        lam = self.G_apply(zd, pd, auxd)
+        for v in (s, lam):
+            m = self.min_margin(v)
+            if m <= 0:
+                for g in LPG:
+                    v[g] = v[g] + (1.0 - m)
+                if P.nsoc:
+                    v["soc"][..., 0] += (1.0 - m)
+        return z, p, aux, s, lam
 
-    status = "ITERATION_LIMIT"
-    info = {}
-    best = None
-    w_last = None
-    for it in range(max_iter + 1):
-        gz, gp, gaux = GT_apply(lam)
+    def residuals(self, z, p, aux, s, lam):
+        """Residuals rx = P xi + c + G'lam and rz = G xi + s - h of an iterate, costs, gap and the relative measures."""
+        P, h, caux = self.P, self.h, self.caux
+        gz, gp, gaux = self.GT_apply(lam)
         rxz = P.Qd * z + P.q + gz
         rxp = P.Qp * p + P.qp + gp
         rxaux = {k_: np.asarray(caux[k_], float) + gaux[k_] for k_ in caux}
-        Gx = G_apply(z, p, aux)
+        Gx = self.G_apply(z, p, aux)
         rz = {g: Gx[g] + s[g] - h[g] for g in h}
-        if track_rz and it > 0:
-            # the Newton step reduces the (linear) primal residual exactly by (1 - alpha): track it instead of
-            # re-evaluating G xi + s - h, whose O(1) terms cancel and leave O(eps) noise that the next step would
-            # try to remove from slacks that are themselves O(eps / weight) on the heavily penalised rows
-            rz = {g: (1.0 - a_last) * rz_last[g] for g in h}
-            if np.sqrt(sum((rz[g] ** 2).sum() for g in h)) / nrm_h < 1e-14:
-                rz = {g: np.zeros_like(rz[g]) for g in h}
-        rz_last = rz
         gap = sum((s[g] * lam[g]).sum() for g in h)
         cx_lin = (P.q * z).sum() + P.qp @ p + (P.om * aux["dyn"]).sum() + P.bw0 @ aux["ic"] + P.bwf @ aux["tc"] + \
-            P.ttr @ aux["etax"] + P.ttr @ aux["etau"] + (P.ttrp * aux["etap"] if npp else 0.0) + (P.hw * aux["v"]).sum()
+            P.ttr @ aux["etax"] + P.ttr @ aux["etau"] + (P.ttrp * aux["etap"] if P.np else 0.0) + (P.hw * aux["v"]).sum()
         pcost = 0.5 * ((P.Qd * z * z).sum() + (P.Qp * p * p).sum()) + cx_lin
         dcost = pcost + sum((lam[g] * rz[g]).sum() for g in h) - gap
-        pres = np.sqrt(sum((rz[g] ** 2).sum() for g in h)) / nrm_h
-        dres = np.sqrt((rxz ** 2).sum() + (rxp ** 2).sum() + sum(np.sum(np.asarray(v) ** 2) for v in rxaux.values())) / nrm_c
+        pres = np.sqrt(sum((rz[g] ** 2).sum() for g in h)) / self.nrm_h
+        dres = np.sqrt((rxz ** 2).sum() + (rxp ** 2).sum() + sum(np.sum(np.asarray(v) ** 2) for v in rxaux.values())) / self.nrm_c
         relgap = gap / -pcost if pcost < 0 else (gap / dcost if dcost > 0 else np.inf)
-        info = dict(z=z, p=p, aux=aux, s=s, lam=lam, pcost=pcost, dcost=dcost, gap=gap, pres=pres, dres=dres,
-                    relgap=relgap, iters=it)
-        if trace is not None:
-            trace.append(dict(it=it, pcost=pcost, dcost=dcost, gap=gap, pres=pres, dres=dres))
-        if debug:
-            ij = np.unravel_index(np.argmax(np.abs(rxz)), rxz.shape)
-            print("   argmax rxz at stage %d comp %d; w tr there: %s" % (ij[0], ij[1], w_last["tr"][ij[0], ij[1]] if w_last else None))
-            print("   rx comps: z %.2e p %.2e " % (np.abs(rxz).max(), np.abs(rxp).max() if npp else 0) +
-                  " ".join("%s %.2e" % (k_, np.max(np.abs(v)) if np.size(v) else 0) for k_, v in rxaux.items()))
-        if verbose:
-            print("%3d pcost % .8e dcost % .8e gap %.2e pres %.2e dres %.2e" % (it, pcost, dcost, gap, pres, dres))
-        merit = max(pres / feastol, dres / feastol, min(gap / abstol, relgap / reltol))
+        return (rxz, rxp, rxaux), rz, dict(pcost=pcost, dcost=dcost, gap=gap, pres=pres, dres=dres, relgap=relgap)
+
+    def nt_update(self, s, lam):
+        """Scalings of the iterate: w = lam / s on the orthant rows; W, W lam and W^-1 of every cone."""
+        P = self.P
+        w = {g: lam[g] / s[g] for g in LPG}
+        Wsoc = np.zeros((P.N, P.nsoc, 4, 4)); lsoc = np.zeros((P.N, P.nsoc, 4)); Wsoc_i = np.zeros((P.N, P.nsoc, 4, 4))
+        for k in range(P.N):
+            for j in range(P.nsoc):
+                Wsoc[k, j], lsoc[k, j], Wsoc_i[k, j] = _nt(s["soc"][k, j], lam["soc"][k, j])
+        return w, Wsoc, lsoc, Wsoc_i
+
+    def combined_rhs(self, sigma, mu, rz, s, lam, dsa, dla, Wsoc, lsoc, Wsoc_i):
+        """Right-hand side of the corrector: r~z = rz - s + (sigma mu e - ds_a o dl_a) / lam, for the cones
+        d_s = sigma mu e - lam o lam - (W^-T ds_a) o (W dl_a) in the NT-scaled space."""
+        P = self.P
+        rtil = {g: rz[g] - s[g] + (sigma * mu - dsa[g] * dla[g]) / lam[g] for g in LPG}
+        rtil["soc"] = np.zeros((P.N, P.nsoc, 4))
+        for k in range(P.N):
+            for j in range(P.nsoc):
+                W = Wsoc[k, j]; l_ = lsoc[k, j]
+                e = np.array([1.0, 0, 0, 0])
+                d_s = sigma * mu * e - _jprod(l_, l_) - _jprod(Wsoc_i[k, j] @ dsa["soc"][k, j], W @ dla["soc"][k, j])
+                rtil["soc"][k, j] = rz["soc"][k, j] + W @ _jinv(l_, d_s)
+        return rtil
+
+    def _cone_step(self, v, dv):
+        a = np.inf
+        for g in LPG:
+            neg = dv[g] < 0
+            if neg.any():
+                a = min(a, np.min(-v[g][neg] / dv[g][neg]))
+        for k in range(self.P.N):
+            for j in range(self.P.nsoc):
+                a = min(a, _soc_max_step(v["soc"][k, j], dv["soc"][k, j]))
+        return a
+
+    def max_step(self, s, ds, lam, dl):
+        """The largest step that keeps s + a ds and lam + a dl in the cone."""
+        return min(self._cone_step(s, ds), self._cone_step(lam, dl))
+
+    def take_step(self, am, z, p, aux, s, lam, dz, dp, daux, ds, dl):
+        """One step length for (xi, s, lam): 0.99 of the way to the boundary, backed off by 0.8 while the new point is
+        not strictly interior."""
+        h = self.h
+        a = min(1.0, 0.99 * am)
+        for _ in range(60):
+            sn = {g: s[g] + a * ds[g] for g in h}; ln = {g: lam[g] + a * dl[g] for g in h}
+            if self.min_margin(sn) > 0 and self.min_margin(ln) > 0:
+                break
+            a *= 0.8
+        z = z + a * dz; p = p + a * dp
+        aux = {k_: aux[k_] + a * daux[k_] for k_ in aux}
+        return z, p, aux, sn, ln
+
+
+def solve(P, max_iter=100, feastol=1e-8, abstol=1e-8, reltol=1e-8, nref=1, stall=3, reg=5e-11, ref_gap=1e-2):
+    """Cold solve of one stage problem by the structured primal-dual method K3 ships: the two-solve ECOS starting point, Mehrotra's
+    predictor-corrector with sigma = (1 - a_aff)^3, one common step length, `nref` refinement steps of both directions once
+    relgap < ref_gap, stop when the merit has not improved for `stall` iterations (the best iterate is returned), ECOS's reduced
+    tolerances for ALMOST_OPTIMAL.  Returns dict(status, z, p, iters, pcost, ...).
+
+    reg, the static regularisation of the nu-blocks, is 5e-11 here and 1e-12 on the device and in the twin.  The device could lower
+    it because it escalates it per problem when a factorisation breaks down, and needed to for the end game of its warm starts
+    from very fine snapshots.  Neither exists here -- a single cold solve, no end-game warm start -- the refinement removes the
+    effect of either value at the accuracy the tests ask for, and the pinned results were recorded with this one."""
+    K = _Ipm(P, reg)
+    h = K.h
+    z, p, aux, s, lam = K.initial_point()
+
+    status = "ITERATION_LIMIT"
+    best = None
+    for it in range(max_iter + 1):
+        rx, rz, m = K.residuals(z, p, aux, s, lam)
+        gap, relgap = m["gap"], m["relgap"]
+        info = dict(z=z, p=p, aux=aux, s=s, lam=lam, iters=it, **m)
+        merit = max(m["pres"] / feastol, m["dres"] / feastol, min(gap / abstol, relgap / reltol))
         if best is None or merit < best[0]:
             best = (merit, dict(info))
         if merit <= 1.0:
@@ -760,145 +703,32 @@ def solve(P, max_iter=100, feastol=1e-8, abstol=1e-8, reltol=1e-8, verbose=False
             break
         if it == max_iter:
             break
-        # stall / divergence guard: normal equations lose accuracy once the gap is tiny; stop when the
+        # stall / divergence guard: the directions lose accuracy once the gap is tiny; stop when the
         # merit has not improved for `stall` iterations (the best iterate is returned)
         if best[0] <= 1e3 and it - best[1]["iters"] >= stall:
             break
-        # scalings
-        w = {g: lam[g] / s[g] for g in LPG}
-        w_last = w
-        Wsoc = np.zeros((N, nsoc, 4, 4)); lsoc = np.zeros((N, nsoc, 4))
-        Wsoc_i = np.zeros((N, nsoc, 4, 4)); Wsoc_i2 = np.zeros((N, nsoc, 4, 4))
-        for k in range(N):
-            for j in range(nsoc):
-                Wsoc[k, j], lsoc[k, j], Wsoc_i[k, j], Wsoc_i2[k, j] = _nt(s["soc"][k, j], lam["soc"][k, j])
+        w, Wsoc, lsoc, Wsoc_i = K.nt_update(s, lam)
         if not (np.all(np.isfinite(Wsoc)) and all(np.all(np.isfinite(w[g])) for g in LPG)):
             status = "NUMERICAL_ERROR"
             break
-        mu = gap / deg
+        mu = gap / K.deg
         # iterative refinement only once the gap is small: the Newton system is well conditioned early on
         nref_it = nref if relgap < ref_gap else 0
-        # affine direction: r~z = rz - s (LP), rz + W'(lam\(-lam o lam)) = rz - W lam_s = rz - s (SOC too)
-        rtil = {g: rz[g] - s[g] for g in h}
-        if debug and hook is not None:
-            hook(dict(it=it, w=w, Wsoc=Wsoc, Wsoc_i=Wsoc_i, rtil=rtil, rx=(rxz, rxp, rxaux), newton=newton,
-                      G_apply=G_apply, GT_apply=GT_apply, h=h, LPG=LPG, caux=caux))
         try:
-            dz, dp, daux, dla, Gd = newton_refined(w, Wsoc, Wsoc_i, rtil, (rxz, rxp, rxaux), nref_it if ref_affine else 0)
+            # predictor (affine direction): r~z = rz - s (LP), rz + W'(lam\(-lam o lam)) = rz - W lam_s = rz - s (SOC too)
+            rtil = {g: rz[g] - s[g] for g in h}
+            dz, dp, daux, dla, Gd = K.newton_refined(w, Wsoc, Wsoc_i, rtil, rx, nref_it)
+            dsa = {g: -rz[g] - Gd[g] for g in h}
+            a_aff = min(1.0, K.max_step(s, dsa, lam, dla))
+            sigma = (1 - a_aff) ** 3
+            # corrector (combined direction)
+            rtil = K.combined_rhs(sigma, mu, rz, s, lam, dsa, dla, Wsoc, lsoc, Wsoc_i)
+            dz, dp, daux, dl, Gd = K.newton_refined(w, Wsoc, Wsoc_i, rtil, rx, nref_it)
         except np.linalg.LinAlgError:
-            if debug:
-                raise
             status = "NUMERICAL_ERROR"
             break
-        dsa = {g: -rz[g] - Gd[g] for g in h}
-
-        def max_step(v, dv):
-            a = np.inf
-            for g in LPG:
-                neg = dv[g] < 0
-                if neg.any():
-                    a = min(a, np.min(-v[g][neg] / dv[g][neg]))
-            for k in range(N):
-                for j in range(nsoc):
-                    a = min(a, _soc_max_step(v["soc"][k, j], dv["soc"][k, j]))
-            return a
-        a_aff = min(1.0, max_step(s, dsa), max_step(lam, dla))
-        sigma = max(sigma_min, (1 - a_aff) ** 3)
-        if sigma_rule == "mehrotra":
-            # Mehrotra's original rule: (mu_aff / mu)^3 with mu_aff the complementarity after the affine step
-            g_aff = sum(((s[g] + a_aff * dsa[g]) * (lam[g] + a_aff * dla[g])).sum() for g in h)
-            sigma = max(sigma_min, min(1.0, (max(g_aff, 0.0) / gap) ** 3))
-        rs_ = (1.0 - sigma) if resid_scale else 1.0   # CVXOPT/ECOS: residuals scaled by (1 - sigma) in the combined step
-        # combined direction: d_s = sigma mu e - lam o lam - (W^-T ds_a) o (W dz_a)
-        rtil2 = {g: rs_ * rz[g] - s[g] + (sigma * mu - dsa[g] * dla[g]) / lam[g] for g in LPG}
-        rtil2["soc"] = np.zeros((N, nsoc, 4))
-        for k in range(N):
-            for j in range(nsoc):
-                W = Wsoc[k, j]; l_ = lsoc[k, j]
-                e = np.array([1.0, 0, 0, 0])
-                d_s = sigma * mu * e - _jprod(l_, l_) - _jprod(Wsoc_i[k, j] @ dsa["soc"][k, j], W @ dla["soc"][k, j])
-                rtil2["soc"][k, j] = rs_ * rz["soc"][k, j] + W @ _jinv(l_, d_s)
-        try:
-            dz, dp, daux, dl, Gd = newton_refined(w, Wsoc, Wsoc_i, rtil2, (rs_ * rxz, rs_ * rxp, {k_: rs_ * v for k_, v in rxaux.items()}), nref_it)
-        except np.linalg.LinAlgError:
-            if debug:
-                raise
-            status = "NUMERICAL_ERROR"
-            break
-        ds = {g: -rs_ * rz[g] - Gd[g] for g in h}
-        # ---- Gondzio multiple centrality correctors (LP rows only) ----
-        for ic_ in range(ncorr):
-            a0_ = min(1.0, step_frac * min(max_step(s, ds), max_step(lam, dl)))
-            at_ = min(1.0, a0_ + corr_delta)
-            mu_t = sigma * mu
-            bmin, bmax = 0.1, 10.0
-            rt3 = {g: rtil2[g].copy() for g in rtil2}
-            for g in LPG:
-                v_ = (s[g] + at_ * ds[g]) * (lam[g] + at_ * dl[g])
-                t_ = np.clip(v_, bmin * mu_t, bmax * mu_t)
-                c_ = np.maximum(t_ - v_, -bmax * mu_t)
-                rt3[g] = rtil2[g] + c_ / lam[g]
-            dz3, dp3, daux3, dl3, Gd3 = newton_refined(w, Wsoc, Wsoc_i, rt3, (rs_ * rxz, rs_ * rxp, {k_: rs_ * v for k_, v in rxaux.items()}), nref_it)
-            ds3 = {g: -rs_ * rz[g] - Gd3[g] for g in h}
-            a3_ = min(1.0, step_frac * min(max_step(s, ds3), max_step(lam, dl3)))
-            if log is not None:
-                log.append(("corr", it, a0_, a3_))
-            if a3_ >= a0_ + corr_accept * corr_delta:
-                dz, dp, daux, dl, Gd, ds, rtil2 = dz3, dp3, daux3, dl3, Gd3, ds3, rt3
-            else:
-                break
-        a = min(1.0, step_frac * min(max_step(s, ds), max_step(lam, dl)))
-        if nbhd > 0.0:
-            for _ in range(40):
-                prods = np.concatenate([((s[g] + a * ds[g]) * (lam[g] + a * dl[g])).ravel() for g in LPG])
-                tot_ = prods.sum() + (sum(((s["soc"] + a * ds["soc"]) * (lam["soc"] + a * dl["soc"])).sum() for _q in [0]) if nsoc else 0.0)
-                if prods.min() >= nbhd * tot_ / deg:
-                    break
-                a *= 0.9
-        for _ in range(60):
-            sn = {g: s[g] + a * ds[g] for g in h}; ln = {g: lam[g] + a * dl[g] for g in h}
-            if min_margin(sn) > 0 and min_margin(ln) > 0:
-                break
-            a *= 0.8
-        if debug:
-            ms_s = max_step(s, ds); ms_l = max_step(lam, dl)
-            print("   a_aff %.3e sigma %.3e a %.3e maxstep s %.3e lam %.3e newton res %.2e" % (
-                a_aff, sigma, a, ms_s, ms_l, 0.0))
-            # which group limits
-            for g in h:
-                vv = {gg: (s[gg] if gg == g else np.ones_like(s[gg]) * 1e30) for gg in h}
-            lim = []
-            for g in LPG:
-                neg = ds[g] < 0
-                if neg.any():
-                    lim.append((np.min(-s[g][neg] / ds[g][neg]), g, "s"))
-                neg = dl[g] < 0
-                if neg.any():
-                    lim.append((np.min(-lam[g][neg] / dl[g][neg]), g, "lam"))
-            lim.sort()
-            print("   limiting:", lim[:3])
-        if split_step:
-            a_p = min(1.0, 0.99 * max_step(s, ds)); a_d = min(1.0, 0.99 * max_step(lam, dl))
-            for _ in range(60):
-                sn = {g: s[g] + a_p * ds[g] for g in h}
-                if min_margin(sn) > 0:
-                    break
-                a_p *= 0.8
-            for _ in range(60):
-                ln = {g: lam[g] + a_d * dl[g] for g in h}
-                if min_margin(ln) > 0:
-                    break
-                a_d *= 0.8
-            z = z + a_p * dz; p = p + a_p * dp
-            aux = {k_: aux[k_] + a_p * daux[k_] for k_ in aux}
-            s = sn; lam = ln
-            continue
-        a_last = a
-        if probe is not None:
-            probe(locals())
-        z = z + a * dz; p = p + a * dp
-        aux = {k_: aux[k_] + a * daux[k_] for k_ in aux}
-        s = sn; lam = ln
+        ds = {g: -rz[g] - Gd[g] for g in h}
+        z, p, aux, s, lam = K.take_step(K.max_step(s, ds, lam, dl), z, p, aux, s, lam, dz, dp, daux, ds, dl)
     if status != "OPTIMAL":
         info = best[1]
         # ECOS "reduced tolerances" (feastol_inacc 1e-4, abstol_inacc / reltol_inacc 5e-5) -> ALMOST_OPTIMAL
@@ -907,17 +737,6 @@ def solve(P, max_iter=100, feastol=1e-8, abstol=1e-8, reltol=1e-8, verbose=False
         info["iters_total"] = it
     info["status"] = status
     return info
-
-
-def _rows_eval_lin(P, z, p):
-    """linear part of the row functions (no constants)."""
-    a = _rows_eval(P, z, p)
-    c = _rows_eval(P, np.zeros_like(z), np.zeros_like(p))
-    return {g: a[g] - c[g] for g in a}
-
-
-def G_apply_dir(P, dz, dp, daux, G_apply, N, nz, npp):
-    return G_apply(dz, dp, daux)
 
 
 def unpack(P, z, p):

@@ -7,7 +7,7 @@
 //   comm_api.hip     RCCL communicator and scp_ptr_run_sharded
 //
 // scp_problem groups its state by the unit that WRITES it; every unit may read every group.  The units are built with
-// different -D flags (SCP_K3_MFMA, SCP_IPM_PROF*): nothing in this file may depend on one.
+// different -D flags (SCP_IPM_PROF*, CONIC_PROF): nothing in this file may depend on one.
 #pragma once
 #include <hip/hip_runtime.h>
 

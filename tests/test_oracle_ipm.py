@@ -1,9 +1,13 @@
 """Pins for the oracle's conic solver (oracle/ipm.py, restating the ECOS algorithm class) by
 solver-independent certificates: agreement with scipy's HiGHS on LPs, closed-form SOCP / QP optima,
 KKT residuals and duality gap of a PTR subproblem."""
+import os
+
 import numpy as np
 import scipy.sparse as sp
 from scipy.optimize import linprog
+
+from tests.golden.make_ipm_struct_pins import CASES, PIN_RTOL, pins, rel_diff, solved
 
 
 def test_lp_matches_highs():
@@ -54,22 +58,30 @@ def test_ptr_subproblem_certificate():
 
 def test_reduced_structured_solver_equals_literal_program():
     """The reduction used by the HIP solver (epigraph / virtual-control variables eliminated, oracle/ipm_struct.py)
-    has the same optimum as the reference's literal conic program."""
-    from oracle import ipm_struct, ptr_ref
-    from oracle.models import MODELS
-    for model, N in (("quadrotor", 10), ("double_integrator", 12)):
-        mdl = MODELS[model]()
-        pars = ptr_ref.PTRParameters(N, 8, 3, 1e3, 0.1, 0, 0, 1e-3)
-        scale = ptr_ref.Scaling(*mdl.bbox())
-        pp = mdl.nominal_pp()
-        x, u, p = mdl.guess(N, pp)
-        ref = ptr_ref.discretize(mdl, pars, scale, x, u, p)
-        for it in range(2):
-            sub = ptr_ref.solve_subproblem(mdl, pars, scale, ref, pp)
-            P = ipm_struct.build_stage_problem(mdl, pars, scale, ref, pp)
-            r = ipm_struct.solve(P)
+    has the same optimum as the reference's literal conic program.  Rocket landing has two second-order cones per node, hinge
+    rows and a free parameter together."""
+    from oracle import ipm_struct
+    for model, N in (("quadrotor", 10), ("double_integrator", 12), ("rocket_landing", 10)):
+        for P, sub, scale, r in solved(model, N):
             assert r["status"] in ("OPTIMAL", "ALMOST_OPTIMAL")
             assert abs(r["pcost"] + P.cost_const - sub["J_aug"]) <= 2e-6 * max(1.0, abs(sub["J_aug"]))
             xa, ua, pa = ipm_struct.unpack(P, r["z"], r["p"])
             assert np.abs((ua - sub["u"]) / scale.Su).max() < 2e-5
-            ref = ptr_ref.discretize(mdl, pars, scale, sub["x"], sub["u"], sub["p"])
+
+
+def test_structured_solver_reproduces_its_pins():
+    """oracle/ipm_struct.py::solve computes what it computed when tests/golden/ipm_struct_pins.npz was recorded
+    (tests/golden/make_ipm_struct_pins.py: the file before it was reduced to the shipped algorithm).  Statuses and iteration counts
+    must be equal; arrays and scalars agree to PIN_RTOL of the array's largest magnitude, 100 x the largest difference measured
+    between two machines' recordings of the same file.  Any of the removed switches moves the iterates by many orders more."""
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "ipm_struct_pins.npz"))
+    for model, N in CASES:
+        for it, (P, sub, scale, r) in enumerate(solved(model, N)):
+            for key, got in pins(model, it, r).items():
+                want = g[key]
+                if got.dtype.kind == "i":
+                    assert got == want, key
+                else:
+                    d = rel_diff(got, want)
+                    print("%-32s %.2e" % (key, d))
+                    assert got.shape == want.shape and d <= PIN_RTOL, key
