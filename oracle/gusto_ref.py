@@ -245,11 +245,15 @@ def model_error(mdl, pars, ref, x, u, p):
     t = linrange(0.0, 1.0, pars.N)
     df, dn = np.zeros(pars.N), np.zeros(pars.N)
     npd = getattr(mdl, "np_dyn", mdl.np)        # parameters the dynamics see (ptr_ref.discretize)
+    if hasattr(mdl, "f"):                       # numpy-dynamics model (oracle/models.py): its own closures, handed the whole p
+        ev = lambda tk, k, xk, uk, pk: (mdl.f(tk, k, xk, uk, pk), mdl.A(tk, k, xk, uk, pk), mdl.B(tk, k, xk, uk, pk), mdl.F(tk, k, xk, uk, pk))
+    else:
+        ev = lambda tk, k, xk, uk, pk: orc.model_eval(mdl.name, mdl.par(), tk, k, xk, uk, pk[:npd])
     for k in range(pars.N):
-        f, A, B, F = orc.model_eval(mdl.name, mdl.par(), t[k], k + 1, ref.xd[k], ref.ud[k], ref.p[:npd])
+        f, A, B, F = ev(t[k], k + 1, ref.xd[k], ref.ud[k], ref.p)
         r = f - A @ ref.xd[k] - B @ ref.ud[k] - (F @ ref.p[:npd] if npd else 0.0)
         f_lin = A @ x[k] + B @ u[k] + (F @ p[:npd] if npd else 0.0) + r
-        f_nl = orc.model_eval(mdl.name, mdl.par(), t[k], k + 1, x[k], u[k], p[:npd])[0]
+        f_nl = ev(t[k], k + 1, x[k], u[k], p)[0]
         df[k] = np.linalg.norm(f_nl - f_lin); dn[k] = np.linalg.norm(f_lin)
     return float(ptr_ref._trapz(df, t)), float(ptr_ref._trapz(dn, t))
 

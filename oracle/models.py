@@ -1,7 +1,12 @@
 """CPU ORACLE (test infrastructure; parity status "parity unpinned", see oracle/__init__.py): numpy restatement of the example problem
-definitions -- everything a `TrajectoryProblem` carries besides the dynamics
-(which live in oracle/scp_oracle.c): non-convex constraints s/C/D/G, convex
+definitions -- everything a `TrajectoryProblem` carries: non-convex constraints s/C/D/G, convex
 sets X/U as cone rows, boundary conditions, cost, initial guess, scaling boxes.
+
+Two kinds of model, told apart by whether the class defines `f`:
+  C-dynamics model      the dynamics live in oracle/scp_oracle.c under `mdl.name`;
+  numpy-dynamics model  the class carries f / A / B / F(t, k, x, u, p) itself (k < 0 selects the impulse response) and needs
+                        nothing in C (Oscillator).
+oracle/ptr_ref.py::discretize is where the two part ways.
 
 Conventions: math layout (matrices are [rows, cols]); a cone constraint is a
 tuple (kind, Mx_or_Mu, Mp, m0) meaning  z = M*x(or u) + Mp*p + m0  with
@@ -9,7 +14,10 @@ tuple (kind, Mx_or_Mu, Mp, m0) meaning  z = M*x(or u) + Mp*p + m0  with
 (src/parser/cone.jl:36-47).  `pp` is the per-problem data vector (Monte-Carlo
 initial/terminal conditions).
 """
-import numpy as _np
+import math
+
+import numpy as np
+import numpy as _np      # inside a class body `np` is the parameter count
 
 from .oracle import default_params  # noqa: F401  (re-export)
 
@@ -646,4 +654,160 @@ class Freeflyer:
         return _np.zeros((13, self.np))
 
 
-MODELS = {m.name: m for m in (DoubleIntegrator, Quadrotor, RocketLanding, Starship, Freeflyer)}
+def smooth_or(pred, grad, kappa, match, normalize):
+    """or(predicates, gradient; kappa, match, normalize) -> (OR, dOR), helper.jl:775-807, through indicator (:724-749), sigmoid
+    (:672-701) and logsumexp (:623-651), in the reference's order of operations."""
+    f = np.asarray(pred, float) / normalize
+    g = np.asarray(grad, float) / normalize
+    mt = np.atleast_1d(np.asarray(match, float) / normalize)
+
+    def logsumexp(v, dv):
+        a = np.max(kappa * v)
+        e = np.exp(kappa * v - a)
+        E = e.sum()
+        return (a + math.log(E)) / kappa, None if dv is None else float((dv * (e / E)).sum())
+
+    def sigmoid(v, dv):
+        with np.errstate(over="ignore", divide="ignore"):
+            L, dL = logsumexp(v, dv)
+            sig = 1.0 - 1.0 / (1.0 + np.exp(kappa * L))
+            if dv is None:
+                return sig, None
+            c = np.exp(kappa * L + 2.0 * np.log(1.0 - sig))
+            return sig, kappa * c * dL
+    offset, _ = sigmoid(mt, None)
+    sig, dsig = sigmoid(f, g)
+    return float(sig + (1.0 - offset)), float(dsig)
+
+
+class Oscillator:
+    """test/examples/oscillator/{parameters,definition}.jl in the interface of oracle/models.py; N fixes np = N."""
+    name = "oscillator"
+    nx, nu, ns, nic, ntc = 2, 4, 2, 2, 0
+    np_dyn = 0
+    zeta, w0, a_db, a_max = 0.5, 1.0, 0.05, 0.3                        # parameters.jl:81-85
+    tf, alpha, gamma, r_nrml = 10.0, 0.06, 1e-1, 1.0                   # :102-108 (r_nrml = traj.r0)
+
+    def __init__(self, N, kappa1=1.0):
+        self.N, self.np, self.kappa1 = int(N), int(N), float(kappa1)
+
+    def par(self):
+        return np.array([self.zeta, self.w0, self.a_db, self.a_max, self.tf, self.kappa1, self.alpha, self.gamma, self.r_nrml])
+
+    def nominal_pp(self):
+        return np.array([1.0, 0.0])
+
+    def bbox(self):      # set_scale!, definition.jl:47-69, from the nominal r0 and v0 = 0
+        a = self.a_max
+        return (np.array([[-self.r_nrml, self.r_nrml], [0.0, 0.0]]), np.array([[-a, a], [-a, a], [0.0, a], [0.0, 2 * a]]),
+                np.tile([[0.0, self.r_nrml]], (self.np, 1)))
+
+    # -- dynamics (definition.jl:161-236); k < 0: the impulse response
+    def Amat(self):
+        return self.tf * np.array([[0.0, 1.0], [-self.w0 ** 2, -2.0 * self.zeta * self.w0]])
+
+    def f(self, t, k, x, u, p):
+        if k < 0:
+            return np.array([0.0, u[0]])
+        return self.tf * np.array([x[1], u[0] - self.w0 ** 2 * x[0] - 2.0 * self.zeta * self.w0 * x[1]])
+
+    def A(self, t, k, x, u, p):
+        return self.Amat()
+
+    def B(self, t, k, x, u, p):
+        B = np.zeros((2, 4)); B[1, 0] = 1.0
+        return B if k < 0 else self.tf * B
+
+    def F(self, t, k, x, u, p):
+        return np.zeros((2, 0))
+
+    def guess(self, N, pp):      # definition.jl:71-114
+        A = self.Amat()
+        tg = linrange(0.0, 1.0, 1000)
+        X = np.zeros((1000, 2)); X[0] = np.asarray(pp, float)[:2]
+        for i in range(999):     # rk4_core_step, helper.jl:411-424
+            h, x = tg[i + 1] - tg[i], X[i]
+            k1 = A @ x; k2 = A @ (x + h / 2 * k1); k3 = A @ (x + h / 2 * k2); k4 = A @ (x + h * k3)
+            X[i + 1] = x + h / 6 * (k1 + 2 * k2 + 2 * k3 + k4)
+        x = np.zeros((N, 2))
+        for k, tau in enumerate(linrange(0.0, 1.0, N)):      # linterp with get_interval, helper.jl:84-118
+            i = max(int((tau > tg).sum()), 1) - 1
+            c = (tg[i + 1] - tau) / (tg[i + 1] - tg[i])
+            x[k] = c * X[i] + (1.0 - c) * X[i + 1]
+        return x, np.zeros((N, 4)), np.abs(x[:, 0]).copy()
+
+    # -- cost (definition.jl:116-142): Gamma = l1r_k / r_nrml + alpha l1aa / a_max + gamma l1adiff / a_max.  The oracle's cost
+    # form has no per-node running term; tp of length N with the trapezoid weights expresses the same sum
+    def cost_terms(self):
+        w = ptr_ref._trapz_weights(linrange(0.0, 1.0, self.N))
+        return dict(Qu=np.zeros(4), lu=np.array([0.0, 0.0, self.alpha / self.a_max, self.gamma / self.a_max]), lx=np.zeros(2),
+                    tx=np.zeros(2), tp=w / self.r_nrml, Qp=np.zeros(self.np))
+
+    # -- convex sets (definition.jl:238-368)
+    def X(self, t, k):
+        rows = []
+        for sg in (1.0, -1.0):
+            Mp = np.zeros((1, self.np)); Mp[0, k - 1] = -1.0
+            rows.append(("NONPOS", np.array([[sg, 0.0]]), Mp, np.zeros(1)))
+        return rows
+
+    def U(self, t, k):
+        a, Z = self.a_max, np.zeros((1, self.np))
+        rows = [("NONPOS", np.array([[1.0, 0, 0, 0]]), Z, np.array([-a])), ("NONPOS", np.array([[-1.0, 0, 0, 0]]), Z, np.array([-a])),
+                ("NONPOS", np.array([[0, 1.0, 0, 0]]), Z, np.array([-a])), ("NONPOS", np.array([[0, -1.0, 0, 0]]), Z, np.array([-a]))]
+        for sg in (1.0, -1.0):
+            rows.append(("NONPOS", np.array([[sg, 0, -1.0, 0]]), Z, np.zeros(1)))
+        for sg in (1.0, -1.0):
+            rows.append(("NONPOS", np.array([[sg, -sg, 0, -1.0]]), Z, np.zeros(1)))
+        return rows
+
+    # -- non-convex deadband (definition.jl:370-444)
+    def _or(self, ar):
+        n = self.a_max - self.a_db
+        return smooth_or([ar - self.a_db, -self.a_db - ar], [1.0, -1.0], self.kappa1, n, n)
+
+    def s(self, t, k, x, u, p):
+        OR, _ = self._or(u[1])
+        return np.array([u[0] - OR * u[1], OR * u[1] - u[0]])
+
+    def C(self, t, k, x, u, p):
+        return np.zeros((2, 2))
+
+    def D(self, t, k, x, u, p):
+        OR, dOR = self._or(u[1])
+        d = dOR * u[1] + OR
+        return np.array([[1.0, -d, 0, 0], [-1.0, d, 0, 0]])
+
+    def G(self, t, k, x, u, p):
+        return np.zeros((2, self.np))
+
+    # -- boundary conditions (definition.jl:446-473): initial condition only
+    def gic(self, x, p, pp):
+        return x - np.asarray(pp, float)[:2]
+
+    def H0(self, x, p, pp):
+        return np.eye(2)
+
+    def K0(self, x, p, pp):
+        return np.zeros((2, self.np))
+
+    def gtc(self, x, p, pp):
+        return np.zeros(0)
+
+    def Hf(self, x, p, pp):
+        return np.zeros((0, 2))
+
+    def Kf(self, x, p, pp):
+        return np.zeros((0, self.np))
+
+
+# the five Monte-Carlo instances pp = (r0, v0) of the fixture tests/golden/oscillator_outcomes_n12.npz
+INSTANCES = np.array([[0.15, 0.0], [0.4, 0.0], [1.0, 0.0], [0.7, 0.2], [-0.5, -0.1]])
+LOG99 = math.log(1.0 / 1e-2 - 1.0)
+KAPPA3 = [LOG99, LOG99 * 1e4, LOG99 * 1e8]            # Homotopy(1e-8) at x = 0, 1/2, 1 (src/utils/homotopy.jl:66-73)
+KAPPA10 = [LOG99 / (1e-8 ** x) for x in linrange(0.0, 1.0, 10)]     # oscillator/tests.jl:60-62
+
+
+MODELS = {m.name: m for m in (DoubleIntegrator, Quadrotor, RocketLanding, Starship, Freeflyer, Oscillator)}      # Starship, Oscillator take N
+
+from . import ptr_ref  # noqa: E402  (Oscillator.cost_terms; last, because ptr_ref imports the names above)

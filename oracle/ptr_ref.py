@@ -13,7 +13,9 @@ Follows, line by line:
   solve/extract    src/solvers/scp.jl:942-950, ptr.jl:399-432
   stopping         src/solvers/ptr.jl:908-932, scp.jl:909-931
   loop             src/solvers/ptr.jl:448-532
-The conic solve itself is oracle/ipm.py (restating the ECOS algorithm class).
+The conic solve itself is oracle/ipm.py (restating the ECOS algorithm class).  `discretize` below is the one place that
+decides how a model is discretised: a numpy-dynamics model (oracle/models.py) by oracle/discretize_ref.py, every other by the
+C oracle under its name.  `homotopy` is the warm-started oscillator homotopy of oscillator/tests.jl:60-77 on the same loop.
 PARITY STATUS: "parity unpinned" -- the reference ships no golden vectors for this path and cannot be run here; this
 restatement is pinned on mathematics (tests/test_oracle_*.py) and on the fixtures generated from it (tests/golden/).
 NormInf / NormOne cones are lowered to R+ rows the way MathOptInterface's
@@ -25,9 +27,9 @@ import time
 import numpy as np
 import scipy.sparse as sp
 
-from . import ipm
+from . import discretize_ref, ipm
 from . import oracle as orc
-from .models import MODELS, linrange
+from .models import MODELS, Oscillator, linrange
 
 
 class _Prog:
@@ -183,22 +185,29 @@ def lower_linf(kind, M, Mp, m0):
     return "NONPOS", Dm @ M, Dm @ Mp, Dm @ m0
 
 
-def discretize(mdl, pars, scale, x, u, p):
+def discretize(mdl, pars, scale, x, u, p, method="foh"):
     """SubproblemSolution(x,u,p,iter,pbm) -> discretize!  (ptr.jl:313-383)."""
+    s = Sol()
+    s.xd, s.ud, s.p = x, u, p
+    s.J_aug = np.nan  # ptr.jl:350
+    if hasattr(mdl, "f"):      # numpy-dynamics model (oracle/models.py)
+        o = discretize_ref.discretize_arrays(mdl, pars.N, pars.Nsub, x, u, p, 1.0 / scale.Sx, pars.feas_tol, method)
+        s.A, s.Bm, s.Bp, s.r, s.E = o["A"], o["Bm"], o["Bp"], o["r"], o["E"]
+        s.F = np.zeros((pars.N - 1, mdl.nx, mdl.np))
+        s.F[:, :, :o["F"].shape[2]] = o["F"]
+        s.defect, s.feas = o["defect"], bool(o["feas"])
+        return s
     # np_dyn: leading parameters that enter the dynamics (free-flyer: the time dilation; its room-SDF slacks delta only
     # appear in constraints, so the columns of F beyond np_dyn are structurally zero, freeflyer/definition.jl:273-281)
     npd = getattr(mdl, "np_dyn", mdl.np)
     out = orc.discretize(mdl.name, mdl.par(), pars.N, pars.Nsub, x[None], u[None], p[None, :npd], 1.0 / scale.Sx,
-                         pars.feas_tol)
-    s = Sol()
-    s.xd, s.ud, s.p = x, u, p
+                         pars.feas_tol, method=method)
     s.A = np.swapaxes(out["A"][0], 1, 2); s.Bm = np.swapaxes(out["Bm"][0], 1, 2)
     s.Bp = np.swapaxes(out["Bp"][0], 1, 2); s.F = np.swapaxes(out["F"][0], 1, 2)
     if npd != mdl.np:
         s.F = np.concatenate([s.F, np.zeros(s.F.shape[:2] + (mdl.np - npd,))], axis=2)
     s.r = out["r"][0]; s.E = np.swapaxes(out["E"][0], 1, 2)
     s.defect = out["defect"][0]; s.feas = bool(out["feas"][0])
-    s.J_aug = np.nan  # ptr.jl:350
     return s
 
 
@@ -445,3 +454,23 @@ def ptr_solve(model, pars, pp=None, guess=None, ipm_opts=None, verbose=False):
         if k > pars.iter_max:
             break
     return status, hist
+
+
+def reference_pars(N, Nsub=10, iter_max=10):
+    """PTR.Parameters of oscillator/tests.jl:24-57"""
+    return PTRParameters(N, Nsub, iter_max, 1e2, 1e-3, -np.inf, 1e-3 / 100, 5e-3)
+
+
+def homotopy(N, Nsub, kappas, pp, iter_max=10):
+    """oscillator/tests.jl:60-77: one solve per kappa1, each warm-started with the previous SOLUTION.  Returns a list of
+    (status, history) per stage."""
+    mdl = Oscillator(N)
+    pars = reference_pars(N, Nsub, iter_max)
+    out, warm = [], None
+    for kap in kappas:
+        mdl.kappa1 = float(kap)
+        st, hist = ptr_solve(mdl, pars, np.asarray(pp, float), guess=warm)
+        last = hist[-1]["sol"]
+        warm = (last.xd, last.ud, last.p)
+        out.append((st, hist))
+    return out

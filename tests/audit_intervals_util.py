@@ -15,6 +15,7 @@ viol_tol chosen by audit_util.choose_viol_tol over the per-sample worst values (
 import numpy as np
 
 import audit_util as au
+from oracle.discretize_ref import _rk4
 from oracle.models import linrange
 
 W, WI = 16, 16      # SCP_AUDIT_WIDTH, SCP_AUDIT_INTERVAL_WIDTH
@@ -32,32 +33,6 @@ def sub_of(N, res):
 def res_values(N):
     """sub = 2 (one step), sub = 3, and sub = 7 through the ceiling"""
     return (2, 3 * (N - 1), 6 * (N - 1) + 1)
-
-
-def _sample(name, mdl, ct, t, k, x, u, p):
-    """(values of the three sampled families, their term scales, parameter-only maximum, Gamma) at one sample"""
-    fam, scale, par_max = np.full(3, -np.inf), np.ones(3), -np.inf
-    s = mdl.s(t, k, x, u, p)
-    if len(s):
-        i = int(np.argmax(s))
-        fam[0], scale[0] = s[i], max(1.0, au._s_terms(name, mdl, x, u, p)[i])
-    for v, rows in ((x, mdl.X(t, k)), (u, mdl.U(t, k))):
-        for kind, M, Mp, m0 in rows:
-            terms = [np.abs(M * v[None, :]), np.abs(Mp * p[None, :]) if p.size else np.zeros((M.shape[0], 0)), np.abs(m0)[:, None]]
-            tmax = np.concatenate(terms, axis=1).max(axis=1)
-            z = M @ v + (Mp @ p if p.size else 0.0) + m0
-            if kind == "NONPOS":
-                for i in range(M.shape[0]):
-                    if not M[i].any() and Mp[i].any():
-                        par_max = max(par_max, z[i])
-                    elif z[i] > fam[1]:
-                        fam[1], scale[1] = z[i], max(1.0, tmax[i])
-            else:
-                assert kind == "SOC" and M.shape[0] == 4
-                q = np.linalg.norm(z[1:]) - z[0]
-                if q > fam[2]:
-                    fam[2], scale[2] = q, max(1.0, tmax.max())
-    return fam, scale, par_max, ct["Qu"] @ (u * u) + ct["lu"] @ u + ct["lx"] @ x
 
 
 class IntervalReference:
@@ -81,13 +56,11 @@ class IntervalReference:
                 def f(t, x):
                     c = (t1 - min(max(t, t0), t1)) / (t1 - t0)
                     return orc.model_eval(name, par, t, N, x, c * ud[k] + (1.0 - c) * ud[k + 1], p)[0]
-                x = xd[k].copy()
-                xc[k, 0] = x
-                for j in range(1, sub):
-                    t, h = self.tg[k, j - 1], self.tg[k, j] - self.tg[k, j - 1]
-                    k1 = f(t, x); k2 = f(t + h / 2, x + h / 2 * k1); k3 = f(t + h / 2, x + h / 2 * k2); k4 = f(t + h, x + h * k3)
-                    x = x + h / 6 * (k1 + 2 * k2 + 2 * k3 + k4)
+                xc[k, 0] = xd[k]
+
+                def keep(j, x):
                     xc[k, j] = x
+                _rk4(f, xd[k].copy(), self.tg[k], on_step=keep)
         self.xc = xc
         ct = mdl.cost_terms()
         fam, scale = np.full((N - 1, sub, 3), -np.inf), np.ones((N - 1, sub, 3))
@@ -101,7 +74,7 @@ class IntervalReference:
                     c = (td[k + 1] - t) / (td[k + 1] - td[k])
                     u = c * ud[k] + (1.0 - c) * ud[k + 1]
                 node = k + 2 if j == sub - 1 else k + 1          # 1-based node index handed to the model functions
-                fam[k, j], scale[k, j], pm, gam[k, j] = _sample(name, mdl, ct, t, node, xc[k, j], u, p)
+                fam[k, j], scale[k, j], pm, gam[k, j] = au._sample(name, mdl, ct, t, node, xc[k, j], u, p)
                 par_max = max(par_max, pm)
         self.fam, self.scale = fam, scale
         self.worst = fam.max(axis=2).ravel()

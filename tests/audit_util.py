@@ -25,7 +25,7 @@ RTOL = 1e-9
 
 
 def oracle_model(name, N):
-    return MODELS[name](N) if name == "starship" else MODELS[name]()
+    return MODELS[name](N) if name in ("starship", "oscillator") else MODELS[name]()
 
 
 def state_scale(mdl):
@@ -79,6 +79,32 @@ def _s_terms(name, mdl, x, u, p):
     return [a, a, b, b, max(np.linalg.norm(x[0:2]) * math.cos(mdl.gamma_gs), abs(x[1]))] + pw + pw + [th, th]
 
 
+def _sample(name, mdl, ct, t, k, x, u, p):
+    """(values of the three sampled families, their term scales, parameter-only maximum, Gamma) at one sample"""
+    fam, scale, par_max = np.full(3, -np.inf), np.ones(3), -np.inf
+    s = mdl.s(t, k, x, u, p)
+    if len(s):
+        i = int(np.argmax(s))
+        fam[0], scale[0] = s[i], max(1.0, _s_terms(name, mdl, x, u, p)[i])
+    for v, rows in ((x, mdl.X(t, k)), (u, mdl.U(t, k))):
+        for kind, M, Mp, m0 in rows:
+            terms = [np.abs(M * v[None, :]), np.abs(Mp * p[None, :]) if p.size else np.zeros((M.shape[0], 0)), np.abs(m0)[:, None]]
+            tmax = np.concatenate(terms, axis=1).max(axis=1)
+            z = M @ v + (Mp @ p if p.size else 0.0) + m0
+            if kind == "NONPOS":
+                for i in range(M.shape[0]):
+                    if not M[i].any() and Mp[i].any():
+                        par_max = max(par_max, z[i])
+                    elif z[i] > fam[1]:
+                        fam[1], scale[1] = z[i], max(1.0, tmax[i])
+            else:
+                assert kind == "SOC" and M.shape[0] == 4
+                q = np.linalg.norm(z[1:]) - z[0]
+                if q > fam[2]:
+                    fam[2], scale[2] = q, max(1.0, tmax.max())
+    return fam, scale, par_max, ct["Qu"] @ (u * u) + ct["lu"] @ u + ct["lx"] @ x
+
+
 class Reference:
     """the audit of ONE problem on the CPU: per-sample values of the three sampled families, their term scales, and the record"""
 
@@ -93,30 +119,10 @@ class Reference:
         par_max, gam = -np.inf, np.zeros(res)
         ct = mdl.cost_terms()
         for j in range(res):
-            t, x = tc[j], xc[j]
+            t = tc[j]
             k = max(int(np.sum(tgrid <= t)), 1)   # 1-based index of the last grid node <= t
-            u = _input(tgrid, ud, t)
-            s = mdl.s(t, k, x, u, p)
-            if len(s):
-                i = int(np.argmax(s))
-                fam[j, 0], scale[j, 0] = s[i], max(1.0, _s_terms(name, mdl, x, u, p)[i])
-            for v, rows in ((x, mdl.X(t, k)), (u, mdl.U(t, k))):
-                for kind, M, Mp, m0 in rows:
-                    terms = [np.abs(M * v[None, :]), np.abs(Mp * p[None, :]) if p.size else np.zeros((M.shape[0], 0)), np.abs(m0)[:, None]]
-                    tmax = np.concatenate(terms, axis=1).max(axis=1)
-                    z = M @ v + (Mp @ p if p.size else 0.0) + m0
-                    if kind == "NONPOS":
-                        for i in range(M.shape[0]):
-                            if not M[i].any() and Mp[i].any():      # parameter-only: evaluated once (the same at every sample)
-                                par_max = max(par_max, z[i])
-                            elif z[i] > fam[j, 1]:
-                                fam[j, 1], scale[j, 1] = z[i], max(1.0, tmax[i])
-                    else:
-                        assert kind == "SOC" and M.shape[0] == 4
-                        q = np.linalg.norm(z[1:]) - z[0]
-                        if q > fam[j, 2]:
-                            fam[j, 2], scale[j, 2] = q, max(1.0, tmax.max())
-            gam[j] = ct["Qu"] @ (u * u) + ct["lu"] @ u + ct["lx"] @ x
+            fam[j], scale[j], pm, gam[j] = _sample(name, mdl, ct, t, k, xc[j], _input(tgrid, ud, t), p)
+            par_max = max(par_max, pm)            # parameter-only rows: the same at every sample
         self.fam, self.scale = fam, scale
         rec = np.zeros(W)
         for f in range(3):

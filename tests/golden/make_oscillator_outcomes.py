@@ -1,5 +1,5 @@
 """Generates tests/golden/oscillator_outcomes_n12.npz: the oracle's PTR homotopy of the oscillator with actuator deadband
-(tests/oscillator_util.py: the numpy model + discretisation around the unchanged oracle/ptr_ref.py).
+(oracle/ptr_ref.py::homotopy: the numpy-dynamics model of oracle/models.py through oracle/discretize_ref.py).
 
   * five Monte-Carlo instances pp = (r0, v0) at N = 12, Nsub = 10, three stages kappa1 = Homotopy(1e-8)(0, 1/2, 1), reference
     parameters of oscillator/tests.jl:24-57.  Per instance and stage: the reference trajectory of the stage's FIRST subproblem
@@ -20,27 +20,27 @@ for d in (ROOT, os.path.dirname(HERE)):
     if d not in sys.path:
         sys.path.insert(0, d)
 
-import oscillator_util as ou  # noqa: E402
+from oracle import models, ptr_ref  # noqa: E402
 
 OUT = os.path.join(HERE, "oscillator_outcomes_n12.npz")
 N12, NSUB = 12, 10
 
 
 def compute():
-    B, S = len(ou.INSTANCES), len(ou.KAPPA3)
-    d = dict(pp=ou.INSTANCES.copy(), kappa=np.array(ou.KAPPA3), N=np.array(N12), Nsub=np.array(NSUB),
+    B, S = len(models.INSTANCES), len(models.KAPPA3)
+    d = dict(pp=models.INSTANCES.copy(), kappa=np.array(models.KAPPA3), N=np.array(N12), Nsub=np.array(NSUB),
              ref_x=np.zeros((B, S, N12, 2)), ref_u=np.zeros((B, S, N12, 4)), ref_p=np.zeros((B, S, N12)), J_aug_first=np.zeros((B, S)),
              status=np.zeros((B, S), np.int32), iterations=np.zeros((B, S), np.int32), J=np.zeros((B, S)))
-    for b, pp in enumerate(ou.INSTANCES):
-        for s, (st, hist) in enumerate(ou.homotopy(N12, NSUB, ou.KAPPA3, pp)):
+    for b, pp in enumerate(models.INSTANCES):
+        for s, (st, hist) in enumerate(ptr_ref.homotopy(N12, NSUB, models.KAPPA3, pp)):
             first = hist[0]
             d["ref_x"][b, s], d["ref_u"][b, s], d["ref_p"][b, s] = first["ref"].xd, first["ref"].ud, first["ref"].p
             d["J_aug_first"][b, s] = first["sub"]["J_aug"]
             d["status"][b, s] = 0 if st == "SCP_SOLVED" else 1
             d["iterations"][b, s] = len(hist)
             d["J"][b, s] = hist[-1]["sub"]["J"]
-    run = ou.homotopy(30, NSUB, ou.KAPPA10, ou.INSTANCES[2])
-    d["kappa30"] = np.array(ou.KAPPA10)
+    run = ptr_ref.homotopy(30, NSUB, models.KAPPA10, models.INSTANCES[2])
+    d["kappa30"] = np.array(models.KAPPA10)
     d["status30"] = np.array([0 if st == "SCP_SOLVED" else 1 for st, _ in run], np.int32)
     d["iterations30"] = np.array([len(h) for _, h in run], np.int32)
     d["J30"] = np.array([h[-1]["sub"]["J"] for _, h in run])

@@ -1,5 +1,5 @@
 """Oscillator with actuator deadband (test/examples/oscillator), CPU side: the compiled model's closures evaluated on the host
-through the C ABI against the numpy restatement of tests/oscillator_util.py, the restatement itself against the C oracle on a
+through the C ABI against the numpy restatement of oracle/models.py, the restatement itself against the C oracle on a
 model both know, the node-parameter running cost, the PTR template with no terminal condition against the oracle's literal
 program, the mutable-constant mask, the homotopy schedule and the committed fixture."""
 import ctypes
@@ -9,8 +9,7 @@ import os
 import numpy as np
 import pytest
 
-import oscillator_util as ou
-from oracle import conic_host, ptr_ref
+from oracle import conic_host, discretize_ref, models, ptr_ref
 from oracle.models import MODELS
 from template_util import make_src, template_matrices
 
@@ -30,7 +29,7 @@ def test_model_query(pkg):
     assert (info.ns, info.nic, info.ntc, info.nsoc, info.ng, info.nl) == (2, 2, 0, 0, 0, 10)
     assert (info.npp, info.npar, info.structured, info.has_subproblem, info.s_input_free, info.linf_groups) == (2, 9, 0, 1, 0, 0)
     m = pkg.REGISTRY["oscillator"]()
-    np.testing.assert_array_equal(m.par(), ou.Oscillator(5).par())      # defaults of parameters.jl:69-115, kappa1 = r_nrml = 1
+    np.testing.assert_array_equal(m.par(), models.Oscillator(5).par())      # defaults of parameters.jl:69-115, kappa1 = r_nrml = 1
     np.testing.assert_array_equal(m.nominal_pp(), [1.0, 0.0])
     assert pkg.TrajectoryProblem("oscillator", kappa1=3.0).mdl.par()[5] == 3.0
 
@@ -58,7 +57,7 @@ def test_numpy_discretisation_agrees_with_the_c_oracle_on_the_double_integrator(
     rng = np.random.default_rng(3)
     x, u, p = rng.standard_normal((N, 2)), rng.standard_normal((N, 1)), np.zeros(0)
     iSx = np.array([0.5, 2.0])
-    mine = ou.discretize_arrays(DI(), N, Nsub, x, u, p, iSx, 1e-3, method)
+    mine = discretize_ref.discretize_arrays(DI(), N, Nsub, x, u, p, iSx, 1e-3, method)
     o = orc.discretize("double_integrator", np.array([g, T]), N, Nsub, x[None], u[None], p[None], iSx, 1e-3, method=method)
     for nm in ("A", "Bm", "Bp", "E"):
         ref = np.swapaxes(o[nm][0], 1, 2)
@@ -90,7 +89,7 @@ def _points(mdl, N):
 @pytest.mark.parametrize("kappa", KAPPAS)
 def test_compiled_closures_against_the_restatement(pkg, kappa):
     N = 7
-    mdl = ou.Oscillator(N, kappa)
+    mdl = models.Oscillator(N, kappa)
     par = mdl.par()
     for k, x, u, p in _points(mdl, N):
         k = int(k)
@@ -108,7 +107,7 @@ def test_compiled_closures_against_the_restatement(pkg, kappa):
 @pytest.mark.parametrize("kappa", [4.595, 35.6])
 def test_jacobian_of_the_deadband_against_central_differences(pkg, kappa):
     N = 7
-    mdl = ou.Oscillator(N, kappa)
+    mdl = models.Oscillator(N, kappa)
     par, h = mdl.par(), 1e-6
     for k, x, u, p in _points(mdl, N):
         D = _eval(pkg, par, N, int(k), x, u, p)["D"]
@@ -122,7 +121,7 @@ def test_rows_and_cost_against_the_restatement(pkg):
     N = 5
     pm = pkg.REGISTRY["oscillator"]()
     mr = pkg.subproblem.ModelRows(pm, N)
-    mdl = ou.Oscillator(N)
+    mdl = models.Oscillator(N)
     for k in (1, 3, N):
         L, Lp, l, Mm, m = mr.rows(N, k)
         assert Mm.shape[0] == 0 and L.shape == (10, 6) and Lp.shape == (10, N)
@@ -146,20 +145,20 @@ def test_freeflyer_node_cost_terms_are_still_tiled(pkg):
     np.testing.assert_array_equal(ct["Qp"][1:], np.zeros(6 * N))
 
 
-@pytest.mark.parametrize("kappa", [ou.KAPPA3[0], ou.KAPPA3[2]])
+@pytest.mark.parametrize("kappa", [models.KAPPA3[0], models.KAPPA3[2]])
 def test_ptr_template_without_a_terminal_condition_equals_the_oracles_program(pkg, orc, kappa):
     """in the manner of tests/test_template_cpu.py: the product's template (ntc = 0: empty vtc, Pf[1] >= ||[]||_1, zero-row
     sources Hf / Kf / lf; the node parameter in the running cost) about the guess, solved by the host build of the conic solver,
     against the oracle's literal program"""
     N, Nsub = 6, 5
-    mdl = ou.Oscillator(N, kappa)
+    mdl = models.Oscillator(N, kappa)
     pm = pkg.REGISTRY["oscillator"](kappa1=kappa)
     mr = pkg.subproblem.ModelRows(pm)
     scale = ptr_ref.Scaling(*mdl.bbox())
-    pars = ou.reference_pars(N, Nsub)
+    pars = ptr_ref.reference_pars(N, Nsub)
     pp = np.array([0.7, 0.2])
     x, u, p = mdl.guess(N, pp)
-    ref = ou.discretize(mdl, pars, scale, x, u, p)
+    ref = ptr_ref.discretize(mdl, pars, scale, x, u, p)
     o = ptr_ref.solve_subproblem(mdl, pars, scale, ref, pp)
     T = pkg.subproblem.build_ptr(mr, N, scale, pars.wvc, pars.wtr, np.inf)
     assert T.variables["vtc"].size == 0 and T.variables["vic"].size == 2
@@ -189,7 +188,7 @@ def test_mutable_constants(pkg):
 def test_audits_refuse_the_oscillator(pkg):
     L = pkg._lib.lib()
     one = np.ones(64)
-    par = ou.Oscillator(5).par()
+    par = models.Oscillator(5).par()
     assert L.scp_model_audit_host(OSC, _vp(par), 5, _vp(one), _vp(one), _vp(one), _vp(one), _vp(one), 4, 0.0, _vp(one)) == 7
     assert L.scp_model_audit_intervals_host(OSC, _vp(par), 5, 0, _vp(one), _vp(one), _vp(one), _vp(one), _vp(one), 4, 0.0, _vp(one),
                                             _vp(one)) == 7
@@ -201,7 +200,7 @@ def test_homotopy_schedule(pkg):
     assert h(1) == pytest.approx(1e8 * math.log(99.0), rel=1e-14)
     assert h(0.5) == pytest.approx(1e4 * math.log(99.0), rel=1e-14)
     assert pkg.Homotopy(1e-3, delta_max=0.5, eps=0.1)(1) == pytest.approx(math.log(9.0) / 1e-3, rel=1e-14)
-    np.testing.assert_allclose([h(x) for x in np.linspace(0, 1, 10)], ou.KAPPA10, rtol=1e-13)
+    np.testing.assert_allclose([h(x) for x in np.linspace(0, 1, 10)], models.KAPPA10, rtol=1e-13)
 
 
 def test_guess_is_the_free_response(pkg):
@@ -211,13 +210,13 @@ def test_guess_is_the_free_response(pkg):
     pm, N = pkg.REGISTRY["oscillator"](), 12
     wd = pm.w0 * math.sqrt(1.0 - pm.zeta ** 2)
     t = pm.tf * np.arange(N) / (N - 1)
-    for pp in ou.INSTANCES:
+    for pp in models.INSTANCES:
         r0, v0 = pp
         a, b = r0, (v0 + pm.zeta * pm.w0 * r0) / wd
         e = np.exp(-pm.zeta * pm.w0 * t)
         r = e * (a * np.cos(wd * t) + b * np.sin(wd * t))
         v = -pm.zeta * pm.w0 * r + e * wd * (-a * np.sin(wd * t) + b * np.cos(wd * t))
-        for mdl in (pm, ou.Oscillator(N)):
+        for mdl in (pm, models.Oscillator(N)):
             x, u, p = mdl.guess(N, pp)
             assert np.abs(x - np.stack([r, v], axis=1)).max() <= 5e-5 * (abs(r0) + abs(v0))
             np.testing.assert_array_equal(x[0], pp)

@@ -1,5 +1,5 @@
 """Oscillator with actuator deadband on the device: discretize! and the device guess against the numpy restatement
-(tests/oscillator_util.py), teacher-forced subproblems and the warm-started PTR homotopy against the oracle's fixture
+(oracle/models.py, oracle/discretize_ref.py), teacher-forced subproblems and the warm-started PTR homotopy against the oracle's fixture
 (tests/golden/oscillator_outcomes_n12.npz), the device-resident continuation against a host restart, model constants changed
 after create, and the refusals."""
 import ctypes
@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-import oscillator_util as ou
+from oracle import discretize_ref, models
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oscillator_outcomes_n12.npz")
@@ -30,17 +30,17 @@ def make(pkg, N, Nsub, cap, kappa1=1.0, method=None, iter_max=10):
 @pytest.mark.parametrize("method,N,Nsub,B", [("foh", 6, 5, 3), ("impulse", 6, 5, 3), ("foh", 30, 10, 1)])
 def test_discretize_against_the_restatement(pkg, method, N, Nsub, B):
     pbm = make(pkg, N, Nsub, B, method=pkg.IMPULSE if method == "impulse" else pkg.FOH)
-    mdl = ou.Oscillator(N)
+    mdl = models.Oscillator(N)
     rng = np.random.default_rng(5)
     xs, us, ps = [], [], []
     for b in range(B):
-        x, u, p = mdl.guess(N, ou.INSTANCES[b])
+        x, u, p = mdl.guess(N, models.INSTANCES[b])
         xs.append(x + 0.1 * rng.standard_normal(x.shape)); us.append(0.3 * rng.uniform(-1, 1, u.shape)); ps.append(p)
     ref = pkg.SubproblemSolutionBatch(np.stack(xs), np.stack(us), np.stack(ps), pbm)
     pkg.discretize_(ref, pbm)
     assert ref.dyn.F.shape[2] == 0
     for b in range(B):
-        o = ou.discretize_arrays(mdl, N, Nsub, ref.xd[b], ref.ud[b], ref.p[b], pbm.scale.iSx, pbm.pars.feas_tol, method)
+        o = discretize_ref.discretize_arrays(mdl, N, Nsub, ref.xd[b], ref.ud[b], ref.p[b], pbm.scale.iSx, pbm.pars.feas_tol, method)
         for nm, got in (("A", ref.dyn.A[b]), ("Bm", ref.dyn.B[0][b]), ("Bp", ref.dyn.B[1][b]), ("E", ref.dyn.E[b])):
             err = np.abs(np.swapaxes(got, 1, 2) - o[nm]).max() / max(1.0, np.abs(o[nm]).max())
             assert err < 1e-10, (nm, b, err)
@@ -53,11 +53,11 @@ def test_discretize_against_the_restatement(pkg, method, N, Nsub, B):
 
 def test_device_guess_against_the_restatement(pkg):
     N = 12
-    pbm = make(pkg, N, 10, len(ou.INSTANCES))
-    xd, ud, p = pkg.device_guess(pbm, ou.INSTANCES)
+    pbm = make(pkg, N, 10, len(models.INSTANCES))
+    xd, ud, p = pkg.device_guess(pbm, models.INSTANCES)
     assert pkg.device_guess_failures(pbm) == 0
-    mdl = ou.Oscillator(N)
-    for b, pp in enumerate(ou.INSTANCES):
+    mdl = models.Oscillator(N)
+    for b, pp in enumerate(models.INSTANCES):
         x, u, pn = mdl.guess(N, pp)
         assert np.abs(xd[b] - x).max() < 1e-10 and np.abs(ud[b] - u).max() == 0.0 and np.abs(p[b] - pn).max() < 1e-10
     pbm.close()
@@ -87,7 +87,7 @@ def test_homotopy_loop_on_a_batch_across_a_wavefront(pkg, gold):
     assert (summ["status"] == 0).all()                      # the reference's own assertion (oscillator/tests.jl:81), at every stage
     assert all(st == "SCP_SOLVED" for st in sol.status)
     assert sol.feas.all()
-    mdl = ou.Oscillator(int(gold["N"]), float(gold["kappa"][-1]))
+    mdl = models.Oscillator(int(gold["N"]), float(gold["kappa"][-1]))
     smax = max(mdl.s(0.0, k + 1, sol.xd[b, k], sol.ud[b, k], sol.p[b]).max() for b in range(B) for k in range(mdl.N))
     print("largest deadband violation max(s, 0) at the last kappa1: %.3e" % max(smax, 0.0))
     assert max(smax, 0.0) <= 1e-6
