@@ -324,6 +324,63 @@ int scp_model_audit_intervals_host(int model_id, const double *model_par, int N,
                                    const double *p, const double *pp, const double *Sx, int res, double viol_tol,
                                    double *audit, double *intervals /* [16, N-1] or NULL */);
 
+/*
+ * Dispersed-flight audit.  Every flight above happens in a perfect world: it starts at exactly xd[:,1], flies exactly the
+ * optimised input and uses exactly the constants the optimiser used.  Here every problem b is flown D times off-nominal in ONE
+ * launch, one device thread per (problem, flight); FOH handles of the four auditable models.  Flight d = 1 .. D is the
+ * single-shooting audit of scp_audit_batch_host -- same samples, same RK4, same k_j rule -- with three changes:
+ *   initial state  x(0) = xd[:,1,b] + dx0[:,d,b], in physical units
+ *   actuators      at every time, stage times included, the flown input is u'(t) = ugain[:,d,b] o u_foh(t) + ubias[:,d,b]
+ *                  (component-wise); the dynamics, the row families of U, the cones and Gamma all see u': the flight is
+ *                  audited as flown
+ *   truth model    par_true[npar], one per call, or NULL = the handle's own constants: the blob, taken as given like the one of
+ *                  scp_problem_create, replaces the handle's constants for everything the flight evaluates (dynamics, s, rows,
+ *                  cost, g_tc); any entry may differ, the handle is not changed
+ * p and pp are not dispersed, and the drift [8] is measured against the undispersed xd[:,N,b].  dx0[nx,D,B], ugain[nu,D,B],
+ * ubias[nu,D,B]; NULL means 0, 1 and 0.  flags = SCP_DISP_SHARED: the three arrays carry no batch dimension ([., D]) and every
+ * problem flies the same D dispersions.
+ *
+ * flights[SCP_AUDIT_WIDTH, D, B]: one record per flight in exactly the single-shooting layout ([12..15] = 0).  May be NULL:
+ * then the records stay on the device.
+ * summary[SCP_AUDIT_WIDTH, B]: the fold of a problem's flight records IN FLIGHT ORDER by one thread per problem, so that both
+ * outputs are independent of B, of the place of a problem in the batch and of the launch geometry.  A flight whose record
+ * [11] != 0 is counted in [11] and takes no part in any other field; m = the number of counted flights:
+ *   [0], [1]   max over the counted flights of the s maximum, and the 1-based flight attaining it (strict >: the first wins;
+ *              no finite value: -Inf, 0);  [2], [3] the same for the linear rows;  [4], [5] for the cones
+ *   [6]        the parameter-only rows, of the first counted flight (-Inf when m = 0)
+ *   [7]        max over the counted flights of ||g_tc||_inf;  [12] the 1-based flight attaining it (the first wins)
+ *   [8]        max of the drift
+ *   [9]        mean cost (((c_1 + c_2) + ...) + c_m) / m;  [15] max cost
+ *   [10]       flights with a violation count > 0
+ *   [11]       flights that were not finite
+ *   [13]       2.0 (single-shooting records hold 0 there, multiple-shooting ones 1.0)
+ *   [14]       D
+ * With m = 0: [7], [8], [9], [15] are NaN and [12] = 0.  A masked or failed problem: NaN in its summary and all its flights.
+ *
+ * Staging, ownership, masking and *seconds (the two kernels without the copies) follow scp_audit_batch_host /
+ * scp_audit_resident.  SCP_ERR_UNSUPPORTED (with an error text on a handle) for IMPULSE handles and for models with node
+ * parameters; SCP_ERR_BAD_ARGUMENT for D < 1, res < 2, a NULL summary, unknown flag bits and a missing p / pp;
+ * SCP_ERR_BATCH_TOO_LARGE for B above the handle's capacity; SCP_ERR_ALLOC when the flight buffer -- 16 D batch_capacity
+ * doubles, owned by the handle, allocated on first use and rebuilt when D grows -- cannot be allocated.
+ */
+#define SCP_DISP_SHARED 1u
+int scp_audit_dispersed_batch_host(scp_handle h, int B, const double *xd, const double *ud, const double *p, const double *pp,
+                                   int res, double viol_tol, int D, const double *dx0, const double *ugain, const double *ubias,
+                                   unsigned flags, const double *par_true, double *summary, double *flights /* may be NULL */,
+                                   double *seconds);
+int scp_audit_dispersed_resident(scp_handle h, int res, double viol_tol, int D, const double *dx0, const double *ugain,
+                                 const double *ubias, unsigned flags, const double *par_true, double *summary,
+                                 double *flights /* may be NULL */, double *seconds);
+/*
+ * The same two outputs for ONE problem on the host by the same code: dx0[nx,D], ugain[nu,D], ubias[nu,D] (each may be NULL),
+ * summary[SCP_AUDIT_WIDTH], flights[SCP_AUDIT_WIDTH, D] or NULL.  model_par plays the handle's blob, par_true (or NULL) the
+ * truth model's.  SCP_ERR_UNSUPPORTED for models with node parameters, SCP_ERR_UNKNOWN_MODEL for an unknown model_id.
+ */
+int scp_model_audit_dispersed_host(int model_id, const double *model_par, const double *par_true, int N, const double *xd,
+                                   const double *ud, const double *p, const double *pp, const double *Sx, int res,
+                                   double viol_tol, int D, const double *dx0, const double *ugain, const double *ubias,
+                                   double *summary, double *flights /* [16, D] or NULL */);
+
 /* ------------------------------------------------------------------------ */
 /* PTR: solve_subproblem! and the outer loop                                  */
 /* ------------------------------------------------------------------------ */

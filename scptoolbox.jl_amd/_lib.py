@@ -110,6 +110,7 @@ EXPORTS = [
     "scp_ptr_solve_subproblem_batch_host", "scp_debug_get_stage_problem", "scp_ptr_restart", "scp_get_kernel_timing", "scp_debug_get_ipm_profile", "scp_propagate_batch_host", "scp_ptr_init_guess_host",
     "scp_audit_batch_host", "scp_audit_resident", "scp_model_audit_host",
     "scp_audit_intervals_batch_host", "scp_audit_intervals_resident", "scp_model_audit_intervals_host",
+    "scp_audit_dispersed_batch_host", "scp_audit_dispersed_resident", "scp_model_audit_dispersed_host",
     "scp_ptr_get_virtual_controls_host", "scp_ptr_iterate_async", "scp_ptr_poll", "scp_ptr_poll_iteration", "scp_guess_batch_host", "scp_guess_failures",
     "scp_sub_source_layout", "scp_sub_create", "scp_sub_destroy", "scp_sub_stats", "scp_sub_last_error", "scp_sub_solve_batch_host",
     "scp_scvx_init_host", "scp_scvx_iterate", "scp_scvx_get_host",
@@ -181,6 +182,12 @@ def lib():
         L.scp_audit_intervals_resident.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, c_double_p]
         L.scp_model_audit_intervals_host.argtypes = ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
                                                      + [ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p])
+        L.scp_audit_dispersed_batch_host.argtypes = ([ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_double, ctypes.c_int]
+                                                     + [ctypes.c_void_p] * 3 + [ctypes.c_uint] + [ctypes.c_void_p] * 3 + [c_double_p])
+        L.scp_audit_dispersed_resident.argtypes = ([ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 3
+                                                   + [ctypes.c_uint] + [ctypes.c_void_p] * 3 + [c_double_p])
+        L.scp_model_audit_dispersed_host.argtypes = ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5
+                                                     + [ctypes.c_int, ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 5)
         L.scp_ptr_get_virtual_controls_host.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 6
         L.scp_get_kernel_timing.argtypes = [ctypes.c_void_p, c_double_p, ctypes.POINTER(ctypes.c_long), ctypes.c_int]
         L.scp_debug_get_stage_problem.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,

@@ -1,6 +1,7 @@
-// The continuous-time audit's own translation unit: the four instantiations of audit_foh_kernel and the six of
-// audit_interval_kernel with their fold (audit_kernel.hpp), their launches for the handle-level entry points of scp_api.hip,
-// and the pure-host twins scp_model_audit_host and scp_model_audit_intervals_host.
+// The continuous-time audit's own translation unit: the four instantiations of audit_foh_kernel, the six of
+// audit_interval_kernel with their fold and the four of audit_dispersed_kernel with its fold (audit_kernel.hpp), their launches
+// for the handle-level entry points of scp_api.hip, and the pure-host twins scp_model_audit_host,
+// scp_model_audit_intervals_host and scp_model_audit_dispersed_host.
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -69,6 +70,32 @@ int audit_intervals_launch(int model_id, const double* model_par, int disc_metho
     });
 }
 
+// one thread per problem: its D records in flight order -> the summary record (no model enters: the records carry everything)
+__global__ __launch_bounds__(64) void audit_dispersed_fold_kernel(AuditDispersedArgs a)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.B) return;
+    double* out = a.audit + (long)b * SCP_AUDIT_WIDTH;
+    if (a.mask != nullptr && a.mask[b] == 0) {
+#pragma unroll
+        for (int i = 0; i < SCP_AUDIT_WIDTH; i++) out[i] = NAN;
+        return;
+    }
+    audit_dispersed_fold(a.D, a.flights + (long)b * a.D * SCP_AUDIT_WIDTH, out);
+}
+
+int audit_dispersed_launch(int model_id, const double* model_par, const AuditDispersedArgs& a, hipStream_t stream)
+{
+    return with_audit_model(model_id, [&](auto m) -> int {
+        using M = decltype(m);
+        const dim3 grid((unsigned)(((long)a.B * a.D + 63) / 64)), block(64);
+        hipLaunchKernelGGL(audit_dispersed_kernel<M>, grid, block, 0, stream, a, M::make_params(model_par));
+        if (hipGetLastError() != hipSuccess) return (int)SCP_ERR_HIP;
+        hipLaunchKernelGGL(audit_dispersed_fold_kernel, dim3((a.B + 63) / 64), block, 0, stream, a);
+        return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+    });
+}
+
 }  // namespace scp
 
 extern "C" int scp_model_audit_host(int model_id, const double* model_par, int N, const double* xd, const double* ud,
@@ -106,6 +133,27 @@ extern "C" int scp_model_audit_intervals_host(int model_id, const double* model_
             scp::audit_interval_one<M, false>(par, N, sub, k0, viol_tol, xd, ud, p, pp, Sx, rec);
         }
         scp::audit_interval_fold(N, sub, intervals, scp::audit_par_max<M>(par, p), M::ng > 0, audit);
+        return (int)SCP_OK;
+    });
+}
+
+extern "C" int scp_model_audit_dispersed_host(int model_id, const double* model_par, const double* par_true, int N, const double* xd,
+                                              const double* ud, const double* p, const double* pp, const double* Sx, int res,
+                                              double viol_tol, int D, const double* dx0, const double* ugain, const double* ubias,
+                                              double* summary, double* flights)
+{
+    if (!model_par || N < 2 || !xd || !ud || !Sx || !summary || res < 2 || D < 1) return SCP_ERR_BAD_ARGUMENT;
+    return scp::with_audit_model(model_id, [&](auto m) -> int {
+        using M = decltype(m);
+        if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
+        const typename M::Params par = M::make_params(par_true ? par_true : model_par);
+        std::vector<double> own;
+        if (!flights) { own.resize((size_t)SCP_AUDIT_WIDTH * D); flights = own.data(); }
+        for (int d = 0; d < D; d++)
+            scp::audit_dispersed_one<M>(par, N, res, viol_tol, xd, ud, p, pp, Sx, dx0 ? dx0 + (size_t)d * M::nx : nullptr,
+                                        ugain ? ugain + (size_t)d * M::nu : nullptr, ubias ? ubias + (size_t)d * M::nu : nullptr,
+                                        flights + (size_t)d * SCP_AUDIT_WIDTH);
+        scp::audit_dispersed_fold(D, flights, summary);
         return (int)SCP_OK;
     });
 }

@@ -474,4 +474,179 @@ __global__ __launch_bounds__(64) void audit_interval_fold_kernel(AuditIntervalAr
                         audit_par_max<M>(par, a.p + (long)b * np_total<M>(a.N)), M::ng > 0, out);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dispersed-flight audit (scp_audit_dispersed_*): every problem is flown D times OFF-nominal by the single-shooting audit above
+// -- same samples, same RK4, same k_j rule -- with three changes per flight d = 1 .. D:
+//   initial state  x(0) = xd[:,1] + dx0[:,d]                                  (physical units)
+//   actuators      u'(t) = ugain[:,d] o u_foh(t) + ubias[:,d] at every time, stage times included; the dynamics, the row
+//                  families, the cones and Gamma all see u': the flight is audited as flown
+//   truth model    `par` is the M::Params of the call's par_true where one is given: dynamics, s, rows, cost and g_tc
+// p and pp are not dispersed, and the drift (record 8) is measured against the undispersed xd[:,N].  One record per flight in
+// the single-shooting layout; the records of a problem are then folded IN FLIGHT ORDER into its summary, so that neither output
+// depends on the batch size, on the place of a problem in the batch or on the launch geometry.
+// audit_one is not touched: the dispersed flight is a body of its own that shares the per-sample and end-point functions.
+// ------------------------------------------------------------------------------------------------
+struct AuditDispersedArgs {
+    int B, N, res, D;
+    int shared;          // 1: dx0 / ugain / ubias carry no batch dimension ([., D]) and every problem flies the same D dispersions
+    double viol_tol;
+    const double* xd;    // [nx,N,B]
+    const double* ud;    // [nu,N,B]
+    const double* p;     // [np,B]
+    const double* pp;    // [npp,B]
+    const double* Sx;    // [nx]
+    const double* dx0;   // [nx,D,B] or [nx,D]; nullptr = 0
+    const double* ugain; // [nu,D,B] or [nu,D]; nullptr = 1
+    const double* ubias; // [nu,D,B] or [nu,D]; nullptr = 0
+    const int* mask;     // optional [B]: problems with mask[b] == 0 are skipped, their summary and flight records are NaN
+    double* flights;     // [SCP_AUDIT_WIDTH,D,B]
+    double* audit;       // [SCP_AUDIT_WIDTH,B]
+};
+
+// audit_api.hip: audit_dispersed_kernel<M> then audit_dispersed_fold_kernel (no model enters the fold: it lives there) on `stream`; model_par is the blob the flights fly with
+int audit_dispersed_launch(int model_id, const double* model_par, const AuditDispersedArgs& a, hipStream_t stream);
+
+// ONE flight of ONE problem: xd[nx,N], ud[nu,N], p[np], pp[npp], Sx[nx], dx0[nx], gain[nu], bias[nu] (each of the last three may
+// be nullptr) -> out[SCP_AUDIT_WIDTH]
+template <class M>
+SCP_DEV void audit_dispersed_one(const typename M::Params& par, int N, int res, double viol_tol, const double* xd, const double* ub,
+                                 const double* pb, const double* pp, const double* Sx, const double* dx0, const double* gain,
+                                 const double* bias, double* out)
+{
+    static_assert(M::np_node == 0, "a row of node k would read that node's own parameters: undefined between the nodes");
+    constexpr int nx = M::nx, nu = M::nu, np = M::np, npa = np > 0 ? np : 1, npF = M::npF, npFa = npF > 0 ? npF : 1, ng = M::ng;
+
+    double x[nx], ug[nu], ubs[nu];
+#pragma unroll
+    for (int i = 0; i < nx; i++) x[i] = xd[i] + (dx0 != nullptr ? dx0[i] : 0.0);
+#pragma unroll
+    for (int i = 0; i < nu; i++) { ug[i] = gain != nullptr ? gain[i] : 1.0; ubs[i] = bias != nullptr ? bias[i] : 0.0; }
+    // u'(t): the first-order hold of audit_one (same clamp, same interval search), then gain and bias
+    auto input = [&](double t, double (&u)[nu]) {
+        const double g0 = audit_linrange(0.0, 1.0, N, 0), g1 = audit_linrange(0.0, 1.0, N, N - 1);
+        t = fmax(g0, fmin(g1, t));
+        int k = (int)floor(t * (N - 1));
+        k = k < 0 ? 0 : (k > N ? N : k);
+        while (k < N && t > audit_linrange(0.0, 1.0, N, k)) k++;
+        while (k > 0 && !(t > audit_linrange(0.0, 1.0, N, k - 1))) k--;
+        if (k == 0) k = 1;
+        const double ta = audit_linrange(0.0, 1.0, N, k - 1), tb = audit_linrange(0.0, 1.0, N, k);
+        const double c = (tb - t) / (tb - ta);
+#pragma unroll
+        for (int i = 0; i < nu; i++) u[i] = ug[i] * (c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i]) + ubs[i];
+    };
+    auto f = [&](double t, const double (&xs)[nx], double (&fx)[nx]) {
+        double u[nu], Am[nx * nx], Bmat[nx * nu], Fc[nx * npFa];
+        input(t, u);
+        M::dyn(par, t, N, xs, u, pb, fx, Am, Bmat, Fc);   // only f survives dead-code elimination
+    };
+
+    double Qu[nu], lu[nu], lx[nx], tx[nx], ctp[npa], cQp[npa];
+#pragma unroll
+    for (int i = 0; i < npa; i++) { ctp[i] = 0.0; cQp[i] = 0.0; }
+    M::cost_terms(par, Qu, lu, lx, tx, ctp, cQp);
+
+    AuditAcc acc;
+    double gam_prev = 0.0, cost_int = 0.0;
+    auto sample = [&](double t) -> double {
+        // 1-based index of the last grid node <= t, decided against the exact grid values (N at t = 1)
+        int k = (int)floor(t * (N - 1)) + 1;
+        k = k < 1 ? 1 : (k > N ? N : k);
+        while (k < N && !(audit_linrange(0.0, 1.0, N, k) > t)) k++;
+        while (k > 1 && audit_linrange(0.0, 1.0, N, k - 1) > t) k--;
+        double u[nu];
+        input(t, u);
+        return audit_sample<M>(par, t, k, x, u, pb, viol_tol, Qu, lu, lx, acc);
+    };
+
+    gam_prev = sample(audit_linrange(0.0, 1.0, res, 0));
+    for (int j = 1; j < res; j++) {
+        const double t = audit_linrange(0.0, 1.0, res, j - 1), tp = audit_linrange(0.0, 1.0, res, j), h = tp - t;
+        double k1[nx], k2[nx], k3[nx], k4[nx], tmp[nx];
+        f(t, x, k1);
+#pragma unroll
+        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h / 2 * k1[i];
+        f(t + h / 2, tmp, k2);
+#pragma unroll
+        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h / 2 * k2[i];
+        f(t + h / 2, tmp, k3);
+#pragma unroll
+        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h * k3[i];
+        f(t + h, tmp, k4);
+#pragma unroll
+        for (int i = 0; i < nx; i++) x[i] = x[i] + h / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+        M::action(x);
+        const double gam = sample(tp);
+        cost_int += 0.5 * h * (gam + gam_prev);
+        gam_prev = gam;
+    }
+
+    // ---- quantities of the end point and of the parameters alone; the drift against the UNDISPERSED last node ----
+    const double par_max = audit_par_max<M>(par, pb);
+    const double bc = audit_bc_tc<M>(par, x, pb, pp, acc.bad);
+    double drift = 0.0;
+#pragma unroll
+    for (int i = 0; i < nx; i++) {
+        const double d = (x[i] - xd[(long)(N - 1) * nx + i]) / Sx[i];
+        acc.bad = acc.bad || !__builtin_isfinite(d);
+        drift = fmax(drift, fabs(d));
+    }
+    const double phi = audit_phi<M>(x, pb, tx, ctp, cQp);
+    const double cost = phi + cost_int;
+    acc.bad = acc.bad || !__builtin_isfinite(cost) || (ng > 0 && !__builtin_isfinite(par_max));
+
+    out[0] = acc.s_max; out[1] = acc.t_s; out[2] = acc.l_max; out[3] = acc.t_l; out[4] = acc.c_max; out[5] = acc.t_c;
+    out[6] = par_max; out[7] = bc; out[8] = drift; out[9] = cost; out[10] = acc.n_viol; out[11] = acc.bad ? 1.0 : 0.0;
+#pragma unroll
+    for (int i = 12; i < SCP_AUDIT_WIDTH; i++) out[i] = 0.0;
+}
+
+// The ordered fold of the D flight records recs[SCP_AUDIT_WIDTH, D] of ONE problem into out[SCP_AUDIT_WIDTH].  A flight whose
+// record [11] != 0 is counted in [11] and takes no part in any other field.  Strict comparisons from -Inf: the first flight wins
+// a tie.  [6] is that of the first counted flight (-Inf when none is counted); the mean cost is (((c_1 + c_2) + ...) + c_m) / m.
+SCP_DEV void audit_dispersed_fold(int D, const double* recs, double* out)
+{
+    double vmax[3] = {-INFINITY, -INFINITY, -INFINITY}, dmax[3] = {0.0, 0.0, 0.0};
+    double par_max = -INFINITY, bc = -INFINITY, dbc = 0.0, drift = -INFINITY, sum = 0.0, cmax = -INFINITY, n_viol = 0.0, n_bad = 0.0;
+    int m = 0;
+    for (int d = 0; d < D; d++) {
+        const double* r = recs + (long)d * SCP_AUDIT_WIDTH;
+        if (r[11] != 0.0) { n_bad += 1.0; continue; }
+#pragma unroll
+        for (int f = 0; f < 3; f++)
+            if (r[2 * f] > vmax[f]) { vmax[f] = r[2 * f]; dmax[f] = (double)(d + 1); }
+        if (m == 0) par_max = r[6];
+        if (r[7] > bc) { bc = r[7]; dbc = (double)(d + 1); }
+        if (r[8] > drift) drift = r[8];
+        sum += r[9];
+        if (r[9] > cmax) cmax = r[9];
+        if (r[10] > 0.0) n_viol += 1.0;
+        m++;
+    }
+    out[0] = vmax[0]; out[1] = dmax[0]; out[2] = vmax[1]; out[3] = dmax[1]; out[4] = vmax[2]; out[5] = dmax[2];
+    out[6] = par_max; out[7] = m > 0 ? bc : NAN; out[8] = m > 0 ? drift : NAN; out[9] = m > 0 ? sum / (double)m : NAN;
+    out[10] = n_viol; out[11] = n_bad; out[12] = dbc; out[13] = 2.0; out[14] = (double)D; out[15] = m > 0 ? cmax : NAN;
+}
+
+// one thread per (problem, flight), gid = b D + (d - 1), blocks of one wavefront: the mapping of audit_interval_kernel.
+// Neighbouring lanes fly the same problem, so their ud loads hit the same addresses and the trip count is uniform.
+template <class M>
+__global__ __launch_bounds__(64) void audit_dispersed_kernel(AuditDispersedArgs a, typename M::Params par)
+{
+    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    if (gid >= (long)a.B * a.D) return;
+    const int b = (int)(gid / a.D);
+    double* rec = a.flights + gid * SCP_AUDIT_WIDTH;
+    if (a.mask != nullptr && a.mask[b] == 0) {
+#pragma unroll
+        for (int i = 0; i < SCP_AUDIT_WIDTH; i++) rec[i] = NAN;
+        return;
+    }
+    const long col = a.shared ? gid % a.D : gid;          // the flight's column of the dispersion arrays
+    audit_dispersed_one<M>(par, a.N, a.res, a.viol_tol, a.xd + (long)b * a.N * M::nx, a.ud + (long)b * a.N * M::nu,
+                           a.p + (long)b * np_total<M>(a.N), a.pp + (long)b * M::npp, a.Sx,
+                           a.dx0 != nullptr ? a.dx0 + col * M::nx : nullptr, a.ugain != nullptr ? a.ugain + col * M::nu : nullptr,
+                           a.ubias != nullptr ? a.ubias + col * M::nu : nullptr, rec);
+}
+
 }  // namespace scp

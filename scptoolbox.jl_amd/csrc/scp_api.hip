@@ -316,6 +316,8 @@ extern "C" int scp_problem_destroy(scp_handle h)
     (void)hipSetDevice(h->device);
     if (h->guess.sg) starship_guess_free(h->guess.sg);
     for (void* p : h->allocs) (void)hipFree(p);
+    for (double* p : {h->audit.flights, h->audit.dx0, h->audit.ugain, h->audit.ubias})
+        if (p) (void)hipFree(p);
     for (auto& st : h->timing.stamps_free) { (void)hipEventDestroy(st.a); (void)hipEventDestroy(st.b); }
     for (auto& st : h->timing.stamps_pending) { (void)hipEventDestroy(st.a); (void)hipEventDestroy(st.b); }
     if (h->timing.ev0) (void)hipEventDestroy(h->timing.ev0);
@@ -682,4 +684,87 @@ extern "C" int scp_audit_intervals_resident(scp_handle h, int res, double viol_t
     AuditSource src;
     TRY(audit_resident_source(h, "scp_audit_intervals_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
     return audit_intervals_run(h, src.B, src.tr, src.d_pp, h->audit.mask, res, viol_tol, audit, intervals, seconds);
+}
+
+// dispersed-flight audit: D off-nominal flights per problem and their ordered fold (audit_kernel.hpp)
+static int audit_dispersed_begin(scp_problem* h, int res, int D, unsigned flags, const double* summary)
+{
+    TRY(audit_begin(h, res, summary));
+    if (D < 1 || (flags & ~SCP_DISP_SHARED) != 0u) { h->err = "audit: D >= 1 and no flag bit but SCP_DISP_SHARED are required"; return SCP_ERR_BAD_ARGUMENT; }
+    return SCP_OK;
+}
+
+// the flight records and the staged dispersions for D flights of every problem the handle can hold
+static int audit_dispersed_reserve(scp_problem* h, int D)
+{
+    scp_problem::Audit& A = h->audit;
+    if (D <= A.disp_D) return SCP_OK;
+    for (double** p : {&A.flights, &A.dx0, &A.ugain, &A.ubias}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    A.disp_D = 0;
+    const size_t n = (size_t)D * (size_t)h->cap * sizeof(double);
+    if (hipMalloc((void**)&A.flights, SCP_AUDIT_WIDTH * n) != hipSuccess || hipMalloc((void**)&A.dx0, (size_t)h->info.nx * n) != hipSuccess ||
+        hipMalloc((void**)&A.ugain, (size_t)h->info.nu * n) != hipSuccess || hipMalloc((void**)&A.ubias, (size_t)h->info.nu * n) != hipSuccess) {
+        (void)hipGetLastError();
+        for (double** p : {&A.flights, &A.dx0, &A.ugain, &A.ubias}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        h->err = "audit: the buffers of " + std::to_string(D) + " flights per problem could not be allocated";
+        return SCP_ERR_ALLOC;
+    }
+    A.disp_D = D;
+    return SCP_OK;
+}
+
+// the dispersions to the device, the two kernels between the handle's two events, then the copies
+static int audit_dispersed_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, int res, double viol_tol,
+                               int D, const double* dx0, const double* ugain, const double* ubias, unsigned flags,
+                               const double* par_true, double* summary, double* flights, double* seconds)
+{
+    TRY(audit_dispersed_reserve(h, D));
+    const bool shared = (flags & SCP_DISP_SHARED) != 0u;
+    const size_t cols = shared ? (size_t)D : (size_t)D * (size_t)B;
+    if (dx0) HIP_TRY(h, hipMemcpyAsync(h->audit.dx0, dx0, sizeof(double) * h->info.nx * cols, hipMemcpyHostToDevice, h->stream));
+    if (ugain) HIP_TRY(h, hipMemcpyAsync(h->audit.ugain, ugain, sizeof(double) * h->info.nu * cols, hipMemcpyHostToDevice, h->stream));
+    if (ubias) HIP_TRY(h, hipMemcpyAsync(h->audit.ubias, ubias, sizeof(double) * h->info.nu * cols, hipMemcpyHostToDevice, h->stream));
+    AuditDispersedArgs a;
+    a.B = B; a.N = h->N; a.res = res; a.D = D; a.shared = shared ? 1 : 0; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
+    a.pp = d_pp; a.Sx = h->d_Sx; a.dx0 = dx0 ? h->audit.dx0 : nullptr; a.ugain = ugain ? h->audit.ugain : nullptr;
+    a.ubias = ubias ? h->audit.ubias : nullptr; a.mask = mask; a.flights = h->audit.flights; a.audit = h->audit.rec;
+    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
+    // the truth model: the blob the flights are flown with; like the handle's own it is taken as given
+    const int rc = audit_dispersed_launch(h->model_id, par_true ? par_true : h->par.data(), a, h->stream);
+    if (rc != SCP_OK) { h->err = "audit: kernel launch failed"; return rc; }
+    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(summary, h->audit.rec, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    if (flights)
+        HIP_TRY(h, hipMemcpyAsync(flights, h->audit.flights, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)D * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    stamps_collect(h);
+    return elapsed_out(h, seconds);
+}
+
+extern "C" int scp_audit_dispersed_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
+                                              int res, double viol_tol, int D, const double* dx0, const double* ugain,
+                                              const double* ubias, unsigned flags, const double* par_true, double* summary,
+                                              double* flights, double* seconds)
+{
+    TRY(audit_dispersed_begin(h, res, D, flags, summary));
+    TRY(audit_stage_host(h, B, xd, ud, p, pp));
+    return audit_dispersed_run(h, B, traj_sol(h), h->audit.pp, nullptr, res, viol_tol, D, dx0, ugain, ubias, flags, par_true, summary,
+                               flights, seconds);
+}
+
+extern "C" int scp_audit_dispersed_resident(scp_handle h, int res, double viol_tol, int D, const double* dx0, const double* ugain,
+                                            const double* ubias, unsigned flags, const double* par_true, double* summary,
+                                            double* flights, double* seconds)
+{
+    TRY(audit_dispersed_begin(h, res, D, flags, summary));
+    AuditSource src;
+    TRY(audit_resident_source(h, "scp_audit_dispersed_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
+    return audit_dispersed_run(h, src.B, src.tr, src.d_pp, h->audit.mask, res, viol_tol, D, dx0, ugain, ubias, flags, par_true, summary,
+                               flights, seconds);
 }

@@ -82,6 +82,11 @@ struct scp_problem {
         double *rec = nullptr, *pp = nullptr;
         double* intervals = nullptr;   // [SCP_AUDIT_INTERVAL_WIDTH (N-1) cap], scp_audit_intervals_*; lazily built
         int* mask = nullptr;
+        // scp_audit_dispersed_*: flight records [SCP_AUDIT_WIDTH disp_D cap] and the staged dispersions dx0 [nx disp_D cap],
+        // ugain, ubias [nu disp_D cap]; built on first use and rebuilt when a call asks for more flights than disp_D.  Not in
+        // h->allocs: audit_dispersed_reserve frees what it replaces, scp_problem_destroy the last set
+        double *flights = nullptr, *dx0 = nullptr, *ugain = nullptr, *ubias = nullptr;
+        int disp_D = 0;
     } audit;
 
     // ---- trajectories: allocated by scp_api.hip at create; written by the run that owns them (h->run: ptr_api.hip or

@@ -426,6 +426,125 @@ def audit_intervals_resident(pbm, res=None, viol_tol=0.0, intervals=True):
     return a
 
 
+DISP_SHARED = 1      # SCP_DISP_SHARED
+_DISPERSED_FIELDS = ("s_max", "flight_s", "lin_max", "flight_lin", "soc_max", "flight_soc", "par_max", "bc_tc", "drift", "cost_mean",
+                     "n_violating", "n_nonfinite", "flight_bc")
+
+
+class DispersedAuditBatch:
+    """The dispersed-flight audit of a batch (scp_audit_dispersed_batch_host / scp_audit_dispersed_resident, include/scp_mi355x.h):
+    every problem flown `D` times off-nominal.  Named views [B] of the summary records: s_max / lin_max / soc_max = the worst
+    value over the counted flights (flight_s / flight_lin / flight_soc: the 1-based flight attaining it, 0 when no value is finite),
+    par_max, bc_tc and drift = the largest over the flights (flight_bc: the flight of bc_tc), cost_mean and cost_max,
+    n_violating = flights with samples above viol_tol, n_nonfinite = flights that were not finite (they take no part in any other
+    field).  Skipped (failed) problems hold NaN everywhere.  `raw` is the [B, 16] array itself; `flights` [B, D, 16] holds the
+    single-shooting record of every flight when they were asked for, else None."""
+
+    def __init__(self, raw, res, viol_tol, D, flights=None):
+        self.raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1, AUDIT_WIDTH)
+        self.res, self.viol_tol, self.D = int(res), float(viol_tol), int(D)
+        for j, name in enumerate(_DISPERSED_FIELDS):
+            setattr(self, name, self.raw[:, j])
+        self.cost_max = self.raw[:, 15]
+        self.flights = None if flights is None else np.ascontiguousarray(flights, dtype=np.float64).reshape(len(self), self.D, AUDIT_WIDTH)
+        self.seconds = 0.0
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    @property
+    def skipped(self):
+        return np.isnan(self.raw[:, 13])
+
+    def flight_batch(self, b):
+        """the D flights of problem b as an AuditBatch (needs flights=True)"""
+        if self.flights is None:
+            raise ValueError("the flight records were not asked for (flights=True)")
+        return AuditBatch(self.flights[b], self.res, self.viol_tol)
+
+
+def _dispersed_args(pbm, B, dx0, ugain, ubias, shared, model):
+    """the three dispersion arrays as [B, D, n] ([D, n] when shared) C arrays (None stays None), D, the flags and par_true"""
+    arrs, D = [], None
+    for a, n in ((dx0, pbm.nx), (ugain, pbm.nu), (ubias, pbm.nu)):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            want = (a.shape[-2] if a.ndim >= 2 else 0, n) if shared else (B, a.shape[-2] if a.ndim >= 2 else 0, n)
+            if a.shape != want:
+                raise ValueError("dispersion array of shape %s, expected %s" % (a.shape, "[D, %d]" % n if shared else "[%d, D, %d]" % (B, n)))
+            if D is not None and a.shape[-2] != D:
+                raise ValueError("the dispersion arrays disagree on the number of flights")
+            D = a.shape[-2]
+        arrs.append(a)
+    par_true = None
+    if model is not None:
+        mdl = pbm.traj.mdl
+        true = type(mdl)(**{**mdl.opts, **model}) if isinstance(model, dict) else model
+        if type(true) is not type(mdl):
+            raise ValueError("the truth model is a %s, the problem's model a %s" % (type(true).__name__, type(mdl).__name__))
+        if hasattr(true, "bind"):
+            true.bind(pbm.pars)      # models whose constraints depend on the grid (Starship: phase-switch node)
+        par_true = np.ascontiguousarray(true.par(), dtype=np.float64)
+        assert par_true.size == pbm.info.npar
+    return arrs, (1 if D is None else D), (DISP_SHARED if shared else 0), par_true
+
+
+def audit_dispersed(sol, pbm, dx0=None, ugain=None, ubias=None, shared=False, model=None, pp=None, res=None, viol_tol=0.0, flights=False):
+    """Dispersed-flight audit of the batch solution `sol` (scp_audit_dispersed_batch_host): every problem is flown D times by the
+    single-shooting audit, flight d starting at xd[:, 0] + dx0[b, d] (physical units) and flying ugain[b, d] * u(t) + ubias[b, d]
+    -- arrays [B, D, nx] and [B, D, nu], or [D, .] with shared=True (every problem flies the same dispersions); None = 0, 1, 0,
+    and D = 1 when all three are None.  `model` = the truth model the flights are flown with: a model instance of the problem's
+    kind or a dict of constant overrides (None: the problem's own constants).  flights=True also returns the record of every
+    flight.  `sol.status` masks as in `audit`.  Returns a DispersedAuditBatch."""
+    L = _lib.lib()
+    xd = np.ascontiguousarray(sol.xd, dtype=np.float64)
+    ud = np.ascontiguousarray(sol.ud, dtype=np.float64)
+    p = np.ascontiguousarray(sol.p, dtype=np.float64)
+    B = xd.shape[0]
+    pp = np.ascontiguousarray(np.tile(pbm.traj.mdl.nominal_pp()[None], (B, 1)) if pp is None else pp, dtype=np.float64)
+    assert pp.shape[0] == B
+    res = _audit_res(pbm, res)
+    (dx0, ugain, ubias), D, flags, par_true = _dispersed_args(pbm, B, dx0, ugain, ubias, shared, model)
+    out = np.zeros((B, AUDIT_WIDTH))
+    recs = np.zeros((B, D, AUDIT_WIDTH)) if flights else None
+    sec = ctypes.c_double(0.0)
+    opt = lambda a: None if a is None else _ptr(a)      # noqa: E731
+    rc = L.scp_audit_dispersed_batch_host(pbm.handle, B, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np > 0 else None,
+                                          _ptr(pp) if pbm.info.npp > 0 else None, res, float(viol_tol), D, opt(dx0), opt(ugain),
+                                          opt(ubias), flags, opt(par_true), _ptr(out), opt(recs), ctypes.byref(sec))
+    _lib.check(rc, pbm.handle)
+    status = getattr(sol, "status", None)
+    if status is not None:
+        bad = ~np.array([str(st).startswith("SCP_SOLVED") for st in status])
+        out[bad] = np.nan
+        if flights:
+            recs[bad] = np.nan
+    a = DispersedAuditBatch(out, res, viol_tol, D, recs)
+    a.seconds = sec.value
+    return a
+
+
+def audit_dispersed_resident(pbm, dx0=None, ugain=None, ubias=None, shared=False, model=None, res=None, viol_tol=0.0, flights=False):
+    """The same for the batch RESIDENT in the handle (scp_audit_dispersed_resident): the trajectories the owning run's get_host
+    would return, its own pp, failed problems skipped by the kernels; the run is left untouched.  Returns a
+    DispersedAuditBatch."""
+    res = _audit_res(pbm, res)
+    B = getattr(pbm, "resident_B", None)
+    if B is None:
+        raise _lib.ScpError(1, "audit_dispersed_resident: no run has been started on this problem")
+    (dx0, ugain, ubias), D, flags, par_true = _dispersed_args(pbm, B, dx0, ugain, ubias, shared, model)
+    cap = max(pbm.batch_capacity, B)      # room for the library's own batch, whatever this module believes
+    out = np.zeros((cap, AUDIT_WIDTH))
+    recs = np.zeros((cap, D, AUDIT_WIDTH)) if flights else None
+    sec = ctypes.c_double(0.0)
+    opt = lambda a: None if a is None else _ptr(a)      # noqa: E731
+    _lib.check(_lib.lib().scp_audit_dispersed_resident(pbm.handle, res, float(viol_tol), D, opt(dx0), opt(ugain), opt(ubias), flags,
+                                                       opt(par_true), _ptr(out), opt(recs), ctypes.byref(sec)), pbm.handle)
+    a = DispersedAuditBatch(out[:B].copy(), res, viol_tol, D, recs[:B].copy() if flights else None)
+    a.seconds = sec.value
+    return a
+
+
 def device_guess(pbm, pp):
     """`traj.guess(N)` for a Monte-Carlo batch evaluated on the device (scp_guess_batch_host): pp[B,npp] ->
     (xd[B,N,nx], ud[B,N,nu], p[B,np])."""
