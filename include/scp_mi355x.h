@@ -381,6 +381,80 @@ int scp_model_audit_dispersed_host(int model_id, const double *model_par, const 
                                    double viol_tol, int D, const double *dx0, const double *ugain, const double *ubias,
                                    double *summary, double *flights /* [16, D] or NULL */);
 
+/*
+ * LQR gains on the discretisation.  discretize! leaves A_k, B-_k, B+_k of every interval of every problem on the device; a
+ * batched time-varying discrete LQR synthesis turns them into sample-and-hold tracking gains at the node rate.  FOH handles of
+ * the four auditable models.  For one problem, with Q = diag(qx), R = diag(ru) and P <- diag(qf), for k = N-1 down to 1:
+ *   Phi = A_k,  Gam = B-_k + B+_k            the exact map of an input deviation HELD over the interval
+ *   H = R + Gam' P Gam                        (Cholesky, nu <= 4)
+ *   K_k = H^-1 Gam' P Phi                     [nu, nx]
+ *   P <- Q + Phi' P (Phi - Gam K_k),  then P <- (P + P') / 2
+ * qx[nx] >= 0, qf[nx] >= 0, ru[nu] > 0 in physical units, shared by the batch.
+ *
+ * K[nu, nx, N-1, B] (column-major like every array here; may be NULL in the handle-level calls: the gains then stay on the device).
+ * info[SCP_LQR_INFO_WIDTH, B]:
+ *   [0]  1 when a pivot of H was <= 0 or anything was not finite; the K of that problem is then NaN throughout, [1], [2] too
+ *   [1]  max over k of max |K_k|
+ *   [2]  trace of P at node 1
+ *   [3]  0
+ * One wavefront lane per entry of P (nx^2 <= 64), floor(64 / nx^2) problems per wavefront; a problem's result does not depend on
+ * B or on its place in the batch, bit for bit.
+ *
+ * scp_lqr_gains_batch_host stages xd / ud / p like scp_audit_batch_host, runs discretize! into A / B- / B+ buffers the handle
+ * owns for this purpose (allocated on first use; SCP_ERR_ALLOC when they cannot be) and then the Riccati kernel.  The gains stay
+ * RESIDENT in the handle, together with the B they were made for, until the next gains call.  scp_lqr_gains_resident does the
+ * same about the trajectories the owning run's get_host would return; failed problems hold NaN in K and info; no buffer of the
+ * run is modified.  *seconds: discretize! and the Riccati kernel without the copies.
+ * SCP_ERR_BAD_ARGUMENT for a NULL, negative or non-finite weight (ru: also 0) and a NULL info; SCP_ERR_UNSUPPORTED (with an error
+ * text) for IMPULSE handles and models with node parameters; SCP_ERR_BATCH_TOO_LARGE as everywhere.
+ */
+#define SCP_LQR_INFO_WIDTH 4
+int scp_lqr_gains_batch_host(scp_handle h, int B, const double *xd, const double *ud, const double *p, const double *qx,
+                             const double *ru, const double *qf, double *K /* may be NULL */, double *info, double *seconds);
+int scp_lqr_gains_resident(scp_handle h, const double *qx, const double *ru, const double *qf, double *K /* may be NULL */,
+                           double *info, double *seconds);
+/*
+ * The same recursion for ONE problem on the host by the same code; no model enters it: A[nx,nx,N-1], Bm, Bp[nx,nu,N-1],
+ * K[nu,nx,N-1], info[SCP_LQR_INFO_WIDTH].  (nx, nu) is one of the pairs of the four auditable models -- (2,1), (6,4), (7,4),
+ * (8,3) -- SCP_ERR_UNSUPPORTED for any other.
+ */
+int scp_lqr_gains_host(int nx, int nu, int N, const double *A, const double *Bm, const double *Bp, const double *qx,
+                       const double *ru, const double *qf, double *K, double *info);
+
+/*
+ * Closed-loop tracking audit: the dispersed-flight audit with the loop closed by gains K[nu, nx, N-1, B] (scp_lqr_gains_*, or
+ * any others).  dx0 / ugain / ubias / SCP_DISP_SHARED / par_true, the masking, staging, ownership and the flights / summary
+ * buffers are those of scp_audit_dispersed_batch_host.  The sampling grid is steps >= 1 RK4 steps per interval,
+ * res = steps (N-1) + 1 samples at LinRange(0, 1, res): every step lies inside one interval, node k is sample (k-1) steps.
+ * One flight:
+ *   1. x = xd[:,1] + dx0; update the hold for k = 1; take sample 0
+ *   2. for j = 0 .. res-2: if j > 0 and j mod steps = 0 update the hold for k = j / steps + 1; take the RK4 step; take sample j+1
+ * The hold update is du = -K_k (x - xd[:,k]).  The commanded input at any time of the step, stage times included, is
+ * u_foh(t) + du; the flown input is ugain o (u_foh(t) + du) + ubias; the dynamics, the U rows, the cones and Gamma all see the
+ * flown input.  A sample at a node is audited with the hold that was in force over the step that ended there.  The commanded
+ * input is NOT saturated: the U rows and cones report what the feedback asked for.
+ *
+ * K: a host array, or NULL = the gains resident in the handle (SCP_ERR_BAD_ARGUMENT with an error text when there are none or
+ * they were made for another B).
+ * flights[SCP_AUDIT_WIDTH, D, B]: the single-shooting layout [0..11], and (strict >: the first occurrence wins a tie)
+ *   [12]  max over the hold updates of ||Su^-1 du||_inf, the feedback effort;  [13] the 1-based node attaining it
+ *   [14]  max over the nodes 1 .. N of ||Sx^-1 (x(t_k) - xd[:,k])||_inf;      [15] the node attaining it
+ * summary[SCP_AUDIT_WIDTH, B]: the fold of scp_audit_dispersed_batch_host over [0..11] of the flights, with [13] = 3.0.
+ * Refusals: those of the dispersed audit, and SCP_ERR_BAD_ARGUMENT for steps < 1.
+ */
+int scp_audit_tracking_batch_host(scp_handle h, int B, const double *xd, const double *ud, const double *p, const double *pp,
+                                  const double *K /* NULL = resident */, int steps, double viol_tol, int D, const double *dx0,
+                                  const double *ugain, const double *ubias, unsigned flags, const double *par_true,
+                                  double *summary, double *flights /* may be NULL */, double *seconds);
+int scp_audit_tracking_resident(scp_handle h, const double *K /* NULL = resident */, int steps, double viol_tol, int D,
+                                const double *dx0, const double *ugain, const double *ubias, unsigned flags,
+                                const double *par_true, double *summary, double *flights /* may be NULL */, double *seconds);
+/* The same two outputs for ONE problem on the host by the same code; Su[nu] scales the effort [12]; K[nu,nx,N-1] is required. */
+int scp_model_audit_tracking_host(int model_id, const double *model_par, const double *par_true, int N, const double *xd,
+                                  const double *ud, const double *p, const double *pp, const double *Sx, const double *Su,
+                                  const double *K, int steps, double viol_tol, int D, const double *dx0, const double *ugain,
+                                  const double *ubias, double *summary, double *flights /* [16, D] or NULL */);
+
 /* ------------------------------------------------------------------------ */
 /* PTR: solve_subproblem! and the outer loop                                  */
 /* ------------------------------------------------------------------------ */

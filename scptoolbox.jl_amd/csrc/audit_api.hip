@@ -1,7 +1,7 @@
 // The continuous-time audit's own translation unit: the four instantiations of audit_foh_kernel, the six of
-// audit_interval_kernel with their fold and the four of audit_dispersed_kernel with its fold (audit_kernel.hpp), their launches
-// for the handle-level entry points of scp_api.hip, and the pure-host twins scp_model_audit_host,
-// scp_model_audit_intervals_host and scp_model_audit_dispersed_host.
+// audit_interval_kernel with their fold, the four of audit_dispersed_kernel with its fold and the four of audit_tracking_kernel
+// with its fold (audit_kernel.hpp), their launches for the handle-level entry points of scp_api.hip, and the pure-host twins
+// scp_model_audit_host, scp_model_audit_intervals_host, scp_model_audit_dispersed_host and scp_model_audit_tracking_host.
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -96,6 +96,32 @@ int audit_dispersed_launch(int model_id, const double* model_par, const AuditDis
     });
 }
 
+// the tracking audit's fold: the dispersed fold over [0..11] of the flight records, marked 3.0
+__global__ __launch_bounds__(64) void audit_tracking_fold_kernel(AuditTrackingArgs a)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.B) return;
+    double* out = a.audit + (long)b * SCP_AUDIT_WIDTH;
+    if (a.mask != nullptr && a.mask[b] == 0) {
+#pragma unroll
+        for (int i = 0; i < SCP_AUDIT_WIDTH; i++) out[i] = NAN;
+        return;
+    }
+    audit_dispersed_fold(a.D, a.flights + (long)b * a.D * SCP_AUDIT_WIDTH, out, 3.0);
+}
+
+int audit_tracking_launch(int model_id, const double* model_par, const AuditTrackingArgs& a, hipStream_t stream)
+{
+    return with_audit_model(model_id, [&](auto m) -> int {
+        using M = decltype(m);
+        const dim3 grid((unsigned)(((long)a.B * a.D + 63) / 64)), block(64);
+        hipLaunchKernelGGL(audit_tracking_kernel<M>, grid, block, 0, stream, a, M::make_params(model_par));
+        if (hipGetLastError() != hipSuccess) return (int)SCP_ERR_HIP;
+        hipLaunchKernelGGL(audit_tracking_fold_kernel, dim3((a.B + 63) / 64), block, 0, stream, a);
+        return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+    });
+}
+
 }  // namespace scp
 
 extern "C" int scp_model_audit_host(int model_id, const double* model_par, int N, const double* xd, const double* ud,
@@ -154,6 +180,27 @@ extern "C" int scp_model_audit_dispersed_host(int model_id, const double* model_
                                         ugain ? ugain + (size_t)d * M::nu : nullptr, ubias ? ubias + (size_t)d * M::nu : nullptr,
                                         flights + (size_t)d * SCP_AUDIT_WIDTH);
         scp::audit_dispersed_fold(D, flights, summary);
+        return (int)SCP_OK;
+    });
+}
+
+extern "C" int scp_model_audit_tracking_host(int model_id, const double* model_par, const double* par_true, int N, const double* xd,
+                                             const double* ud, const double* p, const double* pp, const double* Sx, const double* Su,
+                                             const double* K, int steps, double viol_tol, int D, const double* dx0,
+                                             const double* ugain, const double* ubias, double* summary, double* flights)
+{
+    if (!model_par || N < 2 || !xd || !ud || !Sx || !Su || !K || !summary || steps < 1 || D < 1) return SCP_ERR_BAD_ARGUMENT;
+    return scp::with_audit_model(model_id, [&](auto m) -> int {
+        using M = decltype(m);
+        if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
+        const typename M::Params par = M::make_params(par_true ? par_true : model_par);
+        std::vector<double> own;
+        if (!flights) { own.resize((size_t)SCP_AUDIT_WIDTH * D); flights = own.data(); }
+        for (int d = 0; d < D; d++)
+            scp::audit_tracking_one<M>(par, N, steps, viol_tol, xd, ud, p, pp, Sx, Su, K, dx0 ? dx0 + (size_t)d * M::nx : nullptr,
+                                       ugain ? ugain + (size_t)d * M::nu : nullptr, ubias ? ubias + (size_t)d * M::nu : nullptr,
+                                       flights + (size_t)d * SCP_AUDIT_WIDTH);
+        scp::audit_dispersed_fold(D, flights, summary, 3.0);
         return (int)SCP_OK;
     });
 }

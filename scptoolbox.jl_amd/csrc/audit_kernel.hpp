@@ -604,7 +604,8 @@ SCP_DEV void audit_dispersed_one(const typename M::Params& par, int N, int res, 
 // The ordered fold of the D flight records recs[SCP_AUDIT_WIDTH, D] of ONE problem into out[SCP_AUDIT_WIDTH].  A flight whose
 // record [11] != 0 is counted in [11] and takes no part in any other field.  Strict comparisons from -Inf: the first flight wins
 // a tie.  [6] is that of the first counted flight (-Inf when none is counted); the mean cost is (((c_1 + c_2) + ...) + c_m) / m.
-SCP_DEV void audit_dispersed_fold(int D, const double* recs, double* out)
+// `marker` is what [13] holds: 2.0 for the dispersed audit, 3.0 for the tracking audit.
+SCP_DEV void audit_dispersed_fold(int D, const double* recs, double* out, double marker = 2.0)
 {
     double vmax[3] = {-INFINITY, -INFINITY, -INFINITY}, dmax[3] = {0.0, 0.0, 0.0};
     double par_max = -INFINITY, bc = -INFINITY, dbc = 0.0, drift = -INFINITY, sum = 0.0, cmax = -INFINITY, n_viol = 0.0, n_bad = 0.0;
@@ -625,7 +626,7 @@ SCP_DEV void audit_dispersed_fold(int D, const double* recs, double* out)
     }
     out[0] = vmax[0]; out[1] = dmax[0]; out[2] = vmax[1]; out[3] = dmax[1]; out[4] = vmax[2]; out[5] = dmax[2];
     out[6] = par_max; out[7] = m > 0 ? bc : NAN; out[8] = m > 0 ? drift : NAN; out[9] = m > 0 ? sum / (double)m : NAN;
-    out[10] = n_viol; out[11] = n_bad; out[12] = dbc; out[13] = 2.0; out[14] = (double)D; out[15] = m > 0 ? cmax : NAN;
+    out[10] = n_viol; out[11] = n_bad; out[12] = dbc; out[13] = marker; out[14] = (double)D; out[15] = m > 0 ? cmax : NAN;
 }
 
 // one thread per (problem, flight), gid = b D + (d - 1), blocks of one wavefront: the mapping of audit_interval_kernel.
@@ -647,6 +648,189 @@ __global__ __launch_bounds__(64) void audit_dispersed_kernel(AuditDispersedArgs 
                            a.p + (long)b * np_total<M>(a.N), a.pp + (long)b * M::npp, a.Sx,
                            a.dx0 != nullptr ? a.dx0 + col * M::nx : nullptr, a.ugain != nullptr ? a.ugain + col * M::nu : nullptr,
                            a.ubias != nullptr ? a.ubias + col * M::nu : nullptr, rec);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Closed-loop tracking audit (scp_audit_tracking_*): the dispersed flight with the loop closed by sample-and-hold gains
+// K[nu,nx,N-1] at the node rate (lqr_kernel.hpp, or any others).  The samples are `steps` RK4 steps per interval,
+// res = steps (N-1) + 1 at LinRange(0, 1, res), so that every step lies inside one interval and node k is sample (k-1) steps by
+// integer arithmetic.  One flight:
+//   1. x = xd[:,1] + dx0; hold update for k = 1; sample 0
+//   2. for j = 0 .. res-2: if j > 0 and j mod steps == 0 hold update for k = j / steps + 1; RK4 step; sample j+1
+// hold update: du = -K_k (x - xd[:,k]).  Commanded input u_foh(t) + du, flown input ugain o (u_foh(t) + du) + ubias at every time,
+// stage times included; dynamics, U rows, cones and Gamma see the flown input.  A sample at a node is audited with the hold that
+// was in force over the step that ended there.  Records [0..11] as audit_dispersed_one; [12], [13] the largest ||Su^-1 du||_inf
+// over the hold updates and its node, [14], [15] the largest ||Sx^-1 (x(t_k) - xd[:,k])||_inf over the nodes 1 .. N and its node
+// (strict >: the first wins).  With K = 0 the flight is audit_dispersed_one's at the same res.
+// audit_dispersed_one is not touched: the tracking flight is a body of its own.
+// ------------------------------------------------------------------------------------------------
+struct AuditTrackingArgs {
+    int B, N, steps, D;
+    int shared;          // as AuditDispersedArgs
+    double viol_tol;
+    const double* xd;    // [nx,N,B]
+    const double* ud;    // [nu,N,B]
+    const double* p;     // [np,B]
+    const double* pp;    // [npp,B]
+    const double* Sx;    // [nx]
+    const double* Su;    // [nu]
+    const double* K;     // [nu,nx,N-1,B]
+    const double* dx0;   // [nx,D,B] or [nx,D]; nullptr = 0
+    const double* ugain; // [nu,D,B] or [nu,D]; nullptr = 1
+    const double* ubias; // [nu,D,B] or [nu,D]; nullptr = 0
+    const int* mask;     // optional [B]
+    double* flights;     // [SCP_AUDIT_WIDTH,D,B]
+    double* audit;       // [SCP_AUDIT_WIDTH,B]
+};
+
+// audit_api.hip: audit_tracking_kernel<M> then audit_tracking_fold_kernel on `stream`; model_par is the blob the flights fly with
+int audit_tracking_launch(int model_id, const double* model_par, const AuditTrackingArgs& a, hipStream_t stream);
+
+// ONE flight of ONE problem: xd[nx,N], ud[nu,N], p[np], pp[npp], Sx[nx], Su[nu], K[nu,nx,N-1], dx0[nx], gain[nu], bias[nu] (each of
+// the last three may be nullptr) -> out[SCP_AUDIT_WIDTH]
+template <class M>
+SCP_DEV void audit_tracking_one(const typename M::Params& par, int N, int steps, double viol_tol, const double* xd, const double* ub,
+                                const double* pb, const double* pp, const double* Sx, const double* Su, const double* Kg,
+                                const double* dx0, const double* gain, const double* bias, double* out)
+{
+    static_assert(M::np_node == 0, "a row of node k would read that node's own parameters: undefined between the nodes");
+    constexpr int nx = M::nx, nu = M::nu, np = M::np, npa = np > 0 ? np : 1, npF = M::npF, npFa = npF > 0 ? npF : 1, ng = M::ng;
+    const int res = steps * (N - 1) + 1;
+
+    double x[nx], ug[nu], ubs[nu], du[nu];
+#pragma unroll
+    for (int i = 0; i < nx; i++) x[i] = xd[i] + (dx0 != nullptr ? dx0[i] : 0.0);
+#pragma unroll
+    for (int i = 0; i < nu; i++) { ug[i] = gain != nullptr ? gain[i] : 1.0; ubs[i] = bias != nullptr ? bias[i] : 0.0; du[i] = 0.0; }
+    // u'(t): the first-order hold of audit_one (same clamp, same interval search) plus the held feedback, then gain and bias
+    auto input = [&](double t, double (&u)[nu]) {
+        const double g0 = audit_linrange(0.0, 1.0, N, 0), g1 = audit_linrange(0.0, 1.0, N, N - 1);
+        t = fmax(g0, fmin(g1, t));
+        int k = (int)floor(t * (N - 1));
+        k = k < 0 ? 0 : (k > N ? N : k);
+        while (k < N && t > audit_linrange(0.0, 1.0, N, k)) k++;
+        while (k > 0 && !(t > audit_linrange(0.0, 1.0, N, k - 1))) k--;
+        if (k == 0) k = 1;
+        const double ta = audit_linrange(0.0, 1.0, N, k - 1), tb = audit_linrange(0.0, 1.0, N, k);
+        const double c = (tb - t) / (tb - ta);
+#pragma unroll
+        for (int i = 0; i < nu; i++) u[i] = ug[i] * ((c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i]) + du[i]) + ubs[i];
+    };
+    auto f = [&](double t, const double (&xs)[nx], double (&fx)[nx]) {
+        double u[nu], Am[nx * nx], Bmat[nx * nu], Fc[nx * npFa];
+        input(t, u);
+        M::dyn(par, t, N, xs, u, pb, fx, Am, Bmat, Fc);   // only f survives dead-code elimination
+    };
+
+    double Qu[nu], lu[nu], lx[nx], tx[nx], ctp[npa], cQp[npa];
+#pragma unroll
+    for (int i = 0; i < npa; i++) { ctp[i] = 0.0; cQp[i] = 0.0; }
+    M::cost_terms(par, Qu, lu, lx, tx, ctp, cQp);
+
+    AuditAcc acc;
+    double gam_prev = 0.0, cost_int = 0.0;
+    double effort = -INFINITY, k_effort = 0.0, track = -INFINITY, k_track = 0.0;
+    auto sample = [&](double t) -> double {
+        // 1-based index of the last grid node <= t, decided against the exact grid values (N at t = 1)
+        int k = (int)floor(t * (N - 1)) + 1;
+        k = k < 1 ? 1 : (k > N ? N : k);
+        while (k < N && !(audit_linrange(0.0, 1.0, N, k) > t)) k++;
+        while (k > 1 && audit_linrange(0.0, 1.0, N, k - 1) > t) k--;
+        double u[nu];
+        input(t, u);
+        return audit_sample<M>(par, t, k, x, u, pb, viol_tol, Qu, lu, lx, acc);
+    };
+    // at node k (1-based): the tracking error of the state as it is, and for k < N the new hold from it
+    auto node = [&](int k) {
+        const double* xk = xd + (long)(k - 1) * nx;
+        double e[nx], terr = 0.0;
+#pragma unroll
+        for (int i = 0; i < nx; i++) {
+            e[i] = x[i] - xk[i];
+            const double d = e[i] / Sx[i];
+            acc.bad = acc.bad || !__builtin_isfinite(d);
+            terr = fmax(terr, fabs(d));
+        }
+        if (terr > track) { track = terr; k_track = (double)k; }
+        if (k < N) {
+            const double* Kk = Kg + (long)(k - 1) * nu * nx;
+            double eff = 0.0;
+#pragma unroll
+            for (int a = 0; a < nu; a++) {
+                double s = 0.0;
+#pragma unroll
+                for (int i = 0; i < nx; i++) s += Kk[a + nu * i] * e[i];
+                du[a] = -s;
+                const double d = du[a] / Su[a];
+                acc.bad = acc.bad || !__builtin_isfinite(d);
+                eff = fmax(eff, fabs(d));
+            }
+            if (eff > effort) { effort = eff; k_effort = (double)k; }
+        }
+    };
+
+    node(1);
+    gam_prev = sample(audit_linrange(0.0, 1.0, res, 0));
+    for (int j = 1; j < res; j++) {
+        if (j > 1 && (j - 1) % steps == 0) node((j - 1) / steps + 1);
+        const double t = audit_linrange(0.0, 1.0, res, j - 1), tp = audit_linrange(0.0, 1.0, res, j), h = tp - t;
+        double k1[nx], k2[nx], k3[nx], k4[nx], tmp[nx];
+        f(t, x, k1);
+#pragma unroll
+        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h / 2 * k1[i];
+        f(t + h / 2, tmp, k2);
+#pragma unroll
+        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h / 2 * k2[i];
+        f(t + h / 2, tmp, k3);
+#pragma unroll
+        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h * k3[i];
+        f(t + h, tmp, k4);
+#pragma unroll
+        for (int i = 0; i < nx; i++) x[i] = x[i] + h / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+        M::action(x);
+        const double gam = sample(tp);
+        cost_int += 0.5 * h * (gam + gam_prev);
+        gam_prev = gam;
+    }
+    node(N);
+
+    // ---- quantities of the end point and of the parameters alone; the drift against the UNDISPERSED last node ----
+    const double par_max = audit_par_max<M>(par, pb);
+    const double bc = audit_bc_tc<M>(par, x, pb, pp, acc.bad);
+    double drift = 0.0;
+#pragma unroll
+    for (int i = 0; i < nx; i++) {
+        const double d = (x[i] - xd[(long)(N - 1) * nx + i]) / Sx[i];
+        acc.bad = acc.bad || !__builtin_isfinite(d);
+        drift = fmax(drift, fabs(d));
+    }
+    const double phi = audit_phi<M>(x, pb, tx, ctp, cQp);
+    const double cost = phi + cost_int;
+    acc.bad = acc.bad || !__builtin_isfinite(cost) || (ng > 0 && !__builtin_isfinite(par_max));
+
+    out[0] = acc.s_max; out[1] = acc.t_s; out[2] = acc.l_max; out[3] = acc.t_l; out[4] = acc.c_max; out[5] = acc.t_c;
+    out[6] = par_max; out[7] = bc; out[8] = drift; out[9] = cost; out[10] = acc.n_viol; out[11] = acc.bad ? 1.0 : 0.0;
+    out[12] = effort; out[13] = k_effort; out[14] = track; out[15] = k_track;
+}
+
+// one thread per (problem, flight), gid = b D + (d - 1): the mapping of audit_dispersed_kernel
+template <class M>
+__global__ __launch_bounds__(64) void audit_tracking_kernel(AuditTrackingArgs a, typename M::Params par)
+{
+    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    if (gid >= (long)a.B * a.D) return;
+    const int b = (int)(gid / a.D);
+    double* rec = a.flights + gid * SCP_AUDIT_WIDTH;
+    if (a.mask != nullptr && a.mask[b] == 0) {
+#pragma unroll
+        for (int i = 0; i < SCP_AUDIT_WIDTH; i++) rec[i] = NAN;
+        return;
+    }
+    const long col = a.shared ? gid % a.D : gid;          // the flight's column of the dispersion arrays
+    audit_tracking_one<M>(par, a.N, a.steps, a.viol_tol, a.xd + (long)b * a.N * M::nx, a.ud + (long)b * a.N * M::nu,
+                          a.p + (long)b * np_total<M>(a.N), a.pp + (long)b * M::npp, a.Sx, a.Su, a.K + (long)b * (a.N - 1) * M::nu * M::nx,
+                          a.dx0 != nullptr ? a.dx0 + col * M::nx : nullptr, a.ugain != nullptr ? a.ugain + col * M::nu : nullptr,
+                          a.ubias != nullptr ? a.ubias + col * M::nu : nullptr, rec);
 }
 
 }  // namespace scp

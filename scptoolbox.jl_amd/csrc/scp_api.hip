@@ -10,6 +10,7 @@
 
 #include "scp_handle.hpp"
 #include "audit_kernel.hpp"
+#include "lqr_kernel.hpp"
 #include "discretize_kernel.hpp"
 
 using namespace scp;
@@ -310,6 +311,13 @@ extern "C" int scp_problem_set_model_par(scp_handle h, const double* model_par)
     return SCP_OK;
 }
 
+// every device buffer of h->lqr
+static std::vector<void*> lqr_buffers(scp_problem* h)
+{
+    scp_problem::Lqr& q = h->lqr;
+    return {q.dyn.A, q.dyn.Bm, q.dyn.Bp, q.dyn.F, q.dyn.r, q.dyn.E, q.dyn.defect, q.feas, q.K, q.Kin, q.info, q.w};
+}
+
 extern "C" int scp_problem_destroy(scp_handle h)
 {
     if (!h) return SCP_ERR_BAD_ARGUMENT;
@@ -317,6 +325,8 @@ extern "C" int scp_problem_destroy(scp_handle h)
     if (h->guess.sg) starship_guess_free(h->guess.sg);
     for (void* p : h->allocs) (void)hipFree(p);
     for (double* p : {h->audit.flights, h->audit.dx0, h->audit.ugain, h->audit.ubias})
+        if (p) (void)hipFree(p);
+    for (void* p : lqr_buffers(h))
         if (p) (void)hipFree(p);
     for (auto& st : h->timing.stamps_free) { (void)hipEventDestroy(st.a); (void)hipEventDestroy(st.b); }
     for (auto& st : h->timing.stamps_pending) { (void)hipEventDestroy(st.a); (void)hipEventDestroy(st.b); }
@@ -767,4 +777,169 @@ extern "C" int scp_audit_dispersed_resident(scp_handle h, int res, double viol_t
     TRY(audit_resident_source(h, "scp_audit_dispersed_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
     return audit_dispersed_run(h, src.B, src.tr, src.d_pp, h->audit.mask, res, viol_tol, D, dx0, ugain, ubias, flags, par_true, summary,
                                flights, seconds);
+}
+
+// ------------------------------------------------------------------------------------------
+// LQR gains on the discretisation (lqr_kernel.hpp; the kernels live in lqr_api.hip) and the closed-loop tracking audit
+// ------------------------------------------------------------------------------------------
+
+// the buffers of h->lqr but Kin for every problem the handle can hold: all or none
+static int lqr_reserve(scp_problem* h)
+{
+    scp_problem::Lqr& q = h->lqr;
+    if (q.K) return SCP_OK;
+    const size_t nx = h->info.nx, nu = h->info.nu, npF = h->info.npF > 0 ? h->info.npF : 1, M = h->N - 1, cap = h->cap, D = sizeof(double);
+    const bool ok = hipMalloc((void**)&q.dyn.A, nx * nx * M * cap * D) == hipSuccess && hipMalloc((void**)&q.dyn.Bm, nx * nu * M * cap * D) == hipSuccess &&
+                    hipMalloc((void**)&q.dyn.Bp, nx * nu * M * cap * D) == hipSuccess && hipMalloc((void**)&q.dyn.F, nx * npF * M * cap * D) == hipSuccess &&
+                    hipMalloc((void**)&q.dyn.r, nx * M * cap * D) == hipSuccess && hipMalloc((void**)&q.dyn.E, nx * nx * M * cap * D) == hipSuccess &&
+                    hipMalloc((void**)&q.dyn.defect, nx * M * cap * D) == hipSuccess && hipMalloc((void**)&q.feas, cap * sizeof(int)) == hipSuccess &&
+                    hipMalloc((void**)&q.info, SCP_LQR_INFO_WIDTH * cap * D) == hipSuccess &&
+                    hipMalloc((void**)&q.w, (2 * nx + nu) * D) == hipSuccess && hipMalloc((void**)&q.K, nu * nx * M * cap * D) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (void** p : {(void**)&q.dyn.A, (void**)&q.dyn.Bm, (void**)&q.dyn.Bp, (void**)&q.dyn.F, (void**)&q.dyn.r, (void**)&q.dyn.E,
+                         (void**)&q.dyn.defect, (void**)&q.feas, (void**)&q.info, (void**)&q.w, (void**)&q.K}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        h->err = "lqr: the discretisation and gain buffers could not be allocated";
+        return SCP_ERR_ALLOC;
+    }
+    return SCP_OK;
+}
+
+// what both gains entry points refuse (the audit's refusals, and the weights)
+static int lqr_begin(scp_problem* h, const double* qx, const double* ru, const double* qf, const double* info)
+{
+    TRY(audit_begin(h, 2, info));
+    if (!lqr_weights_ok(h->info.nx, h->info.nu, qx, ru, qf)) {
+        h->err = "lqr: qx >= 0, qf >= 0 and ru > 0, all finite, are required";
+        return SCP_ERR_BAD_ARGUMENT;
+    }
+    return lqr_reserve(h);
+}
+
+// discretize! about `tr` into the buffers of h->lqr and the Riccati kernel between the handle's two events, then the copies
+static int lqr_run(scp_problem* h, int B, const Traj& tr, const int* mask, const double* qx, const double* ru, const double* qf,
+                   double* K, double* info, double* seconds)
+{
+    scp_problem::Lqr& q = h->lqr;
+    const size_t nx = h->info.nx, nu = h->info.nu;
+    q.B = 0;
+    std::vector<double> w(2 * nx + nu);
+    std::copy(qx, qx + nx, w.begin()); std::copy(ru, ru + nu, w.begin() + nx); std::copy(qf, qf + nx, w.begin() + nx + nu);
+    HIP_TRY(h, hipMemcpyAsync(q.w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
+    TRY(discretize_dev(h, B, tr.xd, tr.ud, tr.p, q.dyn, q.feas, mask));
+    LqrArgs a;
+    a.B = B; a.N = h->N; a.A = q.dyn.A; a.Bm = q.dyn.Bm; a.Bp = q.dyn.Bp; a.qx = q.w; a.ru = q.w + nx; a.qf = q.w + nx + nu; a.mask = mask;
+    a.K = q.K; a.info = q.info;
+    const int rc = lqr_launch((int)nx, (int)nu, a, h->stream);
+    if (rc != SCP_OK) { h->err = "lqr: kernel launch failed"; return rc; }
+    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(info, q.info, sizeof(double) * SCP_LQR_INFO_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    if (K) HIP_TRY(h, hipMemcpyAsync(K, q.K, sizeof(double) * nu * nx * (size_t)(h->N - 1) * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // w is on this stack frame
+    stamps_collect(h);
+    q.B = B;
+    return elapsed_out(h, seconds);
+}
+
+extern "C" int scp_lqr_gains_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* qx,
+                                        const double* ru, const double* qf, double* K, double* info, double* seconds)
+{
+    TRY(lqr_begin(h, qx, ru, qf, info));
+    if (B < 1 || !xd || !ud || (h->npt > 0 && !p)) { h->err = "lqr: missing input"; return SCP_ERR_BAD_ARGUMENT; }
+    if (B > h->cap) { h->err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
+    TRY(upload_traj(h, B, xd, ud, p, h->traj.sol_xd, h->traj.sol_ud, h->traj.sol_p));
+    return lqr_run(h, B, traj_sol(h), nullptr, qx, ru, qf, K, info, seconds);
+}
+
+extern "C" int scp_lqr_gains_resident(scp_handle h, const double* qx, const double* ru, const double* qf, double* K, double* info,
+                                      double* seconds)
+{
+    TRY(lqr_begin(h, qx, ru, qf, info));
+    AuditSource src;
+    TRY(audit_resident_source(h, "scp_lqr_gains_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
+    return lqr_run(h, src.B, src.tr, h->audit.mask, qx, ru, qf, K, info, seconds);
+}
+
+static int audit_tracking_begin(scp_problem* h, int steps, int D, unsigned flags, const double* summary)
+{
+    TRY(audit_dispersed_begin(h, 2, D, flags, summary));
+    if (steps < 1) { h->err = "audit: steps >= 1 is required"; return SCP_ERR_BAD_ARGUMENT; }
+    return SCP_OK;
+}
+
+// the gains of the call on the device: the caller's, staged, or the resident ones when they were made for this B
+static int audit_tracking_gains(scp_problem* h, int B, const double* K, const double** d_K)
+{
+    if (K) {
+        if (!h->lqr.Kin && hipMalloc((void**)&h->lqr.Kin, sizeof(double) * h->info.nu * h->info.nx * (size_t)(h->N - 1) * (size_t)h->cap) != hipSuccess) {
+            (void)hipGetLastError();
+            h->lqr.Kin = nullptr;
+            h->err = "audit: the buffer of the gains passed by the caller could not be allocated";
+            return SCP_ERR_ALLOC;
+        }
+        HIP_TRY(h, hipMemcpyAsync(h->lqr.Kin, K, sizeof(double) * h->info.nu * h->info.nx * (size_t)(h->N - 1) * (size_t)B, hipMemcpyHostToDevice, h->stream));
+        *d_K = h->lqr.Kin;
+        return SCP_OK;
+    }
+    if (h->lqr.B == 0) { h->err = "audit: K is NULL and the handle holds no gains; call scp_lqr_gains_batch_host or scp_lqr_gains_resident first"; return SCP_ERR_BAD_ARGUMENT; }
+    if (h->lqr.B != B) {
+        h->err = "audit: K is NULL and the resident gains were made for B = " + std::to_string(h->lqr.B) + ", not " + std::to_string(B);
+        return SCP_ERR_BAD_ARGUMENT;
+    }
+    *d_K = h->lqr.K;
+    return SCP_OK;
+}
+
+static int audit_tracking_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, const double* K, int steps,
+                              double viol_tol, int D, const double* dx0, const double* ugain, const double* ubias, unsigned flags,
+                              const double* par_true, double* summary, double* flights, double* seconds)
+{
+    const double* d_K = nullptr;
+    TRY(audit_tracking_gains(h, B, K, &d_K));
+    TRY(audit_dispersed_reserve(h, D));
+    const bool shared = (flags & SCP_DISP_SHARED) != 0u;
+    const size_t cols = shared ? (size_t)D : (size_t)D * (size_t)B;
+    if (dx0) HIP_TRY(h, hipMemcpyAsync(h->audit.dx0, dx0, sizeof(double) * h->info.nx * cols, hipMemcpyHostToDevice, h->stream));
+    if (ugain) HIP_TRY(h, hipMemcpyAsync(h->audit.ugain, ugain, sizeof(double) * h->info.nu * cols, hipMemcpyHostToDevice, h->stream));
+    if (ubias) HIP_TRY(h, hipMemcpyAsync(h->audit.ubias, ubias, sizeof(double) * h->info.nu * cols, hipMemcpyHostToDevice, h->stream));
+    AuditTrackingArgs a;
+    a.B = B; a.N = h->N; a.steps = steps; a.D = D; a.shared = shared ? 1 : 0; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
+    a.pp = d_pp; a.Sx = h->d_Sx; a.Su = h->d_Su; a.K = d_K; a.dx0 = dx0 ? h->audit.dx0 : nullptr; a.ugain = ugain ? h->audit.ugain : nullptr;
+    a.ubias = ubias ? h->audit.ubias : nullptr; a.mask = mask; a.flights = h->audit.flights; a.audit = h->audit.rec;
+    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
+    const int rc = audit_tracking_launch(h->model_id, par_true ? par_true : h->par.data(), a, h->stream);
+    if (rc != SCP_OK) { h->err = "audit: kernel launch failed"; return rc; }
+    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(summary, h->audit.rec, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    if (flights)
+        HIP_TRY(h, hipMemcpyAsync(flights, h->audit.flights, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)D * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    stamps_collect(h);
+    return elapsed_out(h, seconds);
+}
+
+extern "C" int scp_audit_tracking_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
+                                             const double* K, int steps, double viol_tol, int D, const double* dx0, const double* ugain,
+                                             const double* ubias, unsigned flags, const double* par_true, double* summary,
+                                             double* flights, double* seconds)
+{
+    TRY(audit_tracking_begin(h, steps, D, flags, summary));
+    TRY(audit_stage_host(h, B, xd, ud, p, pp));
+    return audit_tracking_run(h, B, traj_sol(h), h->audit.pp, nullptr, K, steps, viol_tol, D, dx0, ugain, ubias, flags, par_true, summary,
+                              flights, seconds);
+}
+
+extern "C" int scp_audit_tracking_resident(scp_handle h, const double* K, int steps, double viol_tol, int D, const double* dx0,
+                                           const double* ugain, const double* ubias, unsigned flags, const double* par_true,
+                                           double* summary, double* flights, double* seconds)
+{
+    TRY(audit_tracking_begin(h, steps, D, flags, summary));
+    AuditSource src;
+    TRY(audit_resident_source(h, "scp_audit_tracking_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
+    return audit_tracking_run(h, src.B, src.tr, src.d_pp, h->audit.mask, K, steps, viol_tol, D, dx0, ugain, ubias, flags, par_true, summary,
+                              flights, seconds);
 }

@@ -1,6 +1,6 @@
 // The problem handle of the C-ABI library (include/scp_mi355x.h) as its translation units share it: internal, not installed.
 //
-//   scp_api.hip      model queries, handle life cycle, kernel time stamps, discretize! and propagate (K1), scp_audit_*
+//   scp_api.hip      model queries, handle life cycle, kernel time stamps, discretize! and propagate (K1), scp_audit_*, scp_lqr_gains_*
 //   ptr_api.hip      structured PTR path (K2-K4)
 //   guess_api.hip    initial guesses (every model's straight line, the Starship reference guess)
 //   scp_generic.hip  subproblem handles (scp_sub) and the SCvx / GuSTO / generic-PTR loops
@@ -88,6 +88,18 @@ struct scp_problem {
         double *flights = nullptr, *dx0 = nullptr, *ugain = nullptr, *ubias = nullptr;
         int disp_D = 0;
     } audit;
+
+    // ---- scp_api.hip: LQR gains (scp_lqr_gains_*) and the gains a tracking audit is handed (scp_audit_tracking_*).  dyn / feas:
+    // a discretisation of its own, so that no run's buffer is written; K [nu nx (N-1) cap] the resident gains, made for batch B
+    // (0 = none); Kin the same size for gains passed by the caller; info [SCP_LQR_INFO_WIDTH cap]; w = qx [nx], ru [nu], qf [nx].
+    // Built on first use (Kin by the first tracking audit that is handed gains, the rest together by the first gains call), not in
+    // h->allocs: scp_problem_destroy frees them ----
+    struct Lqr {
+        DynBuf dyn;
+        int* feas = nullptr;
+        double *K = nullptr, *Kin = nullptr, *info = nullptr, *w = nullptr;
+        int B = 0;
+    } lqr;
 
     // ---- trajectories: allocated by scp_api.hip at create; written by the run that owns them (h->run: ptr_api.hip or
     // scp_generic.hip) and, between runs, by the stand-alone entry points of every unit (sol_* as their staging buffers) ----

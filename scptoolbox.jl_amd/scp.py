@@ -545,6 +545,178 @@ def audit_dispersed_resident(pbm, dx0=None, ugain=None, ubias=None, shared=False
     return a
 
 
+LQR_INFO_WIDTH = 4      # SCP_LQR_INFO_WIDTH
+
+
+class GainBatch:
+    """Time-varying LQR gains of a batch (scp_lqr_gains_batch_host / scp_lqr_gains_resident, include/scp_mi355x.h): `K`
+    [B, N-1, nu, nx], the hold of interval k is du = -K[b, k] (x - xd[b, k]); `failed` [B] = a pivot <= 0 or a non-finite value
+    (the K of that problem is NaN), `k_max` = the largest |K| entry, `trace_p` = the trace of the cost-to-go at the first node.
+    Skipped (failed SCP) problems hold NaN everywhere.  `raw` [B, N-1, nx, nu] is the library's own layout, `info` [B, 4]."""
+
+    def __init__(self, raw, info, qx, ru, qf):
+        self.raw = np.ascontiguousarray(raw, dtype=np.float64)
+        assert self.raw.ndim == 4
+        self.K = self.raw.transpose(0, 1, 3, 2)
+        self.info = np.ascontiguousarray(info, dtype=np.float64).reshape(-1, LQR_INFO_WIDTH)
+        assert self.info.shape[0] == self.raw.shape[0]
+        self.qx, self.ru, self.qf = (np.asarray(a, dtype=np.float64) for a in (qx, ru, qf))
+        self.k_max, self.trace_p = self.info[:, 1], self.info[:, 2]
+        self.seconds = 0.0
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    @property
+    def failed(self):
+        return self.info[:, 0] == 1.0
+
+    @property
+    def skipped(self):
+        return np.isnan(self.info[:, 0])
+
+
+def _lqr_weights(pbm, qx, ru, qf):
+    """Bryson's rule from the handle's scaling where a weight is None: qx = 1 / Sx^2, ru = 1 / Su^2, qf = 10 / Sx^2"""
+    qx = 1.0 / pbm.scale.Sx ** 2 if qx is None else qx
+    ru = 1.0 / pbm.scale.Su ** 2 if ru is None else ru
+    qf = 10.0 / pbm.scale.Sx ** 2 if qf is None else qf
+    qx, ru, qf = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (qx, ru, qf))
+    if qx.size != pbm.nx or qf.size != pbm.nx or ru.size != pbm.nu:
+        raise ValueError("qx and qf hold nx = %d weights, ru nu = %d" % (pbm.nx, pbm.nu))
+    return qx, ru, qf
+
+
+def lqr_gains(sol, pbm, qx=None, ru=None, qf=None):
+    """Sample-and-hold LQR tracking gains about the batch solution `sol` (scp_lqr_gains_batch_host): discretize! about it and the
+    discrete Riccati recursion on the device.  qx[nx], ru[nu], qf[nx] weigh state, input and final state in physical units
+    (None: Bryson's rule from the problem's scaling).  The gains also stay resident in the handle for `audit_tracking`.
+    `sol.status` masks as in `audit`.  Returns a GainBatch."""
+    xd = np.ascontiguousarray(sol.xd, dtype=np.float64)
+    ud = np.ascontiguousarray(sol.ud, dtype=np.float64)
+    p = np.ascontiguousarray(sol.p, dtype=np.float64)
+    B, N = xd.shape[0], pbm.pars.N
+    qx, ru, qf = _lqr_weights(pbm, qx, ru, qf)
+    raw, info = np.zeros((B, N - 1, pbm.nx, pbm.nu)), np.zeros((B, LQR_INFO_WIDTH))
+    sec = ctypes.c_double(0.0)
+    rc = _lib.lib().scp_lqr_gains_batch_host(pbm.handle, B, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np > 0 else None, _ptr(qx), _ptr(ru),
+                                            _ptr(qf), _ptr(raw), _ptr(info), ctypes.byref(sec))
+    _lib.check(rc, pbm.handle)
+    status = getattr(sol, "status", None)
+    if status is not None:
+        bad = ~np.array([str(st).startswith("SCP_SOLVED") for st in status])
+        raw[bad] = np.nan
+        info[bad] = np.nan
+    g = GainBatch(raw, info, qx, ru, qf)
+    g.seconds = sec.value
+    return g
+
+
+def lqr_gains_resident(pbm, qx=None, ru=None, qf=None):
+    """The same about the batch RESIDENT in the handle (scp_lqr_gains_resident): the trajectories the owning run's get_host would
+    return, failed problems NaN; the run is left untouched.  Returns a GainBatch."""
+    B, N = getattr(pbm, "resident_B", None), pbm.pars.N
+    if B is None:
+        raise _lib.ScpError(1, "lqr_gains_resident: no run has been started on this problem")
+    qx, ru, qf = _lqr_weights(pbm, qx, ru, qf)
+    cap = max(pbm.batch_capacity, B)      # room for the library's own batch, whatever this module believes
+    raw, info = np.zeros((cap, N - 1, pbm.nx, pbm.nu)), np.zeros((cap, LQR_INFO_WIDTH))
+    sec = ctypes.c_double(0.0)
+    _lib.check(_lib.lib().scp_lqr_gains_resident(pbm.handle, _ptr(qx), _ptr(ru), _ptr(qf), _ptr(raw), _ptr(info), ctypes.byref(sec)), pbm.handle)
+    g = GainBatch(raw[:B].copy(), info[:B].copy(), qx, ru, qf)
+    g.seconds = sec.value
+    return g
+
+
+class TrackingAuditBatch(DispersedAuditBatch):
+    """The closed-loop tracking audit of a batch (scp_audit_tracking_batch_host / scp_audit_tracking_resident): a
+    DispersedAuditBatch whose flights were flown with `steps` RK4 steps per interval under sample-and-hold feedback.  Where the
+    flight records are present, views [B, D] of them: `effort` = the largest ||Su^-1 du||_inf over the hold updates and
+    `effort_node` the 1-based node of it, `track_err` = the largest ||Sx^-1 (x(t_k) - xd[:, k])||_inf over the nodes and
+    `track_node` its node; None otherwise."""
+
+    def __init__(self, raw, steps, res, viol_tol, D, flights=None):
+        super().__init__(raw, res, viol_tol, D, flights)
+        self.steps = int(steps)
+        views = ("effort", "effort_node", "track_err", "track_node")
+        for j, name in enumerate(views):
+            setattr(self, name, None if self.flights is None else self.flights[:, :, 12 + j])
+
+
+def _tracking_steps(pbm, steps):
+    N = pbm.pars.N
+    steps = -(-(_audit_res(pbm, None) - 1) // (N - 1)) if steps is None else int(steps)
+    return steps, steps * (N - 1) + 1
+
+
+def _tracking_gains(pbm, B, gains):
+    """None (the gains resident in the handle), a GainBatch or an array [B, N-1, nu, nx] -> the library's layout or None"""
+    if gains is None:
+        return None
+    K = gains.K if isinstance(gains, GainBatch) else np.asarray(gains, dtype=np.float64)
+    if K.shape != (B, pbm.pars.N - 1, pbm.nu, pbm.nx):
+        raise ValueError("gains of shape %s, expected %s" % (K.shape, (B, pbm.pars.N - 1, pbm.nu, pbm.nx)))
+    return np.ascontiguousarray(K.transpose(0, 1, 3, 2))
+
+
+def audit_tracking(sol, pbm, gains=None, steps=None, dx0=None, ugain=None, ubias=None, shared=False, model=None, pp=None, viol_tol=0.0,
+                   flights=False):
+    """Closed-loop tracking audit of the batch solution `sol` (scp_audit_tracking_batch_host): `audit_dispersed` with the loop
+    closed.  `gains` = a GainBatch, an array [B, N-1, nu, nx], or None for the gains the last `lqr_gains` call on this problem left
+    in the handle; `steps` = RK4 steps per interval (None: ceil((default res - 1) / (N - 1))).  At every node k the hold
+    du = -K_k (x - xd[:, k]) is renewed; the flown input is ugain * (u(t) + du) + ubias.  The other arguments are those of
+    `audit_dispersed`.  Returns a TrackingAuditBatch."""
+    L = _lib.lib()
+    xd = np.ascontiguousarray(sol.xd, dtype=np.float64)
+    ud = np.ascontiguousarray(sol.ud, dtype=np.float64)
+    p = np.ascontiguousarray(sol.p, dtype=np.float64)
+    B = xd.shape[0]
+    pp = np.ascontiguousarray(np.tile(pbm.traj.mdl.nominal_pp()[None], (B, 1)) if pp is None else pp, dtype=np.float64)
+    assert pp.shape[0] == B
+    steps, res = _tracking_steps(pbm, steps)
+    K = _tracking_gains(pbm, B, gains)
+    (dx0, ugain, ubias), D, flags, par_true = _dispersed_args(pbm, B, dx0, ugain, ubias, shared, model)
+    out = np.zeros((B, AUDIT_WIDTH))
+    recs = np.zeros((B, D, AUDIT_WIDTH)) if flights else None
+    sec = ctypes.c_double(0.0)
+    opt = lambda a: None if a is None else _ptr(a)      # noqa: E731
+    rc = L.scp_audit_tracking_batch_host(pbm.handle, B, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np > 0 else None,
+                                         _ptr(pp) if pbm.info.npp > 0 else None, opt(K), steps, float(viol_tol), D, opt(dx0), opt(ugain),
+                                         opt(ubias), flags, opt(par_true), _ptr(out), opt(recs), ctypes.byref(sec))
+    _lib.check(rc, pbm.handle)
+    status = getattr(sol, "status", None)
+    if status is not None:
+        bad = ~np.array([str(st).startswith("SCP_SOLVED") for st in status])
+        out[bad] = np.nan
+        if flights:
+            recs[bad] = np.nan
+    a = TrackingAuditBatch(out, steps, res, viol_tol, D, recs)
+    a.seconds = sec.value
+    return a
+
+
+def audit_tracking_resident(pbm, gains=None, steps=None, dx0=None, ugain=None, ubias=None, shared=False, model=None, viol_tol=0.0,
+                            flights=False):
+    """The same for the batch RESIDENT in the handle (scp_audit_tracking_resident), with `gains` None = those of the last
+    `lqr_gains_resident`; the run is left untouched.  Returns a TrackingAuditBatch."""
+    B = getattr(pbm, "resident_B", None)
+    if B is None:
+        raise _lib.ScpError(1, "audit_tracking_resident: no run has been started on this problem")
+    steps, res = _tracking_steps(pbm, steps)
+    K = _tracking_gains(pbm, B, gains)
+    (dx0, ugain, ubias), D, flags, par_true = _dispersed_args(pbm, B, dx0, ugain, ubias, shared, model)
+    cap = max(pbm.batch_capacity, B)      # room for the library's own batch, whatever this module believes
+    out = np.zeros((cap, AUDIT_WIDTH))
+    recs = np.zeros((cap, D, AUDIT_WIDTH)) if flights else None
+    sec = ctypes.c_double(0.0)
+    opt = lambda a: None if a is None else _ptr(a)      # noqa: E731
+    _lib.check(_lib.lib().scp_audit_tracking_resident(pbm.handle, opt(K), steps, float(viol_tol), D, opt(dx0), opt(ugain), opt(ubias), flags,
+                                                      opt(par_true), _ptr(out), opt(recs), ctypes.byref(sec)), pbm.handle)
+    a = TrackingAuditBatch(out[:B].copy(), steps, res, viol_tol, D, recs[:B].copy() if flights else None)
+    a.seconds = sec.value
+    return a
+
+
 def device_guess(pbm, pp):
     """`traj.guess(N)` for a Monte-Carlo batch evaluated on the device (scp_guess_batch_host): pp[B,npp] ->
     (xd[B,N,nx], ud[B,N,nu], p[B,np])."""
