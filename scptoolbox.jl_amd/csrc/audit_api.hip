@@ -84,15 +84,20 @@ __global__ __launch_bounds__(64) void audit_dispersed_fold_kernel(AuditDispersed
     audit_dispersed_fold(a.D, a.flights + (long)b * a.D * SCP_AUDIT_WIDTH, out);
 }
 
+// the two launches of a D-flight audit: one thread per (problem, flight), then one per problem
+template <class Args, class Params>
+static int audit_flights_launch(void (*flight)(Args, Params), void (*fold)(Args), const Args& a, const Params& par, hipStream_t stream)
+{
+    hipLaunchKernelGGL(flight, dim3((unsigned)(((long)a.B * a.D + 63) / 64)), dim3(64), 0, stream, a, par);
+    if (hipGetLastError() != hipSuccess) return (int)SCP_ERR_HIP;
+    hipLaunchKernelGGL(fold, dim3((a.B + 63) / 64), dim3(64), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+}
+
 int audit_dispersed_launch(int model_id, const double* model_par, const AuditDispersedArgs& a, hipStream_t stream)
 {
     return with_audit_model(model_id, [&](auto m) -> int {
-        using M = decltype(m);
-        const dim3 grid((unsigned)(((long)a.B * a.D + 63) / 64)), block(64);
-        hipLaunchKernelGGL(audit_dispersed_kernel<M>, grid, block, 0, stream, a, M::make_params(model_par));
-        if (hipGetLastError() != hipSuccess) return (int)SCP_ERR_HIP;
-        hipLaunchKernelGGL(audit_dispersed_fold_kernel, dim3((a.B + 63) / 64), block, 0, stream, a);
-        return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+        return audit_flights_launch(audit_dispersed_kernel<decltype(m)>, audit_dispersed_fold_kernel, a, decltype(m)::make_params(model_par), stream);
     });
 }
 
@@ -113,12 +118,28 @@ __global__ __launch_bounds__(64) void audit_tracking_fold_kernel(AuditTrackingAr
 int audit_tracking_launch(int model_id, const double* model_par, const AuditTrackingArgs& a, hipStream_t stream)
 {
     return with_audit_model(model_id, [&](auto m) -> int {
+        return audit_flights_launch(audit_tracking_kernel<decltype(m)>, audit_tracking_fold_kernel, a, decltype(m)::make_params(model_par), stream);
+    });
+}
+
+// the host twin of a D-flight audit: the D flights of ONE problem, with the truth model where one is given, and their fold
+template <AuditFlight MODE>
+static int audit_flights_host(int model_id, const double* model_par, const double* par_true, int N, const double* xd, const double* ud,
+                              const double* p, const double* pp, const double* Sx, const double* Su, const double* K, int res_or_steps, double viol_tol,
+                              int D, const double* dx0, const double* ugain, const double* ubias, double marker, double* summary, double* flights)
+{
+    return with_audit_model(model_id, [&](auto m) -> int {
         using M = decltype(m);
-        const dim3 grid((unsigned)(((long)a.B * a.D + 63) / 64)), block(64);
-        hipLaunchKernelGGL(audit_tracking_kernel<M>, grid, block, 0, stream, a, M::make_params(model_par));
-        if (hipGetLastError() != hipSuccess) return (int)SCP_ERR_HIP;
-        hipLaunchKernelGGL(audit_tracking_fold_kernel, dim3((a.B + 63) / 64), block, 0, stream, a);
-        return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+        if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
+        const typename M::Params par = M::make_params(par_true ? par_true : model_par);
+        std::vector<double> own;
+        if (!flights) { own.resize((size_t)SCP_AUDIT_WIDTH * D); flights = own.data(); }
+        for (int d = 0; d < D; d++)
+            audit_flight_one<M, MODE>(par, N, res_or_steps, viol_tol, xd, ud, p, pp, Sx, flights + (size_t)d * SCP_AUDIT_WIDTH,
+                                      dx0 ? dx0 + (size_t)d * M::nx : nullptr, ugain ? ugain + (size_t)d * M::nu : nullptr,
+                                      ubias ? ubias + (size_t)d * M::nu : nullptr, Su, K);
+        audit_dispersed_fold(D, flights, summary, marker);
+        return (int)SCP_OK;
     });
 }
 
@@ -132,7 +153,7 @@ extern "C" int scp_model_audit_host(int model_id, const double* model_par, int N
     return scp::with_audit_model(model_id, [&](auto m) -> int {
         using M = decltype(m);
         if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
-        scp::audit_one<M>(M::make_params(model_par), N, res, viol_tol, xd, ud, p, pp, Sx, audit);
+        scp::audit_flight_one<M, scp::AuditFlight::nominal>(M::make_params(model_par), N, res, viol_tol, xd, ud, p, pp, Sx, audit);
         return (int)SCP_OK;
     });
 }
@@ -169,19 +190,8 @@ extern "C" int scp_model_audit_dispersed_host(int model_id, const double* model_
                                               double* summary, double* flights)
 {
     if (!model_par || N < 2 || !xd || !ud || !Sx || !summary || res < 2 || D < 1) return SCP_ERR_BAD_ARGUMENT;
-    return scp::with_audit_model(model_id, [&](auto m) -> int {
-        using M = decltype(m);
-        if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
-        const typename M::Params par = M::make_params(par_true ? par_true : model_par);
-        std::vector<double> own;
-        if (!flights) { own.resize((size_t)SCP_AUDIT_WIDTH * D); flights = own.data(); }
-        for (int d = 0; d < D; d++)
-            scp::audit_dispersed_one<M>(par, N, res, viol_tol, xd, ud, p, pp, Sx, dx0 ? dx0 + (size_t)d * M::nx : nullptr,
-                                        ugain ? ugain + (size_t)d * M::nu : nullptr, ubias ? ubias + (size_t)d * M::nu : nullptr,
-                                        flights + (size_t)d * SCP_AUDIT_WIDTH);
-        scp::audit_dispersed_fold(D, flights, summary);
-        return (int)SCP_OK;
-    });
+    return scp::audit_flights_host<scp::AuditFlight::dispersed>(model_id, model_par, par_true, N, xd, ud, p, pp, Sx, nullptr, nullptr, res,
+                                                                viol_tol, D, dx0, ugain, ubias, 2.0, summary, flights);
 }
 
 extern "C" int scp_model_audit_tracking_host(int model_id, const double* model_par, const double* par_true, int N, const double* xd,
@@ -190,17 +200,6 @@ extern "C" int scp_model_audit_tracking_host(int model_id, const double* model_p
                                              const double* ugain, const double* ubias, double* summary, double* flights)
 {
     if (!model_par || N < 2 || !xd || !ud || !Sx || !Su || !K || !summary || steps < 1 || D < 1) return SCP_ERR_BAD_ARGUMENT;
-    return scp::with_audit_model(model_id, [&](auto m) -> int {
-        using M = decltype(m);
-        if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
-        const typename M::Params par = M::make_params(par_true ? par_true : model_par);
-        std::vector<double> own;
-        if (!flights) { own.resize((size_t)SCP_AUDIT_WIDTH * D); flights = own.data(); }
-        for (int d = 0; d < D; d++)
-            scp::audit_tracking_one<M>(par, N, steps, viol_tol, xd, ud, p, pp, Sx, Su, K, dx0 ? dx0 + (size_t)d * M::nx : nullptr,
-                                       ugain ? ugain + (size_t)d * M::nu : nullptr, ubias ? ubias + (size_t)d * M::nu : nullptr,
-                                       flights + (size_t)d * SCP_AUDIT_WIDTH);
-        scp::audit_dispersed_fold(D, flights, summary, 3.0);
-        return (int)SCP_OK;
-    });
+    return scp::audit_flights_host<scp::AuditFlight::tracking>(model_id, model_par, par_true, N, xd, ud, p, pp, Sx, Su, K, steps, viol_tol,
+                                                               D, dx0, ugain, ubias, 3.0, summary, flights);
 }

@@ -3,8 +3,8 @@
 // user inspects afterwards -- the worst value of every constraint family BETWEEN the grid nodes, the open-loop terminal
 // miss and the cost actually flown -- to one record of SCP_AUDIT_WIDTH doubles per problem (include/scp_mi355x.h).
 //
-// One body, audit_one<M>, serves the kernel and the host twin (scp_model_audit_host).  The state after each RK4 step is
-// consumed in registers: nothing of size res * B exists anywhere.  The integration repeats propagate_foh_kernel
+// One body, audit_flight_one<M, MODE>, serves the flight kernels and their host twins (scp_model_audit_host and its kin).  The
+// state after each RK4 step is consumed in registers: nothing of size res * B exists anywhere.  The integration repeats propagate_foh_kernel
 // (discretize_kernel.hpp) expression by expression -- same sample times, same interval search of the input
 // interpolation, same stage order, M::action behind every step.
 //
@@ -46,7 +46,7 @@ SCP_DEV double audit_linrange(double a, double b, int n, int j)
     return (1.0 - tt) * a + tt * b;
 }
 
-// what the samples of one flight (audit_one) or of one interval (audit_interval_one) accumulate
+// what the samples of one flight (audit_flight_one) or of one interval (audit_interval_one) accumulate
 struct AuditAcc {
     double s_max = -INFINITY, t_s = 0.0, l_max = -INFINITY, t_l = 0.0, c_max = -INFINITY, t_c = 0.0, n_viol = 0.0;
     bool bad = false;
@@ -175,18 +175,54 @@ SCP_DEV double audit_phi(const double (&x)[M::nx], const double* pb, const doubl
     return phi;
 }
 
-// xd[nx,N], ud[nu,N], p[np], pp[npp], Sx[nx] of ONE problem -> out[SCP_AUDIT_WIDTH]
-template <class M>
-SCP_DEV void audit_one(const typename M::Params& par, int N, int res, double viol_tol, const double* xd, const double* ub,
-                       const double* pb, const double* pp, const double* Sx, double* out)
+// ------------------------------------------------------------------------------------------------
+// ONE flight of ONE problem, the body of the single-shooting, the dispersed and the tracking audit, on the device and in the
+// host twins.  The flight starts at the first node and takes res - 1 RK4 steps over LinRange(0, 1, res); the input is the
+// first-order hold of ud with propagate_foh_kernel's clamp and interval search, stage times included.  The state is sampled
+// before the first and after every step: the sample at time t is audited with the model functions of the last grid node <= t,
+// decided against the exact grid values (the k_j rule), and the running cost is integrated by the trapezoidal rule over the
+// samples.  The end point gives g_tc, the drift against xd[:,N] (the UNDISPERSED one in every mode) and phi.
+//   nominal    x(0) = xd[:,1], u(t) = u_foh(t); out[12..15] = 0
+//   dispersed  x(0) = xd[:,1] + dx0 (physical units), u'(t) = gain o u_foh(t) + bias at every time; the dynamics, the row
+//              families, the cones and Gamma all see u': the flight is audited as flown.  `par` is the truth model's where the
+//              call gives one (dynamics, s, rows, cost and g_tc); p and pp are not dispersed.  out[12..15] = 0
+//   tracking   the dispersed flight with the loop closed by sample-and-hold gains Kg[nu,nx,N-1] at the node rate.  The caller
+//              gives the RK4 steps per interval, the samples are res = steps (N-1) + 1, so that every step lies inside one interval
+//              and node k is sample (k-1) steps by integer arithmetic.  Hold update at node k < N, before the step that leaves
+//              it: du = -K_k (x - xd[:,k]); commanded input u_foh(t) + du, flown input gain o (u_foh(t) + du) + bias.  A sample
+//              at a node is audited with the hold that was in force over the step that ended there.  out[12], [13] the largest
+//              ||Su^-1 du||_inf over the hold updates and its node, [14], [15] the largest ||Sx^-1 (x(t_k) - xd[:,k])||_inf
+//              over the nodes 1 .. N and its node (strict >: the first wins).  With K = 0 it is the dispersed flight.
+// Only these four places -- the initial state, one expression of `input`, the `node` calls and out[12..15] -- stand behind
+// `if constexpr`; what a mode does not use (ug, ubs, du, effort .. k_track, node) is dead there, and every kernel's machine code
+// is what its own copy of this body gave ("One flight body").  Do NOT merge further: sharing the RK4 step with
+// audit_interval_one, one argument struct for the dispersed and the tracking kernel, or one body with the interval audit
+// each changes the register allocation of kernels that sit at their VGPR limit (measured, same place).
+// ------------------------------------------------------------------------------------------------
+enum class AuditFlight { nominal, dispersed, tracking };
+
+// xd[nx,N], ud[nu,N], p[np], pp[npp], Sx[nx] -> out[SCP_AUDIT_WIDTH]; dispersed and tracking: dx0[nx], gain[nu], bias[nu], each
+// may be nullptr; tracking: Su[nu], Kg[nu,nx,N-1]
+template <class M, AuditFlight MODE>
+SCP_DEV void audit_flight_one(const typename M::Params& par, int N, int res_or_steps, double viol_tol, const double* xd,
+                              const double* ub, const double* pb, const double* pp, const double* Sx, double* out, const double* dx0 = nullptr,
+                              const double* gain = nullptr, const double* bias = nullptr, const double* Su = nullptr,
+                              const double* Kg = nullptr)
 {
     static_assert(M::np_node == 0, "a row of node k would read that node's own parameters: undefined between the nodes");
     constexpr int nx = M::nx, nu = M::nu, np = M::np, npa = np > 0 ? np : 1, npF = M::npF, npFa = npF > 0 ? npF : 1, ng = M::ng;
+    constexpr bool tracking = MODE == AuditFlight::tracking;
+    const int steps = res_or_steps, res = tracking ? steps * (N - 1) + 1 : res_or_steps;
 
-    double x[nx];
+    double x[nx], ug[nu], ubs[nu], du[nu];
 #pragma unroll
-    for (int i = 0; i < nx; i++) x[i] = xd[i];
-    // u(t) and f(t, x): propagate_foh_kernel's own
+    for (int i = 0; i < nx; i++) {
+        if constexpr (MODE == AuditFlight::nominal) x[i] = xd[i];
+        else x[i] = xd[i] + (dx0 != nullptr ? dx0[i] : 0.0);
+    }
+#pragma unroll
+    for (int i = 0; i < nu; i++) { ug[i] = gain != nullptr ? gain[i] : 1.0; ubs[i] = bias != nullptr ? bias[i] : 0.0; du[i] = 0.0; }
+    // u(t) and f(t, x): propagate_foh_kernel's own, then the mode's feedback, gain and bias
     auto input = [&](double t, double (&u)[nu]) {
         const double g0 = audit_linrange(0.0, 1.0, N, 0), g1 = audit_linrange(0.0, 1.0, N, N - 1);
         t = fmax(g0, fmin(g1, t));
@@ -198,7 +234,11 @@ SCP_DEV void audit_one(const typename M::Params& par, int N, int res, double vio
         const double ta = audit_linrange(0.0, 1.0, N, k - 1), tb = audit_linrange(0.0, 1.0, N, k);
         const double c = (tb - t) / (tb - ta);
 #pragma unroll
-        for (int i = 0; i < nu; i++) u[i] = c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i];
+        for (int i = 0; i < nu; i++) {
+            if constexpr (MODE == AuditFlight::nominal) u[i] = c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i];
+            else if constexpr (MODE == AuditFlight::dispersed) u[i] = ug[i] * (c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i]) + ubs[i];
+            else u[i] = ug[i] * ((c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i]) + du[i]) + ubs[i];
+        }
     };
     auto f = [&](double t, const double (&xs)[nx], double (&fx)[nx]) {
         double u[nu], Am[nx * nx], Bmat[nx * nu], Fc[nx * npFa];
@@ -213,6 +253,7 @@ SCP_DEV void audit_one(const typename M::Params& par, int N, int res, double vio
 
     AuditAcc acc;
     double gam_prev = 0.0, cost_int = 0.0;
+    double effort = -INFINITY, k_effort = 0.0, track = -INFINITY, k_track = 0.0;
 
     // everything that is evaluated AT a sample (t, x): returns the running cost Gamma there
     auto sample = [&](double t) -> double {
@@ -225,9 +266,41 @@ SCP_DEV void audit_one(const typename M::Params& par, int N, int res, double vio
         input(t, u);
         return audit_sample<M>(par, t, k, x, u, pb, viol_tol, Qu, lu, lx, acc);
     };
+    // tracking, at node k (1-based): the tracking error of the state as it is, and for k < N the new hold from it
+    [[maybe_unused]] auto node = [&](int k) {
+        const double* xk = xd + (long)(k - 1) * nx;
+        double e[nx], terr = 0.0;
+#pragma unroll
+        for (int i = 0; i < nx; i++) {
+            e[i] = x[i] - xk[i];
+            const double d = e[i] / Sx[i];
+            acc.bad = acc.bad || !__builtin_isfinite(d);
+            terr = fmax(terr, fabs(d));
+        }
+        if (terr > track) { track = terr; k_track = (double)k; }
+        if (k < N) {
+            const double* Kk = Kg + (long)(k - 1) * nu * nx;
+            double eff = 0.0;
+#pragma unroll
+            for (int a = 0; a < nu; a++) {
+                double s = 0.0;
+#pragma unroll
+                for (int i = 0; i < nx; i++) s += Kk[a + nu * i] * e[i];
+                du[a] = -s;
+                const double d = du[a] / Su[a];
+                acc.bad = acc.bad || !__builtin_isfinite(d);
+                eff = fmax(eff, fabs(d));
+            }
+            if (eff > effort) { effort = eff; k_effort = (double)k; }
+        }
+    };
 
+    if constexpr (tracking) node(1);
     gam_prev = sample(audit_linrange(0.0, 1.0, res, 0));
     for (int j = 1; j < res; j++) {
+        if constexpr (tracking) {
+            if (j > 1 && (j - 1) % steps == 0) node((j - 1) / steps + 1);
+        }
         const double t = audit_linrange(0.0, 1.0, res, j - 1), tp = audit_linrange(0.0, 1.0, res, j), h = tp - t;
         double k1[nx], k2[nx], k3[nx], k4[nx], tmp[nx];
         f(t, x, k1);
@@ -247,6 +320,7 @@ SCP_DEV void audit_one(const typename M::Params& par, int N, int res, double vio
         cost_int += 0.5 * h * (gam + gam_prev);          // trapz over tc (helper.jl:560-568), normalised time like the discrete J
         gam_prev = gam;
     }
+    if constexpr (tracking) node(N);
 
     // ---- quantities of the end point and of the parameters alone ----
     const double par_max = audit_par_max<M>(par, pb);
@@ -264,8 +338,12 @@ SCP_DEV void audit_one(const typename M::Params& par, int N, int res, double vio
 
     out[0] = acc.s_max; out[1] = acc.t_s; out[2] = acc.l_max; out[3] = acc.t_l; out[4] = acc.c_max; out[5] = acc.t_c;
     out[6] = par_max; out[7] = bc; out[8] = drift; out[9] = cost; out[10] = acc.n_viol; out[11] = acc.bad ? 1.0 : 0.0;
+    if constexpr (tracking) {
+        out[12] = effort; out[13] = k_effort; out[14] = track; out[15] = k_track;
+    } else {
 #pragma unroll
-    for (int i = 12; i < SCP_AUDIT_WIDTH; i++) out[i] = 0.0;
+        for (int i = 12; i < SCP_AUDIT_WIDTH; i++) out[i] = 0.0;
+    }
 }
 
 // one thread per problem, blocks of one wavefront, like propagate_foh_kernel: serial in time, independent across the batch
@@ -280,8 +358,8 @@ __global__ __launch_bounds__(64) void audit_foh_kernel(AuditArgs a, typename M::
         for (int i = 0; i < SCP_AUDIT_WIDTH; i++) out[i] = NAN;
         return;
     }
-    audit_one<M>(par, a.N, a.res, a.viol_tol, a.xd + (long)b * a.N * M::nx, a.ud + (long)b * a.N * M::nu,
-                 a.p + (long)b * np_total<M>(a.N), a.pp + (long)b * M::npp, a.Sx, out);
+    audit_flight_one<M, AuditFlight::nominal>(par, a.N, a.res, a.viol_tol, a.xd + (long)b * a.N * M::nx, a.ud + (long)b * a.N * M::nu,
+                                              a.p + (long)b * np_total<M>(a.N), a.pp + (long)b * M::npp, a.Sx, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -475,16 +553,10 @@ __global__ __launch_bounds__(64) void audit_interval_fold_kernel(AuditIntervalAr
 }
 
 // ------------------------------------------------------------------------------------------------
-// Dispersed-flight audit (scp_audit_dispersed_*): every problem is flown D times OFF-nominal by the single-shooting audit above
-// -- same samples, same RK4, same k_j rule -- with three changes per flight d = 1 .. D:
-//   initial state  x(0) = xd[:,1] + dx0[:,d]                                  (physical units)
-//   actuators      u'(t) = ugain[:,d] o u_foh(t) + ubias[:,d] at every time, stage times included; the dynamics, the row
-//                  families, the cones and Gamma all see u': the flight is audited as flown
-//   truth model    `par` is the M::Params of the call's par_true where one is given: dynamics, s, rows, cost and g_tc
-// p and pp are not dispersed, and the drift (record 8) is measured against the undispersed xd[:,N].  One record per flight in
-// the single-shooting layout; the records of a problem are then folded IN FLIGHT ORDER into its summary, so that neither output
-// depends on the batch size, on the place of a problem in the batch or on the launch geometry.
-// audit_one is not touched: the dispersed flight is a body of its own that shares the per-sample and end-point functions.
+// Dispersed-flight audit (scp_audit_dispersed_*): every problem is flown D times OFF-nominal, audit_flight_one's dispersed mode
+// with column d = 1 .. D of dx0 / ugain / ubias.  One record per flight in the single-shooting layout; the records of a problem
+// are then folded IN FLIGHT ORDER into its summary, so that neither output depends on the batch size, on the place of a problem
+// in the batch or on the launch geometry.
 // ------------------------------------------------------------------------------------------------
 struct AuditDispersedArgs {
     int B, N, res, D;
@@ -505,101 +577,6 @@ struct AuditDispersedArgs {
 
 // audit_api.hip: audit_dispersed_kernel<M> then audit_dispersed_fold_kernel (no model enters the fold: it lives there) on `stream`; model_par is the blob the flights fly with
 int audit_dispersed_launch(int model_id, const double* model_par, const AuditDispersedArgs& a, hipStream_t stream);
-
-// ONE flight of ONE problem: xd[nx,N], ud[nu,N], p[np], pp[npp], Sx[nx], dx0[nx], gain[nu], bias[nu] (each of the last three may
-// be nullptr) -> out[SCP_AUDIT_WIDTH]
-template <class M>
-SCP_DEV void audit_dispersed_one(const typename M::Params& par, int N, int res, double viol_tol, const double* xd, const double* ub,
-                                 const double* pb, const double* pp, const double* Sx, const double* dx0, const double* gain,
-                                 const double* bias, double* out)
-{
-    static_assert(M::np_node == 0, "a row of node k would read that node's own parameters: undefined between the nodes");
-    constexpr int nx = M::nx, nu = M::nu, np = M::np, npa = np > 0 ? np : 1, npF = M::npF, npFa = npF > 0 ? npF : 1, ng = M::ng;
-
-    double x[nx], ug[nu], ubs[nu];
-#pragma unroll
-    for (int i = 0; i < nx; i++) x[i] = xd[i] + (dx0 != nullptr ? dx0[i] : 0.0);
-#pragma unroll
-    for (int i = 0; i < nu; i++) { ug[i] = gain != nullptr ? gain[i] : 1.0; ubs[i] = bias != nullptr ? bias[i] : 0.0; }
-    // u'(t): the first-order hold of audit_one (same clamp, same interval search), then gain and bias
-    auto input = [&](double t, double (&u)[nu]) {
-        const double g0 = audit_linrange(0.0, 1.0, N, 0), g1 = audit_linrange(0.0, 1.0, N, N - 1);
-        t = fmax(g0, fmin(g1, t));
-        int k = (int)floor(t * (N - 1));
-        k = k < 0 ? 0 : (k > N ? N : k);
-        while (k < N && t > audit_linrange(0.0, 1.0, N, k)) k++;
-        while (k > 0 && !(t > audit_linrange(0.0, 1.0, N, k - 1))) k--;
-        if (k == 0) k = 1;
-        const double ta = audit_linrange(0.0, 1.0, N, k - 1), tb = audit_linrange(0.0, 1.0, N, k);
-        const double c = (tb - t) / (tb - ta);
-#pragma unroll
-        for (int i = 0; i < nu; i++) u[i] = ug[i] * (c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i]) + ubs[i];
-    };
-    auto f = [&](double t, const double (&xs)[nx], double (&fx)[nx]) {
-        double u[nu], Am[nx * nx], Bmat[nx * nu], Fc[nx * npFa];
-        input(t, u);
-        M::dyn(par, t, N, xs, u, pb, fx, Am, Bmat, Fc);   // only f survives dead-code elimination
-    };
-
-    double Qu[nu], lu[nu], lx[nx], tx[nx], ctp[npa], cQp[npa];
-#pragma unroll
-    for (int i = 0; i < npa; i++) { ctp[i] = 0.0; cQp[i] = 0.0; }
-    M::cost_terms(par, Qu, lu, lx, tx, ctp, cQp);
-
-    AuditAcc acc;
-    double gam_prev = 0.0, cost_int = 0.0;
-    auto sample = [&](double t) -> double {
-        // 1-based index of the last grid node <= t, decided against the exact grid values (N at t = 1)
-        int k = (int)floor(t * (N - 1)) + 1;
-        k = k < 1 ? 1 : (k > N ? N : k);
-        while (k < N && !(audit_linrange(0.0, 1.0, N, k) > t)) k++;
-        while (k > 1 && audit_linrange(0.0, 1.0, N, k - 1) > t) k--;
-        double u[nu];
-        input(t, u);
-        return audit_sample<M>(par, t, k, x, u, pb, viol_tol, Qu, lu, lx, acc);
-    };
-
-    gam_prev = sample(audit_linrange(0.0, 1.0, res, 0));
-    for (int j = 1; j < res; j++) {
-        const double t = audit_linrange(0.0, 1.0, res, j - 1), tp = audit_linrange(0.0, 1.0, res, j), h = tp - t;
-        double k1[nx], k2[nx], k3[nx], k4[nx], tmp[nx];
-        f(t, x, k1);
-#pragma unroll
-        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h / 2 * k1[i];
-        f(t + h / 2, tmp, k2);
-#pragma unroll
-        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h / 2 * k2[i];
-        f(t + h / 2, tmp, k3);
-#pragma unroll
-        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h * k3[i];
-        f(t + h, tmp, k4);
-#pragma unroll
-        for (int i = 0; i < nx; i++) x[i] = x[i] + h / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
-        M::action(x);
-        const double gam = sample(tp);
-        cost_int += 0.5 * h * (gam + gam_prev);
-        gam_prev = gam;
-    }
-
-    // ---- quantities of the end point and of the parameters alone; the drift against the UNDISPERSED last node ----
-    const double par_max = audit_par_max<M>(par, pb);
-    const double bc = audit_bc_tc<M>(par, x, pb, pp, acc.bad);
-    double drift = 0.0;
-#pragma unroll
-    for (int i = 0; i < nx; i++) {
-        const double d = (x[i] - xd[(long)(N - 1) * nx + i]) / Sx[i];
-        acc.bad = acc.bad || !__builtin_isfinite(d);
-        drift = fmax(drift, fabs(d));
-    }
-    const double phi = audit_phi<M>(x, pb, tx, ctp, cQp);
-    const double cost = phi + cost_int;
-    acc.bad = acc.bad || !__builtin_isfinite(cost) || (ng > 0 && !__builtin_isfinite(par_max));
-
-    out[0] = acc.s_max; out[1] = acc.t_s; out[2] = acc.l_max; out[3] = acc.t_l; out[4] = acc.c_max; out[5] = acc.t_c;
-    out[6] = par_max; out[7] = bc; out[8] = drift; out[9] = cost; out[10] = acc.n_viol; out[11] = acc.bad ? 1.0 : 0.0;
-#pragma unroll
-    for (int i = 12; i < SCP_AUDIT_WIDTH; i++) out[i] = 0.0;
-}
 
 // The ordered fold of the D flight records recs[SCP_AUDIT_WIDTH, D] of ONE problem into out[SCP_AUDIT_WIDTH].  A flight whose
 // record [11] != 0 is counted in [11] and takes no part in any other field.  Strict comparisons from -Inf: the first flight wins
@@ -644,25 +621,16 @@ __global__ __launch_bounds__(64) void audit_dispersed_kernel(AuditDispersedArgs 
         return;
     }
     const long col = a.shared ? gid % a.D : gid;          // the flight's column of the dispersion arrays
-    audit_dispersed_one<M>(par, a.N, a.res, a.viol_tol, a.xd + (long)b * a.N * M::nx, a.ud + (long)b * a.N * M::nu,
-                           a.p + (long)b * np_total<M>(a.N), a.pp + (long)b * M::npp, a.Sx,
-                           a.dx0 != nullptr ? a.dx0 + col * M::nx : nullptr, a.ugain != nullptr ? a.ugain + col * M::nu : nullptr,
-                           a.ubias != nullptr ? a.ubias + col * M::nu : nullptr, rec);
+    audit_flight_one<M, AuditFlight::dispersed>(par, a.N, a.res, a.viol_tol, a.xd + (long)b * a.N * M::nx, a.ud + (long)b * a.N * M::nu,
+                                                a.p + (long)b * np_total<M>(a.N), a.pp + (long)b * M::npp, a.Sx, rec,
+                                                a.dx0 != nullptr ? a.dx0 + col * M::nx : nullptr,
+                                                a.ugain != nullptr ? a.ugain + col * M::nu : nullptr,
+                                                a.ubias != nullptr ? a.ubias + col * M::nu : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
-// Closed-loop tracking audit (scp_audit_tracking_*): the dispersed flight with the loop closed by sample-and-hold gains
-// K[nu,nx,N-1] at the node rate (lqr_kernel.hpp, or any others).  The samples are `steps` RK4 steps per interval,
-// res = steps (N-1) + 1 at LinRange(0, 1, res), so that every step lies inside one interval and node k is sample (k-1) steps by
-// integer arithmetic.  One flight:
-//   1. x = xd[:,1] + dx0; hold update for k = 1; sample 0
-//   2. for j = 0 .. res-2: if j > 0 and j mod steps == 0 hold update for k = j / steps + 1; RK4 step; sample j+1
-// hold update: du = -K_k (x - xd[:,k]).  Commanded input u_foh(t) + du, flown input ugain o (u_foh(t) + du) + ubias at every time,
-// stage times included; dynamics, U rows, cones and Gamma see the flown input.  A sample at a node is audited with the hold that
-// was in force over the step that ended there.  Records [0..11] as audit_dispersed_one; [12], [13] the largest ||Su^-1 du||_inf
-// over the hold updates and its node, [14], [15] the largest ||Sx^-1 (x(t_k) - xd[:,k])||_inf over the nodes 1 .. N and its node
-// (strict >: the first wins).  With K = 0 the flight is audit_dispersed_one's at the same res.
-// audit_dispersed_one is not touched: the tracking flight is a body of its own.
+// Closed-loop tracking audit (scp_audit_tracking_*): the dispersed audit with audit_flight_one's tracking mode, the gains
+// K[nu,nx,N-1] of every problem from lqr_kernel.hpp or any others; the fold is the dispersed one, marked 3.0.
 // ------------------------------------------------------------------------------------------------
 struct AuditTrackingArgs {
     int B, N, steps, D;
@@ -686,133 +654,6 @@ struct AuditTrackingArgs {
 // audit_api.hip: audit_tracking_kernel<M> then audit_tracking_fold_kernel on `stream`; model_par is the blob the flights fly with
 int audit_tracking_launch(int model_id, const double* model_par, const AuditTrackingArgs& a, hipStream_t stream);
 
-// ONE flight of ONE problem: xd[nx,N], ud[nu,N], p[np], pp[npp], Sx[nx], Su[nu], K[nu,nx,N-1], dx0[nx], gain[nu], bias[nu] (each of
-// the last three may be nullptr) -> out[SCP_AUDIT_WIDTH]
-template <class M>
-SCP_DEV void audit_tracking_one(const typename M::Params& par, int N, int steps, double viol_tol, const double* xd, const double* ub,
-                                const double* pb, const double* pp, const double* Sx, const double* Su, const double* Kg,
-                                const double* dx0, const double* gain, const double* bias, double* out)
-{
-    static_assert(M::np_node == 0, "a row of node k would read that node's own parameters: undefined between the nodes");
-    constexpr int nx = M::nx, nu = M::nu, np = M::np, npa = np > 0 ? np : 1, npF = M::npF, npFa = npF > 0 ? npF : 1, ng = M::ng;
-    const int res = steps * (N - 1) + 1;
-
-    double x[nx], ug[nu], ubs[nu], du[nu];
-#pragma unroll
-    for (int i = 0; i < nx; i++) x[i] = xd[i] + (dx0 != nullptr ? dx0[i] : 0.0);
-#pragma unroll
-    for (int i = 0; i < nu; i++) { ug[i] = gain != nullptr ? gain[i] : 1.0; ubs[i] = bias != nullptr ? bias[i] : 0.0; du[i] = 0.0; }
-    // u'(t): the first-order hold of audit_one (same clamp, same interval search) plus the held feedback, then gain and bias
-    auto input = [&](double t, double (&u)[nu]) {
-        const double g0 = audit_linrange(0.0, 1.0, N, 0), g1 = audit_linrange(0.0, 1.0, N, N - 1);
-        t = fmax(g0, fmin(g1, t));
-        int k = (int)floor(t * (N - 1));
-        k = k < 0 ? 0 : (k > N ? N : k);
-        while (k < N && t > audit_linrange(0.0, 1.0, N, k)) k++;
-        while (k > 0 && !(t > audit_linrange(0.0, 1.0, N, k - 1))) k--;
-        if (k == 0) k = 1;
-        const double ta = audit_linrange(0.0, 1.0, N, k - 1), tb = audit_linrange(0.0, 1.0, N, k);
-        const double c = (tb - t) / (tb - ta);
-#pragma unroll
-        for (int i = 0; i < nu; i++) u[i] = ug[i] * ((c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i]) + du[i]) + ubs[i];
-    };
-    auto f = [&](double t, const double (&xs)[nx], double (&fx)[nx]) {
-        double u[nu], Am[nx * nx], Bmat[nx * nu], Fc[nx * npFa];
-        input(t, u);
-        M::dyn(par, t, N, xs, u, pb, fx, Am, Bmat, Fc);   // only f survives dead-code elimination
-    };
-
-    double Qu[nu], lu[nu], lx[nx], tx[nx], ctp[npa], cQp[npa];
-#pragma unroll
-    for (int i = 0; i < npa; i++) { ctp[i] = 0.0; cQp[i] = 0.0; }
-    M::cost_terms(par, Qu, lu, lx, tx, ctp, cQp);
-
-    AuditAcc acc;
-    double gam_prev = 0.0, cost_int = 0.0;
-    double effort = -INFINITY, k_effort = 0.0, track = -INFINITY, k_track = 0.0;
-    auto sample = [&](double t) -> double {
-        // 1-based index of the last grid node <= t, decided against the exact grid values (N at t = 1)
-        int k = (int)floor(t * (N - 1)) + 1;
-        k = k < 1 ? 1 : (k > N ? N : k);
-        while (k < N && !(audit_linrange(0.0, 1.0, N, k) > t)) k++;
-        while (k > 1 && audit_linrange(0.0, 1.0, N, k - 1) > t) k--;
-        double u[nu];
-        input(t, u);
-        return audit_sample<M>(par, t, k, x, u, pb, viol_tol, Qu, lu, lx, acc);
-    };
-    // at node k (1-based): the tracking error of the state as it is, and for k < N the new hold from it
-    auto node = [&](int k) {
-        const double* xk = xd + (long)(k - 1) * nx;
-        double e[nx], terr = 0.0;
-#pragma unroll
-        for (int i = 0; i < nx; i++) {
-            e[i] = x[i] - xk[i];
-            const double d = e[i] / Sx[i];
-            acc.bad = acc.bad || !__builtin_isfinite(d);
-            terr = fmax(terr, fabs(d));
-        }
-        if (terr > track) { track = terr; k_track = (double)k; }
-        if (k < N) {
-            const double* Kk = Kg + (long)(k - 1) * nu * nx;
-            double eff = 0.0;
-#pragma unroll
-            for (int a = 0; a < nu; a++) {
-                double s = 0.0;
-#pragma unroll
-                for (int i = 0; i < nx; i++) s += Kk[a + nu * i] * e[i];
-                du[a] = -s;
-                const double d = du[a] / Su[a];
-                acc.bad = acc.bad || !__builtin_isfinite(d);
-                eff = fmax(eff, fabs(d));
-            }
-            if (eff > effort) { effort = eff; k_effort = (double)k; }
-        }
-    };
-
-    node(1);
-    gam_prev = sample(audit_linrange(0.0, 1.0, res, 0));
-    for (int j = 1; j < res; j++) {
-        if (j > 1 && (j - 1) % steps == 0) node((j - 1) / steps + 1);
-        const double t = audit_linrange(0.0, 1.0, res, j - 1), tp = audit_linrange(0.0, 1.0, res, j), h = tp - t;
-        double k1[nx], k2[nx], k3[nx], k4[nx], tmp[nx];
-        f(t, x, k1);
-#pragma unroll
-        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h / 2 * k1[i];
-        f(t + h / 2, tmp, k2);
-#pragma unroll
-        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h / 2 * k2[i];
-        f(t + h / 2, tmp, k3);
-#pragma unroll
-        for (int i = 0; i < nx; i++) tmp[i] = x[i] + h * k3[i];
-        f(t + h, tmp, k4);
-#pragma unroll
-        for (int i = 0; i < nx; i++) x[i] = x[i] + h / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
-        M::action(x);
-        const double gam = sample(tp);
-        cost_int += 0.5 * h * (gam + gam_prev);
-        gam_prev = gam;
-    }
-    node(N);
-
-    // ---- quantities of the end point and of the parameters alone; the drift against the UNDISPERSED last node ----
-    const double par_max = audit_par_max<M>(par, pb);
-    const double bc = audit_bc_tc<M>(par, x, pb, pp, acc.bad);
-    double drift = 0.0;
-#pragma unroll
-    for (int i = 0; i < nx; i++) {
-        const double d = (x[i] - xd[(long)(N - 1) * nx + i]) / Sx[i];
-        acc.bad = acc.bad || !__builtin_isfinite(d);
-        drift = fmax(drift, fabs(d));
-    }
-    const double phi = audit_phi<M>(x, pb, tx, ctp, cQp);
-    const double cost = phi + cost_int;
-    acc.bad = acc.bad || !__builtin_isfinite(cost) || (ng > 0 && !__builtin_isfinite(par_max));
-
-    out[0] = acc.s_max; out[1] = acc.t_s; out[2] = acc.l_max; out[3] = acc.t_l; out[4] = acc.c_max; out[5] = acc.t_c;
-    out[6] = par_max; out[7] = bc; out[8] = drift; out[9] = cost; out[10] = acc.n_viol; out[11] = acc.bad ? 1.0 : 0.0;
-    out[12] = effort; out[13] = k_effort; out[14] = track; out[15] = k_track;
-}
-
 // one thread per (problem, flight), gid = b D + (d - 1): the mapping of audit_dispersed_kernel
 template <class M>
 __global__ __launch_bounds__(64) void audit_tracking_kernel(AuditTrackingArgs a, typename M::Params par)
@@ -827,10 +668,12 @@ __global__ __launch_bounds__(64) void audit_tracking_kernel(AuditTrackingArgs a,
         return;
     }
     const long col = a.shared ? gid % a.D : gid;          // the flight's column of the dispersion arrays
-    audit_tracking_one<M>(par, a.N, a.steps, a.viol_tol, a.xd + (long)b * a.N * M::nx, a.ud + (long)b * a.N * M::nu,
-                          a.p + (long)b * np_total<M>(a.N), a.pp + (long)b * M::npp, a.Sx, a.Su, a.K + (long)b * (a.N - 1) * M::nu * M::nx,
-                          a.dx0 != nullptr ? a.dx0 + col * M::nx : nullptr, a.ugain != nullptr ? a.ugain + col * M::nu : nullptr,
-                          a.ubias != nullptr ? a.ubias + col * M::nu : nullptr, rec);
+    audit_flight_one<M, AuditFlight::tracking>(par, a.N, a.steps, a.viol_tol, a.xd + (long)b * a.N * M::nx, a.ud + (long)b * a.N * M::nu,
+                                               a.p + (long)b * np_total<M>(a.N), a.pp + (long)b * M::npp, a.Sx, rec,
+                                               a.dx0 != nullptr ? a.dx0 + col * M::nx : nullptr,
+                                               a.ugain != nullptr ? a.ugain + col * M::nu : nullptr,
+                                               a.ubias != nullptr ? a.ubias + col * M::nu : nullptr, a.Su,
+                                               a.K + (long)b * (a.N - 1) * M::nu * M::nx);
 }
 
 }  // namespace scp

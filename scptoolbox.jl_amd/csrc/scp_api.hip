@@ -729,10 +729,11 @@ static int audit_dispersed_reserve(scp_problem* h, int D)
     return SCP_OK;
 }
 
-// the dispersions to the device, the two kernels between the handle's two events, then the copies
-static int audit_dispersed_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, int res, double viol_tol,
-                               int D, const double* dx0, const double* ugain, const double* ubias, unsigned flags,
-                               const double* par_true, double* summary, double* flights, double* seconds)
+// The run of a D-flight audit (dispersed, tracking): the dispersions to the device, `launch` -- the two kernels of the audit, given
+// the staged arrays (nullptr where the caller passed none) and the shared flag -- between the handle's two events, then the copies.
+template <class Launch>
+static int audit_flights_run(scp_problem* h, int B, int D, const double* dx0, const double* ugain, const double* ubias, unsigned flags,
+                             double* summary, double* flights, double* seconds, Launch&& launch)
 {
     TRY(audit_dispersed_reserve(h, D));
     const bool shared = (flags & SCP_DISP_SHARED) != 0u;
@@ -740,13 +741,8 @@ static int audit_dispersed_run(scp_problem* h, int B, const Traj& tr, const doub
     if (dx0) HIP_TRY(h, hipMemcpyAsync(h->audit.dx0, dx0, sizeof(double) * h->info.nx * cols, hipMemcpyHostToDevice, h->stream));
     if (ugain) HIP_TRY(h, hipMemcpyAsync(h->audit.ugain, ugain, sizeof(double) * h->info.nu * cols, hipMemcpyHostToDevice, h->stream));
     if (ubias) HIP_TRY(h, hipMemcpyAsync(h->audit.ubias, ubias, sizeof(double) * h->info.nu * cols, hipMemcpyHostToDevice, h->stream));
-    AuditDispersedArgs a;
-    a.B = B; a.N = h->N; a.res = res; a.D = D; a.shared = shared ? 1 : 0; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
-    a.pp = d_pp; a.Sx = h->d_Sx; a.dx0 = dx0 ? h->audit.dx0 : nullptr; a.ugain = ugain ? h->audit.ugain : nullptr;
-    a.ubias = ubias ? h->audit.ubias : nullptr; a.mask = mask; a.flights = h->audit.flights; a.audit = h->audit.rec;
     HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
-    // the truth model: the blob the flights are flown with; like the handle's own it is taken as given
-    const int rc = audit_dispersed_launch(h->model_id, par_true ? par_true : h->par.data(), a, h->stream);
+    const int rc = launch(shared ? 1 : 0, dx0 ? h->audit.dx0 : nullptr, ugain ? h->audit.ugain : nullptr, ubias ? h->audit.ubias : nullptr);
     if (rc != SCP_OK) { h->err = "audit: kernel launch failed"; return rc; }
     HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
     HIP_TRY(h, hipMemcpyAsync(summary, h->audit.rec, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
@@ -755,6 +751,21 @@ static int audit_dispersed_run(scp_problem* h, int B, const Traj& tr, const doub
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     stamps_collect(h);
     return elapsed_out(h, seconds);
+}
+
+static int audit_dispersed_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, int res, double viol_tol,
+                               int D, const double* dx0, const double* ugain, const double* ubias, unsigned flags,
+                               const double* par_true, double* summary, double* flights, double* seconds)
+{
+    return audit_flights_run(h, B, D, dx0, ugain, ubias, flags, summary, flights, seconds,
+                             [&](int shared, const double* d_dx0, const double* d_ugain, const double* d_ubias) {
+        AuditDispersedArgs a;
+        a.B = B; a.N = h->N; a.res = res; a.D = D; a.shared = shared; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
+        a.pp = d_pp; a.Sx = h->d_Sx; a.dx0 = d_dx0; a.ugain = d_ugain; a.ubias = d_ubias; a.mask = mask; a.flights = h->audit.flights;
+        a.audit = h->audit.rec;
+        // the truth model: the blob the flights are flown with; like the handle's own it is taken as given
+        return audit_dispersed_launch(h->model_id, par_true ? par_true : h->par.data(), a, h->stream);
+    });
 }
 
 extern "C" int scp_audit_dispersed_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
@@ -900,26 +911,14 @@ static int audit_tracking_run(scp_problem* h, int B, const Traj& tr, const doubl
 {
     const double* d_K = nullptr;
     TRY(audit_tracking_gains(h, B, K, &d_K));
-    TRY(audit_dispersed_reserve(h, D));
-    const bool shared = (flags & SCP_DISP_SHARED) != 0u;
-    const size_t cols = shared ? (size_t)D : (size_t)D * (size_t)B;
-    if (dx0) HIP_TRY(h, hipMemcpyAsync(h->audit.dx0, dx0, sizeof(double) * h->info.nx * cols, hipMemcpyHostToDevice, h->stream));
-    if (ugain) HIP_TRY(h, hipMemcpyAsync(h->audit.ugain, ugain, sizeof(double) * h->info.nu * cols, hipMemcpyHostToDevice, h->stream));
-    if (ubias) HIP_TRY(h, hipMemcpyAsync(h->audit.ubias, ubias, sizeof(double) * h->info.nu * cols, hipMemcpyHostToDevice, h->stream));
-    AuditTrackingArgs a;
-    a.B = B; a.N = h->N; a.steps = steps; a.D = D; a.shared = shared ? 1 : 0; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
-    a.pp = d_pp; a.Sx = h->d_Sx; a.Su = h->d_Su; a.K = d_K; a.dx0 = dx0 ? h->audit.dx0 : nullptr; a.ugain = ugain ? h->audit.ugain : nullptr;
-    a.ubias = ubias ? h->audit.ubias : nullptr; a.mask = mask; a.flights = h->audit.flights; a.audit = h->audit.rec;
-    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
-    const int rc = audit_tracking_launch(h->model_id, par_true ? par_true : h->par.data(), a, h->stream);
-    if (rc != SCP_OK) { h->err = "audit: kernel launch failed"; return rc; }
-    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(summary, h->audit.rec, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    if (flights)
-        HIP_TRY(h, hipMemcpyAsync(flights, h->audit.flights, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)D * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    stamps_collect(h);
-    return elapsed_out(h, seconds);
+    return audit_flights_run(h, B, D, dx0, ugain, ubias, flags, summary, flights, seconds,
+                             [&](int shared, const double* d_dx0, const double* d_ugain, const double* d_ubias) {
+        AuditTrackingArgs a;
+        a.B = B; a.N = h->N; a.steps = steps; a.D = D; a.shared = shared; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
+        a.pp = d_pp; a.Sx = h->d_Sx; a.Su = h->d_Su; a.K = d_K; a.dx0 = d_dx0; a.ugain = d_ugain; a.ubias = d_ubias; a.mask = mask;
+        a.flights = h->audit.flights; a.audit = h->audit.rec;
+        return audit_tracking_launch(h->model_id, par_true ? par_true : h->par.data(), a, h->stream);
+    });
 }
 
 extern "C" int scp_audit_tracking_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,

@@ -489,13 +489,10 @@ def _dispersed_args(pbm, B, dx0, ugain, ubias, shared, model):
     return arrs, (1 if D is None else D), (DISP_SHARED if shared else 0), par_true
 
 
-def audit_dispersed(sol, pbm, dx0=None, ugain=None, ubias=None, shared=False, model=None, pp=None, res=None, viol_tol=0.0, flights=False):
-    """Dispersed-flight audit of the batch solution `sol` (scp_audit_dispersed_batch_host): every problem is flown D times by the
-    single-shooting audit, flight d starting at xd[:, 0] + dx0[b, d] (physical units) and flying ugain[b, d] * u(t) + ubias[b, d]
-    -- arrays [B, D, nx] and [B, D, nu], or [D, .] with shared=True (every problem flies the same dispersions); None = 0, 1, 0,
-    and D = 1 when all three are None.  `model` = the truth model the flights are flown with: a model instance of the problem's
-    kind or a dict of constant overrides (None: the problem's own constants).  flights=True also returns the record of every
-    flight.  `sol.status` masks as in `audit`.  Returns a DispersedAuditBatch."""
+def _audit_flights(entry, sol, pbm, pp, lead, viol_tol, disp, flights):
+    """The host-batch call of a D-flight audit, `entry` of the library: `lead(B)` gives the arguments between pp and viol_tol
+    (a pointer made by `_ptr` keeps its array alive), `disp` those of `_dispersed_args` after B.  `sol.status` masks as in `audit`.  Returns summary [B, 16], the flight records
+    [B, D, 16] or None, D and the device seconds."""
     L = _lib.lib()
     xd = np.ascontiguousarray(sol.xd, dtype=np.float64)
     ud = np.ascontiguousarray(sol.ud, dtype=np.float64)
@@ -503,15 +500,14 @@ def audit_dispersed(sol, pbm, dx0=None, ugain=None, ubias=None, shared=False, mo
     B = xd.shape[0]
     pp = np.ascontiguousarray(np.tile(pbm.traj.mdl.nominal_pp()[None], (B, 1)) if pp is None else pp, dtype=np.float64)
     assert pp.shape[0] == B
-    res = _audit_res(pbm, res)
-    (dx0, ugain, ubias), D, flags, par_true = _dispersed_args(pbm, B, dx0, ugain, ubias, shared, model)
+    lead = lead(B)
+    (dx0, ugain, ubias), D, flags, par_true = _dispersed_args(pbm, B, *disp)
     out = np.zeros((B, AUDIT_WIDTH))
     recs = np.zeros((B, D, AUDIT_WIDTH)) if flights else None
     sec = ctypes.c_double(0.0)
-    opt = lambda a: None if a is None else _ptr(a)      # noqa: E731
-    rc = L.scp_audit_dispersed_batch_host(pbm.handle, B, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np > 0 else None,
-                                          _ptr(pp) if pbm.info.npp > 0 else None, res, float(viol_tol), D, opt(dx0), opt(ugain),
-                                          opt(ubias), flags, opt(par_true), _ptr(out), opt(recs), ctypes.byref(sec))
+    rc = getattr(L, entry)(pbm.handle, B, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np > 0 else None, _ptr(pp) if pbm.info.npp > 0 else None,
+                           *lead, float(viol_tol), D, _ptr(dx0), _ptr(ugain), _ptr(ubias), flags, _ptr(par_true), _ptr(out), _ptr(recs),
+                           ctypes.byref(sec))
     _lib.check(rc, pbm.handle)
     status = getattr(sol, "status", None)
     if status is not None:
@@ -519,8 +515,38 @@ def audit_dispersed(sol, pbm, dx0=None, ugain=None, ubias=None, shared=False, mo
         out[bad] = np.nan
         if flights:
             recs[bad] = np.nan
+    return out, recs, D, sec.value
+
+
+def _audit_flights_resident(entry, pbm, lead, viol_tol, disp, flights):
+    """The same for the resident batch (`entry` refuses in the caller's name when no run was started): `lead(B)` gives the
+    arguments between the handle and viol_tol."""
+    B = getattr(pbm, "resident_B", None)
+    if B is None:
+        raise _lib.ScpError(1, "%s: no run has been started on this problem" % entry[len("scp_"):])
+    lead = lead(B)
+    (dx0, ugain, ubias), D, flags, par_true = _dispersed_args(pbm, B, *disp)
+    cap = max(pbm.batch_capacity, B)      # room for the library's own batch, whatever this module believes
+    out = np.zeros((cap, AUDIT_WIDTH))
+    recs = np.zeros((cap, D, AUDIT_WIDTH)) if flights else None
+    sec = ctypes.c_double(0.0)
+    _lib.check(getattr(_lib.lib(), entry)(pbm.handle, *lead, float(viol_tol), D, _ptr(dx0), _ptr(ugain), _ptr(ubias), flags, _ptr(par_true),
+                                          _ptr(out), _ptr(recs), ctypes.byref(sec)), pbm.handle)
+    return out[:B].copy(), recs[:B].copy() if flights else None, D, sec.value
+
+
+def audit_dispersed(sol, pbm, dx0=None, ugain=None, ubias=None, shared=False, model=None, pp=None, res=None, viol_tol=0.0, flights=False):
+    """Dispersed-flight audit of the batch solution `sol` (scp_audit_dispersed_batch_host): every problem is flown D times by the
+    single-shooting audit, flight d starting at xd[:, 0] + dx0[b, d] (physical units) and flying ugain[b, d] * u(t) + ubias[b, d]
+    -- arrays [B, D, nx] and [B, D, nu], or [D, .] with shared=True (every problem flies the same dispersions); None = 0, 1, 0,
+    and D = 1 when all three are None.  `model` = the truth model the flights are flown with: a model instance of the problem's
+    kind or a dict of constant overrides (None: the problem's own constants).  flights=True also returns the record of every
+    flight.  `sol.status` masks as in `audit`.  Returns a DispersedAuditBatch."""
+    res = _audit_res(pbm, res)
+    out, recs, D, sec = _audit_flights("scp_audit_dispersed_batch_host", sol, pbm, pp, lambda B: (res,), viol_tol,
+                                       (dx0, ugain, ubias, shared, model), flights)
     a = DispersedAuditBatch(out, res, viol_tol, D, recs)
-    a.seconds = sec.value
+    a.seconds = sec
     return a
 
 
@@ -529,19 +555,10 @@ def audit_dispersed_resident(pbm, dx0=None, ugain=None, ubias=None, shared=False
     would return, its own pp, failed problems skipped by the kernels; the run is left untouched.  Returns a
     DispersedAuditBatch."""
     res = _audit_res(pbm, res)
-    B = getattr(pbm, "resident_B", None)
-    if B is None:
-        raise _lib.ScpError(1, "audit_dispersed_resident: no run has been started on this problem")
-    (dx0, ugain, ubias), D, flags, par_true = _dispersed_args(pbm, B, dx0, ugain, ubias, shared, model)
-    cap = max(pbm.batch_capacity, B)      # room for the library's own batch, whatever this module believes
-    out = np.zeros((cap, AUDIT_WIDTH))
-    recs = np.zeros((cap, D, AUDIT_WIDTH)) if flights else None
-    sec = ctypes.c_double(0.0)
-    opt = lambda a: None if a is None else _ptr(a)      # noqa: E731
-    _lib.check(_lib.lib().scp_audit_dispersed_resident(pbm.handle, res, float(viol_tol), D, opt(dx0), opt(ugain), opt(ubias), flags,
-                                                       opt(par_true), _ptr(out), opt(recs), ctypes.byref(sec)), pbm.handle)
-    a = DispersedAuditBatch(out[:B].copy(), res, viol_tol, D, recs[:B].copy() if flights else None)
-    a.seconds = sec.value
+    out, recs, D, sec = _audit_flights_resident("scp_audit_dispersed_resident", pbm, lambda B: (res,), viol_tol,
+                                                (dx0, ugain, ubias, shared, model), flights)
+    a = DispersedAuditBatch(out, res, viol_tol, D, recs)
+    a.seconds = sec
     return a
 
 
@@ -666,32 +683,11 @@ def audit_tracking(sol, pbm, gains=None, steps=None, dx0=None, ugain=None, ubias
     in the handle; `steps` = RK4 steps per interval (None: ceil((default res - 1) / (N - 1))).  At every node k the hold
     du = -K_k (x - xd[:, k]) is renewed; the flown input is ugain * (u(t) + du) + ubias.  The other arguments are those of
     `audit_dispersed`.  Returns a TrackingAuditBatch."""
-    L = _lib.lib()
-    xd = np.ascontiguousarray(sol.xd, dtype=np.float64)
-    ud = np.ascontiguousarray(sol.ud, dtype=np.float64)
-    p = np.ascontiguousarray(sol.p, dtype=np.float64)
-    B = xd.shape[0]
-    pp = np.ascontiguousarray(np.tile(pbm.traj.mdl.nominal_pp()[None], (B, 1)) if pp is None else pp, dtype=np.float64)
-    assert pp.shape[0] == B
     steps, res = _tracking_steps(pbm, steps)
-    K = _tracking_gains(pbm, B, gains)
-    (dx0, ugain, ubias), D, flags, par_true = _dispersed_args(pbm, B, dx0, ugain, ubias, shared, model)
-    out = np.zeros((B, AUDIT_WIDTH))
-    recs = np.zeros((B, D, AUDIT_WIDTH)) if flights else None
-    sec = ctypes.c_double(0.0)
-    opt = lambda a: None if a is None else _ptr(a)      # noqa: E731
-    rc = L.scp_audit_tracking_batch_host(pbm.handle, B, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np > 0 else None,
-                                         _ptr(pp) if pbm.info.npp > 0 else None, opt(K), steps, float(viol_tol), D, opt(dx0), opt(ugain),
-                                         opt(ubias), flags, opt(par_true), _ptr(out), opt(recs), ctypes.byref(sec))
-    _lib.check(rc, pbm.handle)
-    status = getattr(sol, "status", None)
-    if status is not None:
-        bad = ~np.array([str(st).startswith("SCP_SOLVED") for st in status])
-        out[bad] = np.nan
-        if flights:
-            recs[bad] = np.nan
+    out, recs, D, sec = _audit_flights("scp_audit_tracking_batch_host", sol, pbm, pp, lambda B: (_ptr(_tracking_gains(pbm, B, gains)), steps),
+                                       viol_tol, (dx0, ugain, ubias, shared, model), flights)
     a = TrackingAuditBatch(out, steps, res, viol_tol, D, recs)
-    a.seconds = sec.value
+    a.seconds = sec
     return a
 
 
@@ -699,21 +695,11 @@ def audit_tracking_resident(pbm, gains=None, steps=None, dx0=None, ugain=None, u
                             flights=False):
     """The same for the batch RESIDENT in the handle (scp_audit_tracking_resident), with `gains` None = those of the last
     `lqr_gains_resident`; the run is left untouched.  Returns a TrackingAuditBatch."""
-    B = getattr(pbm, "resident_B", None)
-    if B is None:
-        raise _lib.ScpError(1, "audit_tracking_resident: no run has been started on this problem")
     steps, res = _tracking_steps(pbm, steps)
-    K = _tracking_gains(pbm, B, gains)
-    (dx0, ugain, ubias), D, flags, par_true = _dispersed_args(pbm, B, dx0, ugain, ubias, shared, model)
-    cap = max(pbm.batch_capacity, B)      # room for the library's own batch, whatever this module believes
-    out = np.zeros((cap, AUDIT_WIDTH))
-    recs = np.zeros((cap, D, AUDIT_WIDTH)) if flights else None
-    sec = ctypes.c_double(0.0)
-    opt = lambda a: None if a is None else _ptr(a)      # noqa: E731
-    _lib.check(_lib.lib().scp_audit_tracking_resident(pbm.handle, opt(K), steps, float(viol_tol), D, opt(dx0), opt(ugain), opt(ubias), flags,
-                                                      opt(par_true), _ptr(out), opt(recs), ctypes.byref(sec)), pbm.handle)
-    a = TrackingAuditBatch(out[:B].copy(), steps, res, viol_tol, D, recs[:B].copy() if flights else None)
-    a.seconds = sec.value
+    out, recs, D, sec = _audit_flights_resident("scp_audit_tracking_resident", pbm, lambda B: (_ptr(_tracking_gains(pbm, B, gains)), steps),
+                                                viol_tol, (dx0, ugain, ubias, shared, model), flights)
+    a = TrackingAuditBatch(out, steps, res, viol_tol, D, recs)
+    a.seconds = sec
     return a
 
 

@@ -4,14 +4,13 @@ tests/test_audit_dispersed_cpu.py and tests/test_audit_dispersed_gpu.py.  It tak
 Flight d of a problem is audit_util.Reference on transformed nodes: xd' = xd with dx0 added to row 0 only, ud' = ud * gain + bias.
 The first-order hold is linear, so holding the transformed nodes is the transformed hold, and the reference's record 8 is already
 measured against the untouched last row.  With a truth model the same loop runs over the C oracle's `propagate` with the changed
-parameter vector (oracle.default_params layout) and an oracle model instance with the same constants overridden (TruthReference).
+parameter vector (oracle.default_params layout) and an oracle model instance with the same constants overridden.
 
 The fold is a numpy loop over the flight records the code under test returned, compared bit for bit.  Tolerances: audit_util's
 (RTOL, choose_viol_tol over all flights of a call, equal counts); nothing new."""
 import numpy as np
 
 import audit_util as au
-from oracle.models import linrange
 
 W = au.W
 D3 = 3
@@ -33,41 +32,6 @@ def dispersions(name, N, rng):
     return dx0, gain, bias
 
 
-class TruthReference(au.Reference):
-    """audit_util.Reference flown with a truth model: `par` the C oracle's parameter vector, `mdl` the oracle model instance
-    with the same constants overridden (the loop of Reference.__init__ with those two in place of the defaults)"""
-
-    def __init__(self, orc, name, N, xd, ud, p, pp, Sx, res, par, mdl):
-        self.name, self.res = name, res
-        tc, xc = orc.propagate(name, par, N, xd, ud, p, res=res)
-        tgrid = linrange(0.0, 1.0, N)
-        self.tc = tc
-        fam, scale = np.full((res, 3), -np.inf), np.ones((res, 3))
-        par_max, gam = -np.inf, np.zeros(res)
-        ct = mdl.cost_terms()
-        for j in range(res):
-            t = tc[j]
-            k = max(int(np.sum(tgrid <= t)), 1)
-            fam[j], scale[j], pm, gam[j] = au._sample(name, mdl, ct, t, k, xc[j], au._input(tgrid, ud, t), p)
-            par_max = max(par_max, pm)
-        self.fam, self.scale = fam, scale
-        rec = np.zeros(W)
-        for f in range(3):
-            if np.isfinite(fam[:, f]).any():
-                j = int(np.argmax(fam[:, f]))
-                rec[2 * f], rec[2 * f + 1] = fam[j, f], tc[j]
-            else:
-                rec[2 * f], rec[2 * f + 1] = -np.inf, 0.0
-        rec[6] = par_max
-        xf = xc[-1]
-        rec[7] = np.abs(mdl.gtc(xf, p, pp)).max()
-        rec[8] = np.abs((xf - xd[-1]) / Sx).max()
-        phi = ct["tx"] @ xf + (ct["tp"] @ p + ct["Qp"] @ (p * p) if p.size else 0.0)
-        rec[9] = phi + sum(0.5 * (tc[j + 1] - tc[j]) * (gam[j + 1] + gam[j]) for j in range(res - 1))
-        self.worst = fam.max(axis=1)
-        self.rec = rec
-
-
 def flight_references(orc, name, N, case, Sx, res, dx0, gain, bias, truth=None):
     """one Reference per flight of ONE problem; truth = (C-oracle parameter vector, oracle model instance) or None"""
     xd, ud, p, pp = case
@@ -75,10 +39,7 @@ def flight_references(orc, name, N, case, Sx, res, dx0, gain, bias, truth=None):
     for d in range(dx0.shape[0]):
         x = xd.copy(); x[0] += dx0[d]
         u = ud * gain[d][None, :] + bias[d][None, :]
-        if truth is None:
-            refs.append(au.Reference(orc, name, N, x, u, p, pp, Sx, res))
-        else:
-            refs.append(TruthReference(orc, name, N, x, u, p, pp, Sx, res, *truth))
+        refs.append(au.Reference(orc, name, N, x, u, p, pp, Sx, res, *(truth or ())))
         assert np.isfinite(refs[-1].rec[[7, 8, 9]]).all() and np.isfinite(refs[-1].worst).all(), (name, N, res, d, "the reference is not finite")
     return refs
 

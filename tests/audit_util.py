@@ -108,10 +108,12 @@ def _sample(name, mdl, ct, t, k, x, u, p):
 class Reference:
     """the audit of ONE problem on the CPU: per-sample values of the three sampled families, their term scales, and the record"""
 
-    def __init__(self, orc, name, N, xd, ud, p, pp, Sx, res):
-        mdl = oracle_model(name, N)
+    def __init__(self, orc, name, N, xd, ud, p, pp, Sx, res, par=None, mdl=None):
+        # a truth model: `par` the C oracle's parameter vector, `mdl` the oracle model instance with the same constants overridden
+        par = orc.default_params(name) if par is None else par
+        mdl = oracle_model(name, N) if mdl is None else mdl
         self.name, self.res = name, res
-        tc, xc = orc.propagate(name, orc.default_params(name), N, xd, ud, p, res=res)
+        tc, xc = orc.propagate(name, par, N, xd, ud, p, res=res)
         tgrid = linrange(0.0, 1.0, N)
         self.tc = tc
         fam = np.full((res, 3), -np.inf)          # s, linear rows, cones
