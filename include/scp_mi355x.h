@@ -455,6 +455,82 @@ int scp_model_audit_tracking_host(int model_id, const double *model_par, const d
                                   const double *K, int steps, double viol_tol, int D, const double *dx0, const double *ugain,
                                   const double *ubias, double *summary, double *flights /* [16, D] or NULL */);
 
+/*
+ * Closed-loop covariance audit: the linear covariance analysis of every solution with the loop closed by gains K[nu, nx, N-1, B]
+ * (scp_lqr_gains_*, or any others) -- what a guidance engineer asks for before spending flights on scp_audit_tracking_*.  FOH
+ * handles of the four auditable models.  Shared by the batch, in physical units like the LQR weights: sig0[nx] >= 0 the initial
+ * 1-sigma, sigu[nu] >= 0 the 1-sigma of a white input disturbance held over each interval, sigw[nx] >= 0 the 1-sigma of additive
+ * state noise per interval; nsig > 0 the sigma level.  For one problem:
+ *   Sigma_1 = diag(sig0^2);  for k = 1 .. N-1:  Phi = A_k,  Gam = B-_k + B+_k  (as in scp_lqr_gains_*),  A_cl = Phi - Gam K_k
+ *   Sigma_{k+1} = A_cl Sigma_k A_cl' + Gam diag(sigu^2) Gam' + diag(sigw^2),  then Sigma <- (Sigma + Sigma') / 2
+ * and at node k (1-based)
+ *   state 1-sigma    sigma_{k,i} = sqrt(max(Sigma_k[i,i], 0)),                                  k = 1 .. N
+ *   effort 1-sigma   e_{k,a} = sqrt(max((K_k Sigma_k K_k')[a,a], 0)) / Su[a],                   k = 1 .. N-1
+ *   sigma margins    of every row of the three sampled families of scp_audit_batch_host (s, the linear rows, the cones; not the
+ *                    parameter-only rows), evaluated at the nominal (xd[:,k], ud[:,k], p) with the (t, k) that audit passes at
+ *                    the sample coinciding with node k.  A row has a value v and a gradient [g_x, g_u] over z = [x; u]: s rows
+ *                    (C_i, D_i); linear rows the row of L; a cone with w = M z + m the value ||w[1:4]|| - w[0] and the gradient
+ *                    (w[1:4]' / ||w[1:4]||) M[1:4,:] - M[0,:]  (-M[0,:] when ||w[1:4]|| = 0).  The hold update makes
+ *                    dz = [I; -K_k] dx: g = g_x - g_u K_k at k <= N-1, g = g_x at k = N; var = max(g Sigma_k g', 0);
+ *                    margin = -v / sqrt(var) when var > 0, else +Inf for v <= 0 and -Inf for v > 0
+ *   terminal         tau_i = sqrt(max((H Sigma_N H')[i,i], 0)) with H = d g_tc / dx at xd[:,N]
+ *
+ * summary[SCP_COV_WIDTH, B]; nodes and indices are 1-based, ties go to the smallest node, then the smallest state:
+ *   [0]        1 when anything was not finite ([1..15] are then NaN), else 0
+ *   [1..3]     max over k, i of sigma_{k,i} / Sx[i]; the node; the state attaining it
+ *   [4], [5]   max over k <= N-1 and a of e_{k,a}; the node
+ *   [6], [7]   the smallest margin over the s rows and the nodes; the node (+Inf, 0 when the model has no such rows or no
+ *              margin is below +Inf)
+ *   [8], [9]   the same for the linear rows;  [10], [11] the same for the cones
+ *   [12]       max_i tau_i (0 when ntc = 0)
+ *   [13]       trace(Sx^-1 Sigma_N Sx^-1)
+ *   [14]       number of (node, row) pairs with margin < nsig
+ *   [15]       0
+ * Optional outputs, copied only when asked for (NULL otherwise): sig[nx, N, B] the state 1-sigma values, and
+ * nodes[SCP_COV_NODE_WIDTH, N, B] per node: [0] max_i sigma / Sx, [1] max_a e (NaN at node N), [2..4] the smallest margin per
+ * family at that node, [5] trace(Sx^-1 Sigma_k Sx^-1), [6], [7] 0.
+ *
+ * Two launches: a node-parallel pre-pass (one thread per (problem, node)) that evaluates the model's rows into a row table the
+ * handle owns (allocated on first use; SCP_ERR_ALLOC when it cannot be), and the covariance chain, built like the Riccati kernel:
+ * one wavefront lane per entry of Sigma, floor(64 / nx^2) problems per wavefront.  A problem's result does not depend on B or on
+ * its place in the batch, bit for bit.
+ *
+ * scp_audit_covariance_batch_host stages xd / ud / p / pp like scp_audit_batch_host and ALWAYS runs discretize! about them into
+ * the A / B- / B+ buffers of scp_lqr_gains_* (the result never depends on an earlier call; resident gains stay as they are).
+ * K: a host array, or NULL = the gains resident in the handle, by the rule and with the error texts of scp_audit_tracking_*.
+ * scp_audit_covariance_resident does the same about the trajectories the owning run's get_host would return; failed problems hold
+ * NaN in every output; no buffer of the run is modified.  *seconds: discretize! and the two kernels without the copies.
+ * SCP_ERR_BAD_ARGUMENT for a NULL, negative or non-finite sig0 / sigu / sigw, nsig <= 0 or not finite, and a NULL summary;
+ * SCP_ERR_UNSUPPORTED (with the error texts of the other audits) for IMPULSE handles and models with node parameters;
+ * SCP_ERR_BATCH_TOO_LARGE as everywhere.
+ */
+#define SCP_COV_WIDTH 16
+#define SCP_COV_NODE_WIDTH 8
+int scp_audit_covariance_batch_host(scp_handle h, int B, const double *xd, const double *ud, const double *p, const double *pp,
+                                    const double *K /* NULL = resident */, const double *sig0, const double *sigu,
+                                    const double *sigw, double nsig, double *summary, double *sig /* may be NULL */,
+                                    double *nodes /* may be NULL */, double *seconds);
+int scp_audit_covariance_resident(scp_handle h, const double *K /* NULL = resident */, const double *sig0, const double *sigu,
+                                  const double *sigw, double nsig, double *summary, double *sig /* may be NULL */,
+                                  double *nodes /* may be NULL */, double *seconds);
+/*
+ * The pre-pass for ONE problem on the host by the same code: xd[nx,N], ud[nu,N], p[np], pp[npp], K[nu,nx,N-1] (required) ->
+ * rows[nx+1, nrow, N] with nrow = ns + nl + nsoc of scp_model_query in family order (s, linear, cone), a row = g[nx] then v, and
+ * Hf[ntc, nx].  SCP_ERR_UNSUPPORTED for the models with node parameters.
+ */
+int scp_model_covariance_rows_host(int model_id, const double *model_par, int N, const double *xd, const double *ud,
+                                   const double *p, const double *pp, const double *K, double *rows, double *Hf);
+/*
+ * The chain for ONE problem on the host by the same code; no model enters it: A[nx,nx,N-1], Bm, Bp[nx,nu,N-1], K[nu,nx,N-1],
+ * nrow[3] = the rows per family of rows[nx+1, nrow[0] + nrow[1] + nrow[2], N], Hf[ntc, nx], Sx[nx], Su[nu] ->
+ * summary[SCP_COV_WIDTH], sig[nx,N] or NULL, nodes[SCP_COV_NODE_WIDTH,N] or NULL.  (nx, nu) is one of the pairs of the four
+ * auditable models -- (2,1), (6,4), (7,4), (8,3) -- SCP_ERR_UNSUPPORTED for any other.
+ */
+int scp_covariance_host(int nx, int nu, int N, const double *A, const double *Bm, const double *Bp, const double *K,
+                        const int *nrow, const double *rows, int ntc, const double *Hf, const double *Sx, const double *Su,
+                        const double *sig0, const double *sigu, const double *sigw, double nsig, double *summary,
+                        double *sig /* may be NULL */, double *nodes /* may be NULL */);
+
 /* ------------------------------------------------------------------------ */
 /* PTR: solve_subproblem! and the outer loop                                  */
 /* ------------------------------------------------------------------------ */

@@ -11,6 +11,7 @@
 #include "scp_handle.hpp"
 #include "audit_kernel.hpp"
 #include "lqr_kernel.hpp"
+#include "cov_kernel.hpp"
 #include "discretize_kernel.hpp"
 
 using namespace scp;
@@ -327,6 +328,8 @@ extern "C" int scp_problem_destroy(scp_handle h)
     for (double* p : {h->audit.flights, h->audit.dx0, h->audit.ugain, h->audit.ubias})
         if (p) (void)hipFree(p);
     for (void* p : lqr_buffers(h))
+        if (p) (void)hipFree(p);
+    for (double* p : {h->cov.rows, h->cov.Hf, h->cov.rec, h->cov.sig, h->cov.nodes, h->cov.w})
         if (p) (void)hipFree(p);
     for (auto& st : h->timing.stamps_free) { (void)hipEventDestroy(st.a); (void)hipEventDestroy(st.b); }
     for (auto& st : h->timing.stamps_pending) { (void)hipEventDestroy(st.a); (void)hipEventDestroy(st.b); }
@@ -941,4 +944,91 @@ extern "C" int scp_audit_tracking_resident(scp_handle h, const double* K, int st
     TRY(audit_resident_source(h, "scp_audit_tracking_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
     return audit_tracking_run(h, src.B, src.tr, src.d_pp, h->audit.mask, K, steps, viol_tol, D, dx0, ugain, ubias, flags, par_true, summary,
                               flights, seconds);
+}
+
+// ------------------------------------------------------------------------------------------
+// closed-loop covariance audit (cov_kernel.hpp; the kernels live in cov_api.hip)
+// ------------------------------------------------------------------------------------------
+
+// the buffers of h->cov for every problem the handle can hold: all or none
+static int cov_reserve(scp_problem* h)
+{
+    scp_problem::Cov& c = h->cov;
+    if (c.rows) return SCP_OK;
+    const size_t nx = h->info.nx, nu = h->info.nu, nrow = (size_t)h->info.ns + h->info.nl + h->info.nsoc, ntc = h->info.ntc, N = h->N,
+                 cap = h->cap, D = sizeof(double);
+    const bool ok = hipMalloc((void**)&c.rows, std::max<size_t>((nx + 1) * nrow * N * cap, 1) * D) == hipSuccess &&
+                    hipMalloc((void**)&c.Hf, std::max<size_t>(ntc * nx * cap, 1) * D) == hipSuccess &&
+                    hipMalloc((void**)&c.rec, SCP_COV_WIDTH * cap * D) == hipSuccess && hipMalloc((void**)&c.sig, nx * N * cap * D) == hipSuccess &&
+                    hipMalloc((void**)&c.nodes, SCP_COV_NODE_WIDTH * N * cap * D) == hipSuccess && hipMalloc((void**)&c.w, (2 * nx + nu) * D) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (double** p : {&c.rows, &c.Hf, &c.rec, &c.sig, &c.nodes, &c.w}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        h->err = "audit: the row table and the records of the covariance audit could not be allocated";
+        return SCP_ERR_ALLOC;
+    }
+    return SCP_OK;
+}
+
+// what both covariance entry points refuse (the audit's refusals, and the dispersions), and the buffers of the call
+static int cov_begin(scp_problem* h, const double* sig0, const double* sigu, const double* sigw, double nsig, const double* summary)
+{
+    TRY(audit_begin(h, 2, summary));
+    if (!cov_sigmas_ok(h->info.nx, h->info.nu, sig0, sigu, sigw, nsig)) {
+        h->err = "audit: sig0 >= 0, sigu >= 0, sigw >= 0, all finite, and a finite nsig > 0 are required";
+        return SCP_ERR_BAD_ARGUMENT;
+    }
+    TRY(lqr_reserve(h));
+    return cov_reserve(h);
+}
+
+// discretize! about `tr` into the buffers of h->lqr, the row pre-pass and the chain between the handle's two events, then the copies
+static int cov_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, const double* K, const double* sig0,
+                   const double* sigu, const double* sigw, double nsig, double* summary, double* sig, double* nodes, double* seconds)
+{
+    scp_problem::Lqr& q = h->lqr;
+    scp_problem::Cov& c = h->cov;
+    const size_t nx = h->info.nx, nu = h->info.nu, N = h->N;
+    const double* d_K = nullptr;
+    TRY(audit_tracking_gains(h, B, K, &d_K));
+    std::vector<double> w(2 * nx + nu);
+    std::copy(sig0, sig0 + nx, w.begin()); std::copy(sigu, sigu + nu, w.begin() + nx); std::copy(sigw, sigw + nx, w.begin() + nx + nu);
+    HIP_TRY(h, hipMemcpyAsync(c.w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
+    TRY(discretize_dev(h, B, tr.xd, tr.ud, tr.p, q.dyn, q.feas, mask));
+    CovArgs a;
+    a.B = B; a.N = h->N; a.nrow[0] = h->info.ns; a.nrow[1] = h->info.nl; a.nrow[2] = h->info.nsoc; a.ntc = h->info.ntc; a.nsig = nsig;
+    a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p; a.pp = d_pp; a.A = q.dyn.A; a.Bm = q.dyn.Bm; a.Bp = q.dyn.Bp; a.K = d_K;
+    a.Sx = h->d_Sx; a.Su = h->d_Su; a.sig0 = c.w; a.sigu = c.w + nx; a.sigw = c.w + nx + nu; a.mask = mask;
+    a.rows = c.rows; a.Hf = c.Hf; a.summary = c.rec; a.sig = sig ? c.sig : nullptr; a.nodes = nodes ? c.nodes : nullptr;
+    const int rc = cov_launch(h->model_id, h->par.data(), a, h->stream);
+    if (rc != SCP_OK) { h->err = "audit: kernel launch failed"; return rc; }
+    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(summary, c.rec, sizeof(double) * SCP_COV_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    if (sig) HIP_TRY(h, hipMemcpyAsync(sig, c.sig, sizeof(double) * nx * N * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    if (nodes) HIP_TRY(h, hipMemcpyAsync(nodes, c.nodes, sizeof(double) * SCP_COV_NODE_WIDTH * N * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // w is on this stack frame
+    stamps_collect(h);
+    return elapsed_out(h, seconds);
+}
+
+extern "C" int scp_audit_covariance_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
+                                               const double* K, const double* sig0, const double* sigu, const double* sigw, double nsig,
+                                               double* summary, double* sig, double* nodes, double* seconds)
+{
+    TRY(cov_begin(h, sig0, sigu, sigw, nsig, summary));
+    TRY(audit_stage_host(h, B, xd, ud, p, pp));
+    return cov_run(h, B, traj_sol(h), h->audit.pp, nullptr, K, sig0, sigu, sigw, nsig, summary, sig, nodes, seconds);
+}
+
+extern "C" int scp_audit_covariance_resident(scp_handle h, const double* K, const double* sig0, const double* sigu, const double* sigw,
+                                             double nsig, double* summary, double* sig, double* nodes, double* seconds)
+{
+    TRY(cov_begin(h, sig0, sigu, sigw, nsig, summary));
+    AuditSource src;
+    TRY(audit_resident_source(h, "scp_audit_covariance_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
+    return cov_run(h, src.B, src.tr, src.d_pp, h->audit.mask, K, sig0, sigu, sigw, nsig, summary, sig, nodes, seconds);
 }

@@ -1,6 +1,7 @@
 // The problem handle of the C-ABI library (include/scp_mi355x.h) as its translation units share it: internal, not installed.
 //
 //   scp_api.hip      model queries, handle life cycle, kernel time stamps, discretize! and propagate (K1), scp_audit_*, scp_lqr_gains_*
+//                    (the kernels of the last two live in audit_api.hip, lqr_api.hip and cov_api.hip)
 //   ptr_api.hip      structured PTR path (K2-K4)
 //   guess_api.hip    initial guesses (every model's straight line, the Starship reference guess)
 //   scp_generic.hip  subproblem handles (scp_sub) and the SCvx / GuSTO / generic-PTR loops
@@ -100,6 +101,13 @@ struct scp_problem {
         double *K = nullptr, *Kin = nullptr, *info = nullptr, *w = nullptr;
         int B = 0;
     } lqr;
+
+    // ---- scp_api.hip: covariance audit (scp_audit_covariance_*): the row table rows [(nx+1) nrow N cap], Hf [ntc nx cap], the
+    // records rec [SCP_COV_WIDTH cap], sig [nx N cap], nodes [SCP_COV_NODE_WIDTH N cap] and w = sig0 [nx], sigu [nu], sigw [nx].
+    // Built together on first use, not in h->allocs: scp_problem_destroy frees them.  The discretisation and the gains are h->lqr's ----
+    struct Cov {
+        double *rows = nullptr, *Hf = nullptr, *rec = nullptr, *sig = nullptr, *nodes = nullptr, *w = nullptr;
+    } cov;
 
     // ---- trajectories: allocated by scp_api.hip at create; written by the run that owns them (h->run: ptr_api.hip or
     // scp_generic.hip) and, between runs, by the stand-alone entry points of every unit (sol_* as their staging buffers) ----

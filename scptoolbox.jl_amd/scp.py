@@ -703,6 +703,111 @@ def audit_tracking_resident(pbm, gains=None, steps=None, dx0=None, ugain=None, u
     return a
 
 
+COV_WIDTH, COV_NODE_WIDTH = 16, 8      # SCP_COV_WIDTH, SCP_COV_NODE_WIDTH
+_COV_FIELDS = (None, "sigma_max", "sigma_node", "sigma_state", "effort", "effort_node", "margin_s", "margin_s_node", "margin_lin",
+               "margin_lin_node", "margin_soc", "margin_soc_node", "terminal_sigma", "trace_final", "n_below")
+
+
+class CovarianceAuditBatch:
+    """The closed-loop covariance audit of a batch (scp_audit_covariance_batch_host / scp_audit_covariance_resident,
+    include/scp_mi355x.h).  Named views [B] of the summary records: sigma_max = the largest state 1-sigma in units of Sx with its
+    1-based sigma_node and sigma_state, effort = the largest 1-sigma feedback effort in units of Su and effort_node, margin_s /
+    margin_lin / margin_soc = the smallest distance of a row of that family from its boundary in sigmas and margin_*_node
+    (+Inf and 0 without rows), terminal_sigma = the largest 1-sigma of the terminal conditions, trace_final =
+    trace(Sx^-1 Sigma_N Sx^-1), n_below = the (node, row) pairs with a margin below `nsig`.  `failed` [B] = something was not
+    finite (the other fields are NaN); skipped (failed SCP) problems hold NaN everywhere.  `raw` is the [B, 16] array itself;
+    `sig` [B, N, nx] and `nodes` [B, N, 8] hold the state 1-sigma values and the per-node records when they were asked for, else
+    None."""
+
+    def __init__(self, raw, nsig, sig=None, nodes=None):
+        self.raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1, COV_WIDTH)
+        self.nsig = float(nsig)
+        for j, name in enumerate(_COV_FIELDS):
+            if name is not None:
+                setattr(self, name, self.raw[:, j])
+        self.sig = None if sig is None else np.ascontiguousarray(sig, dtype=np.float64)
+        self.nodes = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.float64).reshape(len(self), -1, COV_NODE_WIDTH)
+        self.seconds = 0.0
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    @property
+    def failed(self):
+        return self.raw[:, 0] == 1.0
+
+    @property
+    def skipped(self):
+        return np.isnan(self.raw[:, 0])
+
+
+def _cov_sigmas(pbm, sig0, sigu, sigw):
+    """sig0 is required; sigu and sigw default to zeros"""
+    if sig0 is None:
+        raise ValueError("sig0, the initial 1-sigma of every state, is required")
+    sigu = np.zeros(pbm.nu) if sigu is None else sigu
+    sigw = np.zeros(pbm.nx) if sigw is None else sigw
+    sig0, sigu, sigw = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (sig0, sigu, sigw))
+    if sig0.size != pbm.nx or sigw.size != pbm.nx or sigu.size != pbm.nu:
+        raise ValueError("sig0 and sigw hold nx = %d values, sigu nu = %d" % (pbm.nx, pbm.nu))
+    return sig0, sigu, sigw
+
+
+def audit_covariance(sol, pbm, gains=None, sig0=None, sigu=None, sigw=None, nsig=3.0, per_node=False, pp=None):
+    """Closed-loop covariance audit of the batch solution `sol` (scp_audit_covariance_batch_host): discretize! about it, then the
+    covariance recursion Sigma_{k+1} = A_cl Sigma_k A_cl' + Gam diag(sigu^2) Gam' + diag(sigw^2) with A_cl = A_k - Gam K_k on the
+    device, from Sigma_1 = diag(sig0^2).  `gains` = a GainBatch, an array [B, N-1, nu, nx], or None for the gains the last
+    `lqr_gains` call on this problem left in the handle; sig0[nx], sigu[nu], sigw[nx] in physical units (sigu, sigw: None = 0);
+    `nsig` = the sigma level of n_below.  per_node=True also returns `sig` and `nodes`.  `sol.status` masks as in `audit`.
+    Returns a CovarianceAuditBatch."""
+    xd = np.ascontiguousarray(sol.xd, dtype=np.float64)
+    ud = np.ascontiguousarray(sol.ud, dtype=np.float64)
+    p = np.ascontiguousarray(sol.p, dtype=np.float64)
+    B, N = xd.shape[0], pbm.pars.N
+    pp = np.ascontiguousarray(np.tile(pbm.traj.mdl.nominal_pp()[None], (B, 1)) if pp is None else pp, dtype=np.float64)
+    assert pp.shape[0] == B
+    sig0, sigu, sigw = _cov_sigmas(pbm, sig0, sigu, sigw)
+    K = _tracking_gains(pbm, B, gains)
+    out = np.zeros((B, COV_WIDTH))
+    sig = np.zeros((B, N, pbm.nx)) if per_node else None
+    nodes = np.zeros((B, N, COV_NODE_WIDTH)) if per_node else None
+    sec = ctypes.c_double(0.0)
+    rc = _lib.lib().scp_audit_covariance_batch_host(pbm.handle, B, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np > 0 else None,
+                                                   _ptr(pp) if pbm.info.npp > 0 else None, _ptr(K), _ptr(sig0), _ptr(sigu), _ptr(sigw),
+                                                   float(nsig), _ptr(out), _ptr(sig), _ptr(nodes), ctypes.byref(sec))
+    _lib.check(rc, pbm.handle)
+    status = getattr(sol, "status", None)
+    if status is not None:
+        bad = ~np.array([str(st).startswith("SCP_SOLVED") for st in status])
+        out[bad] = np.nan
+        if per_node:
+            sig[bad] = np.nan
+            nodes[bad] = np.nan
+    a = CovarianceAuditBatch(out, nsig, sig, nodes)
+    a.seconds = sec.value
+    return a
+
+
+def audit_covariance_resident(pbm, gains=None, sig0=None, sigu=None, sigw=None, nsig=3.0, per_node=False):
+    """The same for the batch RESIDENT in the handle (scp_audit_covariance_resident), with `gains` None = those of the last
+    `lqr_gains_resident`; failed problems NaN; the run is left untouched.  Returns a CovarianceAuditBatch."""
+    B, N = getattr(pbm, "resident_B", None), pbm.pars.N
+    if B is None:
+        raise _lib.ScpError(1, "audit_covariance_resident: no run has been started on this problem")
+    sig0, sigu, sigw = _cov_sigmas(pbm, sig0, sigu, sigw)
+    K = _tracking_gains(pbm, B, gains)
+    cap = max(pbm.batch_capacity, B)      # room for the library's own batch, whatever this module believes
+    out = np.zeros((cap, COV_WIDTH))
+    sig = np.zeros((cap, N, pbm.nx)) if per_node else None
+    nodes = np.zeros((cap, N, COV_NODE_WIDTH)) if per_node else None
+    sec = ctypes.c_double(0.0)
+    _lib.check(_lib.lib().scp_audit_covariance_resident(pbm.handle, _ptr(K), _ptr(sig0), _ptr(sigu), _ptr(sigw), float(nsig), _ptr(out),
+                                                       _ptr(sig), _ptr(nodes), ctypes.byref(sec)), pbm.handle)
+    a = CovarianceAuditBatch(out[:B].copy(), nsig, sig[:B].copy() if per_node else None, nodes[:B].copy() if per_node else None)
+    a.seconds = sec.value
+    return a
+
+
 def device_guess(pbm, pp):
     """`traj.guess(N)` for a Monte-Carlo batch evaluated on the device (scp_guess_batch_host): pp[B,npp] ->
     (xd[B,N,nx], ud[B,N,nu], p[B,np])."""
