@@ -531,6 +531,70 @@ int scp_covariance_host(int nx, int nu, int N, const double *A, const double *Bm
                         const double *sig0, const double *sigu, const double *sigw, double nsig, double *summary,
                         double *sig /* may be NULL */, double *nodes /* may be NULL */);
 
+/*
+ * Monte-Carlo audit: D >= 2 NOISY closed-loop flights per problem through the nonlinear dynamics, under exactly the disturbance
+ * model of scp_audit_covariance_*, and the sample statistics of the node errors -- the check of that audit's linear prediction.
+ * FOH handles of the four auditable models; sig0 / sigu / sigw as there (shared by the batch, physical units), K and steps as
+ * in scp_audit_tracking_*.  Flight d = 1 .. D is the tracking flight with ugain = 1, ubias = 0 and
+ *   1. x = xd[:,1] + sig0 o xi0
+ *   2. at node k < N the hold update du = -K_k (x - xd[:,k]), then w_k = sigu o xiu_k is drawn
+ *   3. the flown input is (u_foh(t) + du) + w_k over the whole interval, stage times included; the dynamics, the U rows, the cones
+ *      and Gamma see it; the effort is measured on du alone
+ *   4. after the last RK4 step of interval k and BEFORE that sample is audited: x += sigw o xiw_{k+1}; the sample at node k+1 and
+ *      that node's tracking error see the kicked state
+ * Linearised, this is the Sigma recursion of the covariance audit (Gam = B- + B+ is the response to an input offset held over the
+ * interval).  The xi are standard normals of a counter-based generator inside the kernel: Philox4x32-10 keyed by the two halves
+ * of `seed`, counter (pair index i / 2, node k, d - 1, kind) with kind 0 = xi0 (k = 0), 1 = xiu_k (k = 1 .. N-1), 2 = xiw_k
+ * (k = 2 .. N); from the output words r0 .. r3, u1 = ((r0 >> 5) 2^26 + (r1 >> 6) + 0.5) 2^-53 and u2 likewise from r2, r3;
+ * rho = sqrt(-2 ln u1), component 2q = rho cos(2 pi u2), component 2q+1 = rho sin(2 pi u2).  A draw depends on (seed, kind, k, d,
+ * i) only: every problem of a batch sees the same disturbances (common random numbers: the right default for ranking the
+ * problems of a batch), and a problem's result does not depend on B or on its place in the batch, bit for bit.
+ * scp_mc_draws_host returns the n normals z of one draw and, when asked, the 4 ceil(n / 2) output words behind them.
+ *
+ * Nothing of size N D B is stored: at every node the errors e = x - xd[:,k] and du / Su of the flights are reduced across the
+ * wavefront in registers by a fixed tree (the xor butterfly over the lanes 0 .. 63; a problem owns ceil(D / 64) whole wavefronts,
+ * whose partial sums are added in wavefront order).  A flight COUNTS at node k when e and (k < N) du / Su are all finite.
+ * moments[1 + 2 nx + nu, N, B] (NULL: not copied), per node k:
+ *   [0]            n_k, the flights counted
+ *   [1 .. nx]      the sample mean m_i of e_i
+ *   [nx+1 .. 2nx]  the sample standard deviation s_i = sqrt(max((sum e_i^2 - (sum e_i)^2 / n_k) / (n_k - 1), 0))
+ *   [2nx+1 ..]     rms_a = sqrt(sum (du_a / Su_a)^2 / n_k); NaN at node N
+ * all NaN but [0] where n_k < 2.  stat[SCP_MC_STAT_WIDTH, B]; nodes and indices 1-based, ties go to the smallest node, then the
+ * smallest index; a maximum to which no node contributes is NaN with the indices 0:
+ *   [0..2]     max over k, i of s_i / Sx[i]; its node; its state
+ *   [3], [4]   max over k, i of |m_i| / Sx[i]; its node -- the bias that nonlinearity puts on the mean, which the linear analysis
+ *              cannot see
+ *   [5], [6]   max over k < N and a of rms_a; its node
+ *   [7]        min over k of n_k
+ * flights[SCP_AUDIT_WIDTH, D, B] (may be NULL): the records of scp_audit_tracking_*, unchanged in layout; summary
+ * [SCP_AUDIT_WIDTH, B]: their fold as there, with [13] = 4.0.
+ *
+ * Staging, masking, the resident gains (K = NULL), the error texts and *seconds (the three kernels without the copies) follow
+ * scp_audit_tracking_*; the partial sums live in a buffer the handle owns, allocated on first use and rebuilt when D needs more
+ * wavefronts (SCP_ERR_ALLOC when it cannot be).  SCP_ERR_BAD_ARGUMENT for D < 2, steps < 1, a NULL, negative or non-finite
+ * sigma and a NULL summary or stat; SCP_ERR_UNSUPPORTED (with the other audits' texts) for IMPULSE handles and the models with node
+ * parameters; SCP_ERR_UNKNOWN_MODEL and SCP_ERR_BATCH_TOO_LARGE as everywhere.
+ */
+#define SCP_MC_STAT_WIDTH 8
+int scp_audit_montecarlo_batch_host(scp_handle h, int B, const double *xd, const double *ud, const double *p, const double *pp,
+                                    const double *K /* NULL = resident */, int steps, double viol_tol, int D, uint64_t seed,
+                                    const double *sig0, const double *sigu, const double *sigw, double *summary, double *stat,
+                                    double *moments /* may be NULL */, double *flights /* may be NULL */, double *seconds);
+int scp_audit_montecarlo_resident(scp_handle h, const double *K /* NULL = resident */, int steps, double viol_tol, int D,
+                                  uint64_t seed, const double *sig0, const double *sigu, const double *sigw, double *summary,
+                                  double *stat, double *moments /* may be NULL */, double *flights /* may be NULL */,
+                                  double *seconds);
+/* The same outputs for ONE problem on the host by the same code and the same tree, no device: summary[16], stat[8],
+ * moments[1 + 2 nx + nu, N] or NULL, flights[16, D] or NULL; K[nu,nx,N-1] is required. */
+int scp_model_audit_montecarlo_host(int model_id, const double *model_par, int N, const double *xd, const double *ud,
+                                    const double *p, const double *pp, const double *Sx, const double *Su, const double *K,
+                                    int steps, double viol_tol, int D, uint64_t seed, const double *sig0, const double *sigu,
+                                    const double *sigw, double *summary, double *stat, double *moments /* may be NULL */,
+                                    double *flights /* [16, D] or NULL */);
+/* z[n] of the draw (seed, kind, k, d) and, when words is not NULL, its 4 ceil(n / 2) Philox output words; SCP_ERR_BAD_ARGUMENT
+ * for kind outside 0 .. 2, k < 0, d < 1, n < 1 or a NULL z. */
+int scp_mc_draws_host(uint64_t seed, int kind, int k, int d, int n, double *z, unsigned *words /* may be NULL */);
+
 /* ------------------------------------------------------------------------ */
 /* PTR: solve_subproblem! and the outer loop                                  */
 /* ------------------------------------------------------------------------ */

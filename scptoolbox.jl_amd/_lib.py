@@ -114,6 +114,7 @@ EXPORTS = [
     "scp_lqr_gains_batch_host", "scp_lqr_gains_resident", "scp_lqr_gains_host",
     "scp_audit_tracking_batch_host", "scp_audit_tracking_resident", "scp_model_audit_tracking_host",
     "scp_audit_covariance_batch_host", "scp_audit_covariance_resident", "scp_model_covariance_rows_host", "scp_covariance_host",
+    "scp_audit_montecarlo_batch_host", "scp_audit_montecarlo_resident", "scp_model_audit_montecarlo_host", "scp_mc_draws_host",
     "scp_ptr_get_virtual_controls_host", "scp_ptr_iterate_async", "scp_ptr_poll", "scp_ptr_poll_iteration", "scp_guess_batch_host", "scp_guess_failures",
     "scp_sub_source_layout", "scp_sub_create", "scp_sub_destroy", "scp_sub_stats", "scp_sub_last_error", "scp_sub_solve_batch_host",
     "scp_scvx_init_host", "scp_scvx_iterate", "scp_scvx_get_host",
@@ -206,6 +207,13 @@ def lib():
         L.scp_model_covariance_rows_host.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 7
         L.scp_covariance_host.argtypes = ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6 + [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_double]
                                           + [ctypes.c_void_p] * 3)
+        L.scp_audit_montecarlo_batch_host.argtypes = ([ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                                      ctypes.c_uint64] + [ctypes.c_void_p] * 7 + [c_double_p])
+        L.scp_audit_montecarlo_resident.argtypes = ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_uint64]
+                                                    + [ctypes.c_void_p] * 7 + [c_double_p])
+        L.scp_model_audit_montecarlo_host.argtypes = ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 7
+                                                      + [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_uint64] + [ctypes.c_void_p] * 7)
+        L.scp_mc_draws_host.argtypes = [ctypes.c_uint64] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
         L.scp_ptr_get_virtual_controls_host.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 6
         L.scp_get_kernel_timing.argtypes = [ctypes.c_void_p, c_double_p, ctypes.POINTER(ctypes.c_long), ctypes.c_int]
         L.scp_debug_get_stage_problem.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,

@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "../../include/scp_mi355x.h"
+#include "mc_rng.hpp"
 #include "models/model_common.hpp"
 
 namespace scp {
@@ -176,8 +177,8 @@ SCP_DEV double audit_phi(const double (&x)[M::nx], const double* pb, const doubl
 }
 
 // ------------------------------------------------------------------------------------------------
-// ONE flight of ONE problem, the body of the single-shooting, the dispersed and the tracking audit, on the device and in the
-// host twins.  The flight starts at the first node and takes res - 1 RK4 steps over LinRange(0, 1, res); the input is the
+// ONE flight of ONE problem, the body of the single-shooting, the dispersed, the tracking and the Monte-Carlo audit, on the device
+// and in the host twins.The flight starts at the first node and takes res - 1 RK4 steps over LinRange(0, 1, res); the input is the
 // first-order hold of ud with propagate_foh_kernel's clamp and interval search, stage times included.  The state is sampled
 // before the first and after every step: the sample at time t is audited with the model functions of the last grid node <= t,
 // decided against the exact grid values (the k_j rule), and the running cost is integrated by the trapezoidal rule over the
@@ -193,35 +194,52 @@ SCP_DEV double audit_phi(const double (&x)[M::nx], const double* pb, const doubl
 //              at a node is audited with the hold that was in force over the step that ended there.  out[12], [13] the largest
 //              ||Su^-1 du||_inf over the hold updates and its node, [14], [15] the largest ||Sx^-1 (x(t_k) - xd[:,k])||_inf
 //              over the nodes 1 .. N and its node (strict >: the first wins).  With K = 0 it is the dispersed flight.
-// Only these four places -- the initial state, one expression of `input`, the `node` calls and out[12..15] -- stand behind
-// `if constexpr`; what a mode does not use (ug, ubs, du, effort .. k_track, node) is dead there, and every kernel's machine code
-// is what its own copy of this body gave ("One flight body").  Do NOT merge further: sharing the RK4 step with
+//   montecarlo the tracking flight with gain = 1, bias = 0 under the disturbance model of the covariance audit (cov_kernel.hpp),
+//              drawn inside the flight by mc_rng.hpp for flight mc.d: x(0) = xd[:,1] + sig0 o xi0; at node k < N, after the hold
+//              update, w_k = sigu o xiu_k is drawn and the flown input is (u_foh(t) + du) + w_k over the whole interval, stage
+//              times included (dynamics, U rows, cones and Gamma see it; the effort is measured on du alone); after the last RK4
+//              step of interval k and BEFORE that sample is audited x += sigw o xiw_{k+1}, then M::action(x): the sample at node
+//              k+1 and the node's tracking error see the kicked state.  Linearised, this is the Sigma recursion of
+//              scp_audit_covariance_*: Gam = B- + B+ is the response to an input offset held over the interval.  At every node
+//              mc.node(k, N, e, du / Su, finite) receives the node error -- on the device the cross-flight reduction
+//              (mc_kernel.hpp) -- so every lane of a wavefront must reach it: the loops below have uniform trip counts.
+// Only these places -- the initial state, one expression of `input`, the `node` calls with the draws, the kick and out[12..15] --
+// stand behind `if constexpr`; what a mode does not use (ug, ubs, du, wk, effort .. k_track, node, mc) is dead there, and every
+// kernel's machine code is what its own copy of this body gave ("One flight body").  Do NOT merge further: sharing the RK4 step with
 // audit_interval_one, one argument struct for the dispersed and the tracking kernel, or one body with the interval audit
 // each changes the register allocation of kernels that sit at their VGPR limit (measured, same place).
 // ------------------------------------------------------------------------------------------------
-enum class AuditFlight { nominal, dispersed, tracking };
+enum class AuditFlight { nominal, dispersed, tracking, montecarlo };
+struct AuditNoNoise {};      // the `mc` of the three deterministic modes
 
 // xd[nx,N], ud[nu,N], p[np], pp[npp], Sx[nx] -> out[SCP_AUDIT_WIDTH]; dispersed and tracking: dx0[nx], gain[nu], bias[nu], each
-// may be nullptr; tracking: Su[nu], Kg[nu,nx,N-1]
-template <class M, AuditFlight MODE>
+// may be nullptr; tracking: Su[nu], Kg[nu,nx,N-1]; montecarlo: those two and mc = {seed, d, sig0[nx], sigu[nu], sigw[nx], node(...)}
+template <class M, AuditFlight MODE, class Mc = AuditNoNoise>
 SCP_DEV void audit_flight_one(const typename M::Params& par, int N, int res_or_steps, double viol_tol, const double* xd,
                               const double* ub, const double* pb, const double* pp, const double* Sx, double* out, const double* dx0 = nullptr,
                               const double* gain = nullptr, const double* bias = nullptr, const double* Su = nullptr,
-                              const double* Kg = nullptr)
+                              const double* Kg = nullptr, Mc&& mc = Mc{})
 {
     static_assert(M::np_node == 0, "a row of node k would read that node's own parameters: undefined between the nodes");
     constexpr int nx = M::nx, nu = M::nu, np = M::np, npa = np > 0 ? np : 1, npF = M::npF, npFa = npF > 0 ? npF : 1, ng = M::ng;
-    constexpr bool tracking = MODE == AuditFlight::tracking;
+    constexpr bool noisy = MODE == AuditFlight::montecarlo, tracking = MODE == AuditFlight::tracking || noisy;
     const int steps = res_or_steps, res = tracking ? steps * (N - 1) + 1 : res_or_steps;
 
-    double x[nx], ug[nu], ubs[nu], du[nu];
+    double x[nx], ug[nu], ubs[nu], du[nu], wk[nu];
+    if constexpr (noisy) {
+        double xi[nx];
+        mc_normals<nx>(mc.seed, 0, 0, mc.d, xi);
 #pragma unroll
-    for (int i = 0; i < nx; i++) {
-        if constexpr (MODE == AuditFlight::nominal) x[i] = xd[i];
-        else x[i] = xd[i] + (dx0 != nullptr ? dx0[i] : 0.0);
+        for (int i = 0; i < nx; i++) x[i] = xd[i] + mc.sig0[i] * xi[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < nx; i++) {
+            if constexpr (MODE == AuditFlight::nominal) x[i] = xd[i];
+            else x[i] = xd[i] + (dx0 != nullptr ? dx0[i] : 0.0);
+        }
     }
 #pragma unroll
-    for (int i = 0; i < nu; i++) { ug[i] = gain != nullptr ? gain[i] : 1.0; ubs[i] = bias != nullptr ? bias[i] : 0.0; du[i] = 0.0; }
+    for (int i = 0; i < nu; i++) { ug[i] = gain != nullptr ? gain[i] : 1.0; ubs[i] = bias != nullptr ? bias[i] : 0.0; du[i] = 0.0; wk[i] = 0.0; }
     // u(t) and f(t, x): propagate_foh_kernel's own, then the mode's feedback, gain and bias
     auto input = [&](double t, double (&u)[nu]) {
         const double g0 = audit_linrange(0.0, 1.0, N, 0), g1 = audit_linrange(0.0, 1.0, N, N - 1);
@@ -237,6 +255,7 @@ SCP_DEV void audit_flight_one(const typename M::Params& par, int N, int res_or_s
         for (int i = 0; i < nu; i++) {
             if constexpr (MODE == AuditFlight::nominal) u[i] = c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i];
             else if constexpr (MODE == AuditFlight::dispersed) u[i] = ug[i] * (c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i]) + ubs[i];
+            else if constexpr (noisy) u[i] = ((c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i]) + du[i]) + wk[i];
             else u[i] = ug[i] * ((c * ub[(long)(k - 1) * nu + i] + (1.0 - c) * ub[(long)k * nu + i]) + du[i]) + ubs[i];
         }
     };
@@ -270,12 +289,19 @@ SCP_DEV void audit_flight_one(const typename M::Params& par, int N, int res_or_s
     [[maybe_unused]] auto node = [&](int k) {
         const double* xk = xd + (long)(k - 1) * nx;
         double e[nx], terr = 0.0;
+        [[maybe_unused]] double dus[nu];
+        [[maybe_unused]] bool fin = true;      // montecarlo: e and du / Su of this node are all finite
 #pragma unroll
         for (int i = 0; i < nx; i++) {
             e[i] = x[i] - xk[i];
             const double d = e[i] / Sx[i];
             acc.bad = acc.bad || !__builtin_isfinite(d);
+            if constexpr (noisy) fin = fin && __builtin_isfinite(e[i]);
             terr = fmax(terr, fabs(d));
+        }
+        if constexpr (noisy) {
+#pragma unroll
+            for (int a = 0; a < nu; a++) dus[a] = 0.0;
         }
         if (terr > track) { track = terr; k_track = (double)k; }
         if (k < N) {
@@ -289,9 +315,19 @@ SCP_DEV void audit_flight_one(const typename M::Params& par, int N, int res_or_s
                 du[a] = -s;
                 const double d = du[a] / Su[a];
                 acc.bad = acc.bad || !__builtin_isfinite(d);
+                if constexpr (noisy) { dus[a] = d; fin = fin && __builtin_isfinite(d); }
                 eff = fmax(eff, fabs(d));
             }
             if (eff > effort) { effort = eff; k_effort = (double)k; }
+        }
+        if constexpr (noisy) {
+            mc.node(k, N, e, dus, fin);
+            if (k < N) {
+                double xi[nu];
+                mc_normals<nu>(mc.seed, 1, k, mc.d, xi);
+#pragma unroll
+                for (int a = 0; a < nu; a++) wk[a] = mc.sigu[a] * xi[a];
+            }
         }
     };
 
@@ -316,6 +352,15 @@ SCP_DEV void audit_flight_one(const typename M::Params& par, int N, int res_or_s
 #pragma unroll
         for (int i = 0; i < nx; i++) x[i] = x[i] + h / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
         M::action(x);
+        if constexpr (noisy) {
+            if (j % steps == 0) {                         // the step that arrives at node j / steps + 1
+                double xi[nx];
+                mc_normals<nx>(mc.seed, 2, j / steps + 1, mc.d, xi);
+#pragma unroll
+                for (int i = 0; i < nx; i++) x[i] += mc.sigw[i] * xi[i];
+                M::action(x);
+            }
+        }
         const double gam = sample(tp);
         cost_int += 0.5 * h * (gam + gam_prev);          // trapz over tc (helper.jl:560-568), normalised time like the discrete J
         gam_prev = gam;

@@ -12,6 +12,7 @@
 #include "audit_kernel.hpp"
 #include "lqr_kernel.hpp"
 #include "cov_kernel.hpp"
+#include "mc_kernel.hpp"
 #include "discretize_kernel.hpp"
 
 using namespace scp;
@@ -330,6 +331,8 @@ extern "C" int scp_problem_destroy(scp_handle h)
     for (void* p : lqr_buffers(h))
         if (p) (void)hipFree(p);
     for (double* p : {h->cov.rows, h->cov.Hf, h->cov.rec, h->cov.sig, h->cov.nodes, h->cov.w})
+        if (p) (void)hipFree(p);
+    for (double* p : {h->mc.part, h->mc.moments, h->mc.stat, h->mc.w})
         if (p) (void)hipFree(p);
     for (auto& st : h->timing.stamps_free) { (void)hipEventDestroy(st.a); (void)hipEventDestroy(st.b); }
     for (auto& st : h->timing.stamps_pending) { (void)hipEventDestroy(st.a); (void)hipEventDestroy(st.b); }
@@ -1031,4 +1034,102 @@ extern "C" int scp_audit_covariance_resident(scp_handle h, const double* K, cons
     AuditSource src;
     TRY(audit_resident_source(h, "scp_audit_covariance_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
     return cov_run(h, src.B, src.tr, src.d_pp, h->audit.mask, K, sig0, sigu, sigw, nsig, summary, sig, nodes, seconds);
+}
+
+// ------------------------------------------------------------------------------------------
+// Monte-Carlo audit (mc_kernel.hpp; the kernels live in mc_api.hip)
+// ------------------------------------------------------------------------------------------
+
+// the buffers of h->mc for W wavefronts per problem and every problem the handle can hold: all or none
+static int mc_reserve(scp_problem* h, int W)
+{
+    scp_problem::Mc& c = h->mc;
+    if (W <= c.W) return SCP_OK;
+    for (double** p : {&c.part, &c.moments, &c.stat, &c.w}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    c.W = 0;
+    const size_t nx = h->info.nx, nu = h->info.nu, nv = 1 + 2 * nx + nu, N = h->N, cap = h->cap, D = sizeof(double);
+    const bool ok = hipMalloc((void**)&c.part, nv * N * (size_t)W * cap * D) == hipSuccess && hipMalloc((void**)&c.moments, nv * N * cap * D) == hipSuccess &&
+                    hipMalloc((void**)&c.stat, SCP_MC_STAT_WIDTH * cap * D) == hipSuccess && hipMalloc((void**)&c.w, (2 * nx + nu) * D) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (double** p : {&c.part, &c.moments, &c.stat, &c.w}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        h->err = "audit: the partial sums and the records of the Monte-Carlo audit could not be allocated";
+        return SCP_ERR_ALLOC;
+    }
+    c.W = W;
+    return SCP_OK;
+}
+
+// what both Monte-Carlo entry points refuse (the tracking audit's refusals, D < 2, the dispersions, a NULL stat)
+static int mc_begin(scp_problem* h, int steps, int D, const double* sig0, const double* sigu, const double* sigw, const double* summary,
+                    const double* stat)
+{
+    TRY(audit_tracking_begin(h, steps, D, 0u, summary));
+    if (D < 2 || !stat) { h->err = "audit: D >= 2 flights and the stat array are required"; return SCP_ERR_BAD_ARGUMENT; }
+    if (!mc_sigmas_ok(h->info.nx, h->info.nu, sig0, sigu, sigw)) {
+        h->err = "audit: sig0 >= 0, sigu >= 0, sigw >= 0, all finite, are required";
+        return SCP_ERR_BAD_ARGUMENT;
+    }
+    return SCP_OK;
+}
+
+// the three kernels between the handle's two events, then the copies
+static int mc_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, const double* K, int steps, double viol_tol,
+                  int D, uint64_t seed, const double* sig0, const double* sigu, const double* sigw, double* summary, double* stat,
+                  double* moments, double* flights, double* seconds)
+{
+    scp_problem::Mc& c = h->mc;
+    const size_t nx = h->info.nx, nu = h->info.nu, nv = 1 + 2 * nx + nu, N = h->N;
+    const int W = (D + 63) / 64;
+    const double* d_K = nullptr;
+    TRY(audit_tracking_gains(h, B, K, &d_K));
+    TRY(audit_dispersed_reserve(h, D));
+    TRY(mc_reserve(h, W));
+    std::vector<double> w(2 * nx + nu);
+    std::copy(sig0, sig0 + nx, w.begin()); std::copy(sigu, sigu + nu, w.begin() + nx); std::copy(sigw, sigw + nx, w.begin() + nx + nu);
+    HIP_TRY(h, hipMemcpyAsync(c.w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, h->stream));
+    McArgs a;
+    a.B = B; a.N = h->N; a.steps = steps; a.D = D; a.W = W; a.seed = seed; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
+    a.pp = d_pp; a.Sx = h->d_Sx; a.Su = h->d_Su; a.K = d_K; a.sig0 = c.w; a.sigu = c.w + nx; a.sigw = c.w + nx + nu; a.mask = mask;
+    a.flights = h->audit.flights; a.audit = h->audit.rec; a.part = c.part; a.moments = c.moments; a.stat = c.stat;
+    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
+    const int rc = mc_launch(h->model_id, h->par.data(), a, h->stream);
+    if (rc != SCP_OK) { h->err = "audit: kernel launch failed"; return rc; }
+    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(summary, h->audit.rec, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(stat, c.stat, sizeof(double) * SCP_MC_STAT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    if (moments) HIP_TRY(h, hipMemcpyAsync(moments, c.moments, sizeof(double) * nv * N * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    if (flights)
+        HIP_TRY(h, hipMemcpyAsync(flights, h->audit.flights, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)D * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // w is on this stack frame
+    stamps_collect(h);
+    return elapsed_out(h, seconds);
+}
+
+extern "C" int scp_audit_montecarlo_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
+                                               const double* K, int steps, double viol_tol, int D, uint64_t seed, const double* sig0,
+                                               const double* sigu, const double* sigw, double* summary, double* stat, double* moments,
+                                               double* flights, double* seconds)
+{
+    TRY(mc_begin(h, steps, D, sig0, sigu, sigw, summary, stat));
+    TRY(audit_stage_host(h, B, xd, ud, p, pp));
+    return mc_run(h, B, traj_sol(h), h->audit.pp, nullptr, K, steps, viol_tol, D, seed, sig0, sigu, sigw, summary, stat, moments, flights,
+                  seconds);
+}
+
+extern "C" int scp_audit_montecarlo_resident(scp_handle h, const double* K, int steps, double viol_tol, int D, uint64_t seed,
+                                             const double* sig0, const double* sigu, const double* sigw, double* summary, double* stat,
+                                             double* moments, double* flights, double* seconds)
+{
+    TRY(mc_begin(h, steps, D, sig0, sigu, sigw, summary, stat));
+    AuditSource src;
+    TRY(audit_resident_source(h, "scp_audit_montecarlo_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
+    return mc_run(h, src.B, src.tr, src.d_pp, h->audit.mask, K, steps, viol_tol, D, seed, sig0, sigu, sigw, summary, stat, moments, flights,
+                  seconds);
 }

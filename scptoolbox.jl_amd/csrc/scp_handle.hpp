@@ -1,7 +1,7 @@
 // The problem handle of the C-ABI library (include/scp_mi355x.h) as its translation units share it: internal, not installed.
 //
 //   scp_api.hip      model queries, handle life cycle, kernel time stamps, discretize! and propagate (K1), scp_audit_*, scp_lqr_gains_*
-//                    (the kernels of the last two live in audit_api.hip, lqr_api.hip and cov_api.hip)
+//                    (the kernels of the last two live in audit_api.hip, lqr_api.hip, cov_api.hip and mc_api.hip)
 //   ptr_api.hip      structured PTR path (K2-K4)
 //   guess_api.hip    initial guesses (every model's straight line, the Starship reference guess)
 //   scp_generic.hip  subproblem handles (scp_sub) and the SCvx / GuSTO / generic-PTR loops
@@ -108,6 +108,15 @@ struct scp_problem {
     struct Cov {
         double *rows = nullptr, *Hf = nullptr, *rec = nullptr, *sig = nullptr, *nodes = nullptr, *w = nullptr;
     } cov;
+
+    // ---- scp_api.hip: Monte-Carlo audit (scp_audit_montecarlo_*): the wavefront partials part [NV N W cap] with NV = 1 + 2 nx + nu,
+    // the node records moments [NV N cap], stat [SCP_MC_STAT_WIDTH cap] and w = sig0 [nx], sigu [nu], sigw [nx].  Built together on
+    // first use and rebuilt when a call needs more than W wavefronts per problem, not in h->allocs: scp_problem_destroy frees them.
+    // The flight records are h->audit's, the gains h->lqr's ----
+    struct Mc {
+        double *part = nullptr, *moments = nullptr, *stat = nullptr, *w = nullptr;
+        int W = 0;
+    } mc;
 
     // ---- trajectories: allocated by scp_api.hip at create; written by the run that owns them (h->run: ptr_api.hip or
     // scp_generic.hip) and, between runs, by the stand-alone entry points of every unit (sol_* as their staging buffers) ----

@@ -808,6 +808,118 @@ def audit_covariance_resident(pbm, gains=None, sig0=None, sigu=None, sigw=None, 
     return a
 
 
+MC_STAT_WIDTH = 8      # SCP_MC_STAT_WIDTH
+_MC_STAT_FIELDS = ("std_max", "std_node", "std_state", "mean_max", "mean_node", "effort_rms_max", "effort_rms_node", "n_min")
+
+
+class MonteCarloAuditBatch(TrackingAuditBatch):
+    """The Monte-Carlo audit of a batch (scp_audit_montecarlo_batch_host / scp_audit_montecarlo_resident, include/scp_mi355x.h):
+    a TrackingAuditBatch whose `D` flights were flown under the noise model of the covariance audit, drawn from `seed`.  Named
+    views [B] of `stat` [B, 8]: std_max = the largest sample standard deviation of a node error in units of Sx with its 1-based
+    std_node and std_state, mean_max = the largest |sample mean| in units of Sx and mean_node, effort_rms_max = the largest rms
+    feedback effort in units of Su and effort_rms_node, n_min = the fewest flights counted at a node.  Where the node records were
+    asked for: `n` [B, N] the flights counted, `mean` and `std` [B, N, nx] of the node errors x(t_k) - xd[:, k], `effort_rms`
+    [B, N, nu] (NaN at the last node); `moments` [B, N, 1 + 2 nx + nu] is the array itself; None otherwise.  Skipped (failed)
+    problems hold NaN everywhere."""
+
+    def __init__(self, raw, stat, nx, steps, res, viol_tol, D, seed=0, moments=None, flights=None):
+        super().__init__(raw, steps, res, viol_tol, D, flights)
+        self.stat = np.ascontiguousarray(stat, dtype=np.float64).reshape(-1, MC_STAT_WIDTH)
+        assert self.stat.shape[0] == len(self)
+        self.seed, nx = int(seed), int(nx)
+        for j, name in enumerate(_MC_STAT_FIELDS):
+            setattr(self, name, self.stat[:, j])
+        self.moments = None if moments is None else np.ascontiguousarray(moments, dtype=np.float64)
+        self.n = self.mean = self.std = self.effort_rms = None
+        if self.moments is not None:
+            assert self.moments.ndim == 3 and self.moments.shape[0] == len(self) and self.moments.shape[2] > 1 + 2 * nx
+            self.n, self.mean = self.moments[:, :, 0], self.moments[:, :, 1:1 + nx]
+            self.std, self.effort_rms = self.moments[:, :, 1 + nx:1 + 2 * nx], self.moments[:, :, 1 + 2 * nx:]
+
+    def compare(self, cov):
+        """Against the linear prediction: `cov` = a CovarianceAuditBatch of the same batch, made with per_node=True and the same
+        sigmas and gains.  Returns an object with ratio [B, N, nx] = std / cov.sig (NaN where cov.sig == 0), ratio_max and
+        ratio_min [B] over the nodes and states, and z_mean [B, N, nx] = |mean| / (cov.sig / sqrt(n)), the sample mean in
+        standard errors of the prediction.  ValueError when the node records of either side are missing or the shapes differ."""
+        from types import SimpleNamespace
+        sig = getattr(cov, "sig", None)
+        if self.moments is None or sig is None:
+            raise ValueError("compare needs the node records of both audits (moments=True here, per_node=True there)")
+        sig = np.asarray(sig, dtype=np.float64)
+        if sig.shape != self.std.shape:
+            raise ValueError("cov.sig of shape %s, the Monte-Carlo moments of shape %s" % (sig.shape, self.std.shape))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            pos = sig > 0.0
+            ratio = np.where(pos, self.std / np.where(pos, sig, 1.0), np.nan)
+            z_mean = np.where(pos, np.abs(self.mean) / (np.where(pos, sig, 1.0) / np.sqrt(self.n)[:, :, None]), np.nan)
+            flat = ratio.reshape(len(self), -1)
+            some = np.isfinite(flat).any(axis=1)
+            ratio_max = np.where(some, np.nanmax(np.where(np.isfinite(flat), flat, -np.inf), axis=1), np.nan)
+            ratio_min = np.where(some, np.nanmin(np.where(np.isfinite(flat), flat, np.inf), axis=1), np.nan)
+        return SimpleNamespace(ratio=ratio, ratio_max=ratio_max, ratio_min=ratio_min, z_mean=z_mean)
+
+
+def audit_montecarlo(sol, pbm, gains=None, steps=None, sig0=None, sigu=None, sigw=None, D=64, seed=0, viol_tol=0.0, moments=True,
+                     flights=False, pp=None):
+    """Monte-Carlo audit of the batch solution `sol` (scp_audit_montecarlo_batch_host): `D` >= 2 closed-loop flights per problem
+    through the nonlinear dynamics under the noise model of `audit_covariance` -- initial state xd[:, 0] + sig0 * xi, an input
+    disturbance sigu * xi held over each interval, a state kick sigw * xi on arrival at each node -- drawn on the device from
+    `seed` (every problem sees the same draws), and the per-node sample moments of the tracking error, reduced on the device.
+    `gains` and `steps` as in `audit_tracking`; sig0[nx], sigu[nu], sigw[nx] as in `audit_covariance`.  moments=True also returns
+    the node records, flights=True the record of every flight.  `sol.status` masks as in `audit`.  Returns a
+    MonteCarloAuditBatch; its `compare(cov)` sets the moments next to the covariance audit's prediction."""
+    xd = np.ascontiguousarray(sol.xd, dtype=np.float64)
+    ud = np.ascontiguousarray(sol.ud, dtype=np.float64)
+    p = np.ascontiguousarray(sol.p, dtype=np.float64)
+    B, N, D = xd.shape[0], pbm.pars.N, int(D)
+    pp = np.ascontiguousarray(np.tile(pbm.traj.mdl.nominal_pp()[None], (B, 1)) if pp is None else pp, dtype=np.float64)
+    assert pp.shape[0] == B
+    steps, res = _tracking_steps(pbm, steps)
+    sig0, sigu, sigw = _cov_sigmas(pbm, sig0, sigu, sigw)
+    K = _tracking_gains(pbm, B, gains)
+    out, stat = np.zeros((B, AUDIT_WIDTH)), np.zeros((B, MC_STAT_WIDTH))
+    mom = np.zeros((B, N, 1 + 2 * pbm.nx + pbm.nu)) if moments else None
+    recs = np.zeros((B, max(D, 1), AUDIT_WIDTH)) if flights else None
+    sec = ctypes.c_double(0.0)
+    rc = _lib.lib().scp_audit_montecarlo_batch_host(pbm.handle, B, _ptr(xd), _ptr(ud), _ptr(p) if pbm.np > 0 else None,
+                                                   _ptr(pp) if pbm.info.npp > 0 else None, _ptr(K), steps, float(viol_tol), D, int(seed),
+                                                   _ptr(sig0), _ptr(sigu), _ptr(sigw), _ptr(out), _ptr(stat), _ptr(mom), _ptr(recs),
+                                                   ctypes.byref(sec))
+    _lib.check(rc, pbm.handle)
+    status = getattr(sol, "status", None)
+    if status is not None:
+        bad = ~np.array([str(st).startswith("SCP_SOLVED") for st in status])
+        for a in (out, stat, mom, recs):
+            if a is not None:
+                a[bad] = np.nan
+    a = MonteCarloAuditBatch(out, stat, pbm.nx, steps, res, viol_tol, D, seed, mom, recs)
+    a.seconds = sec.value
+    return a
+
+
+def audit_montecarlo_resident(pbm, gains=None, steps=None, sig0=None, sigu=None, sigw=None, D=64, seed=0, viol_tol=0.0, moments=True,
+                              flights=False):
+    """The same for the batch RESIDENT in the handle (scp_audit_montecarlo_resident), with `gains` None = those of the last
+    `lqr_gains_resident`; failed problems NaN; the run is left untouched.  Returns a MonteCarloAuditBatch."""
+    B, N, D = getattr(pbm, "resident_B", None), pbm.pars.N, int(D)
+    if B is None:
+        raise _lib.ScpError(1, "audit_montecarlo_resident: no run has been started on this problem")
+    steps, res = _tracking_steps(pbm, steps)
+    sig0, sigu, sigw = _cov_sigmas(pbm, sig0, sigu, sigw)
+    K = _tracking_gains(pbm, B, gains)
+    cap = max(pbm.batch_capacity, B)      # room for the library's own batch, whatever this module believes
+    out, stat = np.zeros((cap, AUDIT_WIDTH)), np.zeros((cap, MC_STAT_WIDTH))
+    mom = np.zeros((cap, N, 1 + 2 * pbm.nx + pbm.nu)) if moments else None
+    recs = np.zeros((cap, max(D, 1), AUDIT_WIDTH)) if flights else None
+    sec = ctypes.c_double(0.0)
+    _lib.check(_lib.lib().scp_audit_montecarlo_resident(pbm.handle, _ptr(K), steps, float(viol_tol), D, int(seed), _ptr(sig0), _ptr(sigu),
+                                                       _ptr(sigw), _ptr(out), _ptr(stat), _ptr(mom), _ptr(recs), ctypes.byref(sec)), pbm.handle)
+    a = MonteCarloAuditBatch(out[:B].copy(), stat[:B].copy(), pbm.nx, steps, res, viol_tol, D, seed, mom[:B].copy() if moments else None,
+                             recs[:B].copy() if flights else None)
+    a.seconds = sec.value
+    return a
+
+
 def device_guess(pbm, pp):
     """`traj.guess(N)` for a Monte-Carlo batch evaluated on the device (scp_guess_batch_host): pp[B,npp] ->
     (xd[B,N,nx], ud[B,N,nu], p[B,np])."""
