@@ -1,19 +1,24 @@
 // K3: batched stage-structured primal-dual interior-point solver for the reduced PTR subproblem
 // (replaces JuMP `optimize!` -> ECOS, src/parser/program.jl:419-424 / src/solvers/scp.jl:942-950).
 //
-// Same algorithm as oracle/ipm_struct.py (see that file and DESIGN.md sections 2 and 4); this is the device
-// implementation:
+// The scalar mirror of this solver is oracle/cpu_ptr.cpp (CpuIpm; the algebra is derived in oracle/ipm_struct.py and DESIGN.md
+// sections 2 and 4); this is the device implementation:
 //   * one wavefront per problem, the whole IPM inside one launch; two kernel variants (WPE = 1 / 2 waves per SIMD,
 //     512 / 256 registers) selected by batch size;
-//   * every sweep over the horizon stages the part of the node's contiguous STAGE RECORD (csrc/stage_problem.hpp) it
-//     reads, the row / primal records and the packed FACTOR RECORD through LDS with coalesced, unconditional
-//     (clamped-index) loads, software-prefetched one node ahead into registers;
-//   * the horizon sweeps (G, G', factor, solve, direction) are separate non-inlined device functions, and inside each
-//     the first and last node are peeled off so that the hot loop holds one instantiation and no node-type predicates
-//     (both for the sake of the register allocator);
-//   * all inner loops have compile-time bounds (model dimensions are template constants);
-//   * the block factorisation keeps EXPLICIT inverses of the small Cholesky factors, so the four triangular solves per
-//     node and per right-hand side become dense mat-vecs (a triangular solve is a longer dependency chain for one wave);
+//   * the chain sweeps over the horizon (factor, forward / backward substitution) stage the node's packed FACTOR RECORD and the
+//     part of its STAGE RECORD (csrc/stage_problem.hpp) they read through LDS with coalesced, unconditional (clamped-index)
+//     loads, software-prefetched ahead into registers; the first and last node are peeled off so that the hot loop holds one
+//     instantiation and no node-type predicates (for the sake of the register allocator);
+//   * everything that does not depend on the chain is NODE-PARALLEL and flat: G, G', the right-hand sides, the chain-independent
+//     part of the factorisation and the direction pass own one (node, row) or (node, column) item per lane and read their
+//     coefficients straight from global memory, two items per lane in flight.  The structural part of a stage record -- the
+//     identity x-block of E, the zeros of Kl / Kp outside the model's declared pattern (models/model_common.hpp) -- is not read
+//     at all: those passes take E's input block and the pattern's Kl entries from a COMPACT STAGE RECORD (StagePat, `Off::sc`)
+//     that build_constants fills once per launch, checking the pattern against the slab;
+//   * the phases are separate non-inlined device functions (ipm2_run.hpp), all inner loops have compile-time bounds (model
+//     dimensions are template constants);
+//   * the block factorisation keeps the Cholesky FACTORS (reciprocal pivots on the diagonal); the substitutions of the chain
+//     sweeps run in registers across the lanes of a DPP row (ipm2_newton.hpp);
 //   * row-vector passes are flat, batched sweeps (8 loads in flight per lane);
 //   * the direction pass fuses G*dxi, the epigraph-variable recovery, the multiplier recovery and ds.
 #pragma once
@@ -21,6 +26,7 @@
 #include <stdint.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "ipm_kernel.hpp"   // IpmArgs, wave_* helpers, status codes
 #include "stage_problem.hpp"
@@ -29,41 +35,26 @@
 namespace scp {
 
 // Phase counters (scp_debug_get_ipm_profile) cost registers and s_memrealtime reads, so they are compiled only into
-// the diagnostic builds: -DSCP_IPM_PROF (phases: G, G', factor, rhs+fwd, bwd, arrow, finish, total) or
-// -DSCP_FACTOR_PROF (sub-phases of factor_stage: A, chol Sz, factor total, Y, Snu, chol Snu, X; currently
-// miscompiled by hipcc 7.2 in the phase-function build -- not part of the Makefile).  The production library reports zeros.
-#if defined(SCP_FACTOR_PROF)
+// the diagnostic builds: -DSCP_IPM_PROF (phases: G, G', factor, rhs+fwd, bwd, arrow, finish, total), -DSCP_IPM_PROF_CALLER and
+// -DSCP_IPM_PROF_OTHER (csrc/Makefile: prof, profc, profo).  The production library reports zeros.
+#if defined(SCP_IPM_PROF_CALLER)
 #define SCP_TICK() ((long long)wall_clock64())
-#define FPROF_BEGIN() long long fp_t_ = tick()
-#define FPROF(i) do { const long long n_ = tick(); fprof_[i] += n_ - fp_t_; fp_t_ = n_; } while (0)
-#define PROF_ADD(i, v) ((void)0)
-#define PROF_ADD2(i, v) do { if (lane == 0) L->prof[i] += (v); } while (0)
-#elif defined(SCP_IPM_PROF_CALLER)
-#define SCP_TICK() ((long long)wall_clock64())
-#define FPROF_BEGIN() ((void)0)
-#define FPROF(i) ((void)0)
 #define PROF_ADD(i, v) ((void)(v))
 #define PROF_ADD2(i, v) do { if ((i) == 7 && lane == 0) L->prof[i] += (v); } while (0)
 #elif defined(SCP_IPM_PROF_OTHER)
 // the light passes of run() itself (everything the phase clocks of SCP_IPM_PROF report as "other"): slots 0 residual passes + snapshots,
 // 1 nt_update, 2 combined right-hand side, 3 refinement residuals, 4 refinement updates, 5 step-length pass, 6 step trial + update
 #define SCP_TICK() ((long long)wall_clock64())
-#define FPROF_BEGIN() ((void)0)
-#define FPROF(i) ((void)0)
 #define PROF_ADD(i, v) ((void)(v))
 #define PROF_ADD2(i, v) do { if ((i) == 7 && lane == 0) L->prof[i] += (v); } while (0)
 #define OT_BEGIN() long long ot_t_ = (long long)wall_clock64()
 #define OT_END(i) do { const long long n_ = (long long)wall_clock64(); if (lane == 0) L->prof[i] += n_ - ot_t_; ot_t_ = n_; } while (0)
 #elif defined(SCP_IPM_PROF)
 #define SCP_TICK() ((long long)wall_clock64())
-#define FPROF_BEGIN() ((void)0)
-#define FPROF(i) ((void)0)
 #define PROF_ADD(i, v) do { if (lane == 0) L->prof[i] += (v); } while (0)
 #define PROF_ADD2(i, v) do { if (lane == 0) L->prof[i] += (v); } while (0)
 #else
 #define SCP_TICK() (0LL)
-#define FPROF_BEGIN() ((void)0)
-#define FPROF(i) ((void)0)
 #define PROF_ADD(i, v) ((void)(v))
 #define PROF_ADD2(i, v) ((void)(v))
 #endif
@@ -72,9 +63,62 @@ namespace scp {
 #define OT_END(i) ((void)0)
 #endif
 
+// Structural pattern of a stage record (compile-time data; models/model_common.hpp: kl_width, kl_col, has_kp) and the layout of the
+// COMPACT STAGE RECORD the node-parallel passes read instead of the dense E / Kl / Kp blocks:
+//   [ Eu nx x nu (input block of E; its x-block is the identity) | Kc ml x KW (slot s of row r = Kl[r][col(r, s)], padding slots
+//     0.0) | Kp ml x npa (models with has_kp only) ]
+// Default pattern: KW = nz, col(r, s) = s -- Kc is Kl itself.
+template <class M>
+struct StagePat {
+    using S = SP<M>;
+    static constexpr bool DENSE = M::kl_width == 0, HASKP = M::has_kp;
+    static constexpr int KW = DENSE ? S::nz : M::kl_width;
+    static constexpr int C_EU = 0, C_KL = S::nx * S::nu, C_KP = C_KL + S::ml * KW, SRC = C_KP + (HASKP ? S::ml * S::npa : 0);
+    static constexpr int col(int r, int s) { return DENSE ? s : M::kl_col(r, s); }
+    // number of used slots of row r: they come first, in ascending column order (checked below)
+    static constexpr int count(int r) { int n = 0; for (int s = 0; s < KW; s++) n += col(r, s) >= 0 ? 1 : 0; return n; }
+    static constexpr bool valid()
+    {
+        for (int r = 0; r < S::ml; r++)
+            for (int s = 0; s < KW; s++) {
+                const int c = col(r, s);
+                if (c >= S::nz) return false;
+                if (s > 0 && c >= 0 && !(col(r, s - 1) >= 0 && col(r, s - 1) < c)) return false;
+            }
+        return true;
+    }
+    // a lane's row is a runtime value and a dynamically indexed table would live in scratch: one word per row -- 4-bit column per
+    // slot (padding slots: column 0), used-slot count in bits 28..31 -- picked with selects (Ipm2::kword)
+    static constexpr unsigned word(int r)
+    {
+        unsigned w = 0;
+        for (int s = 0; s < KW && s < 7; s++) w |= (unsigned)(col(r, s) >= 0 ? col(r, s) : 0) << (4 * s);
+        return w | ((unsigned)count(r) << 28);
+    }
+    // TRANSPOSED view, for the passes whose lane owns a COLUMN (G', the right-hand sides): the slots of the rows >= r_lo whose column
+    // is j, in ascending row order.  col_entry: the q-th of them as row * 8 + slot, -1 beyond the last; col_width: the longest list
+    static constexpr int col_entry(int j, int q, int r_lo)
+    {
+        int n = 0;
+        for (int r = r_lo; r < S::ml; r++)
+            for (int s = 0; s < KW; s++)
+                if (col(r, s) == j) { if (n == q) return r * 8 + s; n++; }
+        return -1;
+    }
+    static constexpr int col_width(int r_lo)
+    {
+        int m = 0;
+        for (int j = 0; j < S::nz; j++) { int n = 0; while (col_entry(j, n, r_lo) >= 0) n++; m = n > m ? n : m; }
+        return m;
+    }
+    static_assert(DENSE || KW <= 7, "packed pattern word: at most 7 slots");
+    static_assert(S::nz <= 16, "packed pattern word: 4-bit columns");
+};
+
 template <class M>
 struct Ipm2Work {
     using S = SP<M>;
+    using PT = StagePat<M>;
     __host__ __device__ static long XI(int N) { return (long)N * (S::nz + S::AS) + S::npa + S::AG; }
     __host__ __device__ static long ROWS(int N) { return (long)N * S::RS + S::RG; }
     // per-node factor record: [Li tri(nz) | Lni tri(MM) | X MM*nz | Y nz*MM | row coefficients MM*2]
@@ -96,6 +140,7 @@ struct Ipm2Work {
         long F, C0, Ycz, Ycnu, fb, ft, nuv;                       // newton (F: per-node factor records)
         long tl;                                                  // [N][4 nsoc]: W^-1 (W^-1 rtil) of the cone rows (newton_rhs)
         long H0;                                                  // [N][HS]: chain-independent part of Sz_k (factor_pre)
+        long sc;                                                  // [N][SRC]: compact stage records (StagePat; build_constants)
         long sn_xi[IpmArgs::NWL], sn_s[IpmArgs::NWL], sn_lam[IpmArgs::NWL];   // warm-start snapshots (level 0 coarse ... NWL - 1 very fine): xi | s | lam
         long total;
     };
@@ -118,6 +163,7 @@ struct Ipm2Work {
         o.nuv = take((long)N * S::MNU);
         o.tl = take((long)N * 4 * (S::nsoc > 0 ? S::nsoc : 1));
         o.H0 = take((long)N * HS);
+        o.sc = take((long)N * PT::SRC);
         for (int q = 0; q < IpmArgs::NWL; q++) { o.sn_xi[q] = take(xi); o.sn_s[q] = take(rows); o.sn_lam[q] = take(rows); }
         o.total = c;
         return o;
@@ -128,6 +174,9 @@ template <class M>
 struct Ipm2 {
     using S = SP<M>;
     using WK = Ipm2Work<M>;
+    using PT = StagePat<M>;
+    static_assert(PT::valid(), "kl_col: columns below nz, ascending within a row, padding slots last");
+    static constexpr int KW = PT::KW, SRC = PT::SRC, C_EU = PT::C_EU, C_KL = PT::C_KL, C_KP = PT::C_KP;
     static constexpr int nx = S::nx, nu = S::nu, np = S::np, npa = S::npa, nz = S::nz, ns = S::ns, nl = S::nl,
                          nsoc = S::nsoc, ml = S::ml, ng = S::ng, nic = S::nic, ntc = S::ntc, nbc = S::nbc, RS = S::RS,
                          RG = S::RG, AS = S::AS, AG = S::AG, MNU = S::MNU, MMID = S::MNU_MID, SR = S::SR, GR = S::GR;
@@ -179,9 +228,6 @@ struct Ipm2 {
     Lds* L;
     IpmArgs a;
     double ttrp, cost_const;
-#ifdef SCP_FACTOR_PROF
-    long long fprof_[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // sub-phase ticks of this factor() call, flushed to LDS at its end
-#endif
     double pre[NPRE];
     double preF[NPREF];
     static constexpr int NROWR = (RS + 63) / 64, NSOCR = (NSOC1 * 36 + 63) / 64;
@@ -350,7 +396,7 @@ struct Ipm2 {
     // Round 6: FLAT over the rows, by row type (before: one node at a time, the node's records staged through LDS -- 750
     // instructions and one exposed memory round trip per node).  A lane owns one (node, row) item, reads that row's coefficients
     // straight from the slab (the L1 absorbs the stride), items are processed two at a time with all loads ahead of the stores;
-    // lanes past the end repeat the last item.
+    // lanes past the end repeat the last item.  Round 7: the structural part of E / Kl / Kp is not read (compact stage record).
     template <class F>
     __device__ __forceinline__ void flat_items(int count, F&& f) const
     {
@@ -360,6 +406,90 @@ struct Ipm2 {
             auto r0 = f(i0 < count ? i0 : count - 1), r1 = f(i1 < count ? i1 : count - 1);
             r0.store(); r1.store();
         }
+    }
+    // ---------------- compact stage record (StagePat): E's input block and the pattern's Kl / Kp entries ----------------
+    __device__ __forceinline__ const double* Crec(int k) const { return W + wo.sc + (long)k * SRC; }
+    // f(std::integral_constant<int, R>) for the rows R in [LO, HI): the row is a compile-time value in f
+    template <int LO, class F, int... I>
+    __device__ __forceinline__ static void for_rows_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, LO + I>{}), ...); }
+    template <int LO, int HI, class F>
+    __device__ __forceinline__ static void for_rows(F&& f) { for_rows_<LO>(f, std::make_integer_sequence<int, (HI > LO ? HI - LO : 0)>{}); }
+    // pattern word (StagePat::word) of a RUNTIME row in [LO, HI): selects between compile-time words, no table
+    template <int LO, int HI>
+    __device__ __forceinline__ static unsigned kword(int row)
+    {
+        unsigned w = 0;
+        for_rows<LO, HI>([&](auto R) { w = (row == decltype(R)::value) ? std::integral_constant<unsigned, PT::word(decltype(R)::value)>::value : w; });
+        return w;
+    }
+    // Kl[R][j] for a compile-time row and a RUNTIME column: the slot of the row whose column is j, else the structural 0.0
+    // (loads unconditional, the choice is a select: a branch around a load is an exposed round trip, see GT_apply)
+    template <int R>
+    __device__ __forceinline__ static double kl_at(const double* Ck_, int j)
+    {
+        if constexpr (PT::DENSE) return Ck_[C_KL + R * nz + j];
+        else {
+            double c = 0.0;
+            for_rows<0, KW>([&](auto S_) {
+                constexpr int cc = PT::col(R, decltype(S_)::value);
+                if constexpr (cc >= 0) { const double v = Ck_[C_KL + R * KW + decltype(S_)::value]; c = (j == cc) ? v : c; }
+            });
+            return c;
+        }
+    }
+    // q-th slot (row * 8 + slot, -1: none) among the rows >= RLO that holds an entry of the RUNTIME column j (StagePat::col_entry):
+    // selects between compile-time values
+    template <int RLO, int Q>
+    __device__ __forceinline__ static int col_slot(int j)
+    {
+        int e = -1;
+        for_rows<0, nz>([&](auto J) { e = (j == decltype(J)::value) ? std::integral_constant<int, PT::col_entry(decltype(J)::value, Q, RLO)>::value : e; });
+        return e;
+    }
+    // (row `row` of [Kl Kp]) * (z_k, p) for a RUNTIME row in [LO, HI): the row's slots in ascending column order (the order of the dense
+    // sum over j with the structural zeros left out; a padding slot multiplies a stored 0.0)
+    template <int LO, int HI>
+    __device__ __forceinline__ double loc_row(int k, int row, double* v, const double (&pv_)[npa]) const
+    {
+        const double* Ck_ = Crec(k);
+        double acc = 0.0;
+        if constexpr (PT::DENSE) {
+#pragma unroll
+            for (int j = 0; j < nz; j++) acc += Ck_[C_KL + row * nz + j] * Z(v, k, j);
+        } else {
+            const unsigned w = kword<LO, HI>(row);
+#pragma unroll
+            for (int s = 0; s < KW; s++) acc += Ck_[C_KL + row * KW + s] * Z(v, k, (int)((w >> (4 * s)) & 15u));
+        }
+        if constexpr (PT::HASKP) {
+#pragma unroll
+            for (int j = 0; j < np; j++) acc += Ck_[C_KP + row * npa + j] * pv_[j];
+        }
+        return acc;
+    }
+    // D_k[i] z_k + E_k[i] z_{k+1} + Fp_k[i] p of dynamics row i.  E's x-block is the identity (checked in build_constants): row i takes
+    // z_{k+1}[i] itself and no coefficient.  The rounding sequence is the one `acc += d * z + e * zn` compiled to while E was read from
+    // the slab -- t = fma(d, z, e * zn), acc = acc + t -- and is pinned here (contraction off), so that results stay bit for bit:
+    // e * zn is zn for e = 1 and a zero for e = 0.
+    __device__ __forceinline__ double dyn_row(double* v, int k, int kn, int i, const double (&pv_)[npa]) const
+    {
+        const double* Pk_ = Pg + (long)k * SR;
+        const double* Ck_ = Crec(k);
+        const double zni = Z(v, kn, i);
+        double acc = 0.0;
+        {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int j = 0; j < nx; j++) acc = acc + __builtin_fma(Pk_[S::O_D + i * nz + j], Z(v, k, j), j == i ? zni : 0.0);
+#pragma unroll
+            for (int j = nx; j < nz; j++) {
+                const double ez = Ck_[C_EU + i * nu + (j - nx)] * Z(v, kn, j);
+                acc = acc + __builtin_fma(Pk_[S::O_D + i * nz + j], Z(v, k, j), ez);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < np; j++) acc += Pk_[S::O_FP + i * npa + j] * pv_[j];
+        return acc;
     }
     __device__ __forceinline__ void G_apply(double* v, double* out)
     {
@@ -371,12 +501,7 @@ struct Ipm2 {
         // dynamics rows: +-(D z_k + E z_{k+1} + Fp p) - y   (absent at the last node: zeros)
         flat_items(N * nx, [&](int idx) {
             const int k = idx / nx, i = idx - k * nx, kn = k + 1 < N ? k + 1 : N - 1;
-            const double* Pk_ = Pg + (long)k * SR;
-            double acc = 0.0;
-#pragma unroll
-            for (int j = 0; j < nz; j++) acc += Pk_[S::O_D + i * nz + j] * Z(v, k, j) + Pk_[S::O_E + i * nz + j] * Z(v, kn, j);
-#pragma unroll
-            for (int j = 0; j < np; j++) acc += Pk_[S::O_FP + i * npa + j] * pv_[j];
+            const double acc = dyn_row(v, k, kn, i, pv_);
             const double y = AUX(v, k, S::A_Y + i);
             const bool lastk = k == N - 1;
             return R2{&ROW(out, k, i), &ROW(out, k, nx + i), lastk ? 0.0 : acc - y, lastk ? 0.0 : -acc - y};
@@ -385,12 +510,7 @@ struct Ipm2 {
         if (ml > 0) {
             flat_items(N * ml, [&](int idx) {
                 const int k = idx / ml, row = idx - k * ml;
-                const double* Pk_ = Pg + (long)k * SR;
-                double acc = 0.0;
-#pragma unroll
-                for (int j = 0; j < nz; j++) acc += Pk_[S::O_KL + row * nz + j] * Z(v, k, j);
-#pragma unroll
-                for (int j = 0; j < np; j++) acc += Pk_[S::O_KP + row * npa + j] * pv_[j];
+                const double acc = loc_row<0, ml>(k, row, v, pv_);
                 const bool hg = row < ns, lin = row < ns + nl;
                 const double vv = AUX(v, k, S::A_V + (hg ? row : 0));
                 const int r = hg ? S::R_H0 + row : (lin ? S::R_LIN + row - ns : S::R_SOC + row - ns - nl);
@@ -498,7 +618,10 @@ struct Ipm2 {
         flat_items(N * nz, [&](int idx) {
             const int k = idx / nz, j = idx - k * nz, kp = k > 0 ? k - 1 : 0, jx = j < nx ? j : nx - 1;
             const double* Pk_ = Pg + (long)k * SR;
-            const double* Pp_ = Pg + (long)kp * SR;
+            const double* Ck_ = Crec(k);
+            const double* Cp_ = Crec(kp);
+            const bool isu = j >= nx;
+            const int ju = isu ? j - nx : 0;
             const double* mk = mu + (long)k * RS;
             const double* mp = mu + (long)kp * RS;
             const double fl = k == N - 1 ? 0.0 : 1.0, ff = k == 0 ? 0.0 : 1.0;
@@ -506,15 +629,36 @@ struct Ipm2 {
             double acc = 0.0;
 #pragma unroll
             for (int i = 0; i < nx; i++) acc += Pk_[S::O_D + i * nz + j] * (fl * (mk[i] - mk[nx + i]));
+            // E' of the previous node: column j of the identity for a state component (a 1.0 / 0.0 coefficient: acc + 1.0 * m and
+            // acc + 0.0 * m are exact), column j - nx of the input block otherwise
 #pragma unroll
-            for (int i = 0; i < nx; i++) acc += Pp_[S::O_E + i * nz + j] * (ff * (mp[i] - mp[nx + i]));
+            for (int i = 0; i < nx; i++) {
+                double eu = Cp_[C_EU + i * nu + ju];
+                asm volatile("" : "+v"(eu));   // (the load is issued for every lane: no branch around it)
+                const double e = isu ? eu : (i == j ? 1.0 : 0.0);
+                acc += e * (ff * (mp[i] - mp[nx + i]));
+            }
             acc += mk[S::R_TR0 + j] - mk[S::R_TR1 + j];
+            if constexpr (PT::DENSE) {
 #pragma unroll
-            for (int i = 0; i < ns; i++) acc += Pk_[S::O_KL + i * nz + j] * mk[S::R_H0 + i];
+                for (int i = 0; i < ns; i++) acc += Ck_[C_KL + i * nz + j] * mk[S::R_H0 + i];
 #pragma unroll
-            for (int i = 0; i < nl; i++) acc += Pk_[S::O_KL + (ns + i) * nz + j] * mk[S::R_LIN + i];
+                for (int i = 0; i < nl; i++) acc += Ck_[C_KL + (ns + i) * nz + j] * mk[S::R_LIN + i];
 #pragma unroll
-            for (int i = 0; i < 4 * nsoc; i++) acc -= Pk_[S::O_KL + (ns + nl + i) * nz + j] * mk[S::R_SOC + i];
+                for (int i = 0; i < 4 * nsoc; i++) acc -= Ck_[C_KL + (ns + nl + i) * nz + j] * mk[S::R_SOC + i];
+            } else {
+                // Kl': the slots of column j in ascending row order (the order of the dense sums over the hinge, linear and cone rows with
+                // the structural zeros left out); a column with fewer slots multiplies 0.0.  Cone rows enter with -1.
+                // (both loads of a slot are issued whether it is used or not -- slot 0 --: the choice is a select, not a branch)
+                for_rows<0, PT::col_width(0)>([&](auto Q) {
+                    const int e = col_slot<0, decltype(Q)::value>(j), ee = e >= 0 ? e : 0, r = ee >> 3, sl_ = ee & 7;
+                    const bool lin = r < ns + nl;
+                    const int ri = r < ns ? S::R_H0 + r : (lin ? S::R_LIN + r - ns : S::R_SOC + r - ns - nl);
+                    double kv = Ck_[C_KL + r * KW + sl_], m = mk[ri];
+                    asm volatile("" : "+v"(kv), "+v"(m));
+                    acc += (e >= 0 ? kv : 0.0) * (lin ? m : -m);
+                });
+            }
             double aic = 0.0, atc = 0.0;
 #pragma unroll
             for (int i = 0; i < nic; i++) aic += gH0()[i * nx + jx] * (mu[NRS + S::G_IC0 + i] - mu[NRS + S::G_IC1 + i]);
@@ -601,8 +745,13 @@ struct Ipm2 {
     }
 
     // ---------------- constants: hneg (= -h), cost vector cv, diagonal qd on the xi layout ----------------
-    __device__ __forceinline__ void build_constants(double* hn, double* cv, double* qd)
+    // Also fills the compact stage records (StagePat) from the staged dense record and CHECKS the model's pattern against it: E's
+    // x-block the identity (k < N - 1), Kl exactly 0.0 outside the declared slots, Kp exactly 0.0 where the model declares none.
+    // Returns true (wave-uniform) when the slab violates the pattern: the solve must not run on it (run(): IPM_NUMERR).
+    __device__ __forceinline__ bool build_constants(double* hn, double* cv, double* qd)
     {
+        double* Wc = W + wo.sc;
+        bool bad = false;
         prefetch(0);
         for (int k = 0; k < N; k++) {
             commit();
@@ -627,6 +776,38 @@ struct Ipm2 {
                 else c = L->st.Pk[S::O_TTR];
                 AUX(cv, k, i) = c; AUX(qd, k, i) = 0.0;
             }
+            for (int idx = lane; idx < SRC; idx += 64) {
+                double val;
+                if (idx < C_KL) { const int i = idx / nu, ju = idx - i * nu; val = L->st.Pk[S::O_E + i * nz + nx + ju]; }
+                else if (idx < C_KP) {
+                    const int t = idx - C_KL, row = t / KW, s = t - row * KW;
+                    if constexpr (PT::DENSE) val = L->st.Pk[S::O_KL + t];
+                    else {
+                        const unsigned w = kword<0, ml>(row);
+                        const double kv = L->st.Pk[S::O_KL + row * nz + (int)((w >> (4 * s)) & 15u)];
+                        val = s < (int)(w >> 28) ? kv : 0.0;
+                    }
+                }
+                else val = L->st.Pk[S::O_KP + (idx - C_KP)];
+                Wc[(long)k * SRC + idx] = val;
+            }
+            for (int idx = lane; idx < nx * nx; idx += 64) {
+                const int i = idx / nx, j = idx - i * nx;
+                if (k < N - 1 && L->st.Pk[S::O_E + i * nz + j] != (i == j ? 1.0 : 0.0)) bad = true;
+            }
+            if constexpr (!PT::DENSE) {
+                for (int idx = lane; idx < ml * nz; idx += 64) {
+                    const int row = idx / nz, j = idx - row * nz;
+                    const unsigned w = kword<0, ml>(row);
+                    bool in = false;
+#pragma unroll
+                    for (int s = 0; s < KW; s++) in = in | ((s < (int)(w >> 28)) & ((int)((w >> (4 * s)) & 15u) == j));
+                    if (!in && L->st.Pk[S::O_KL + idx] != 0.0) bad = true;
+                }
+            }
+            if constexpr (!PT::HASKP) {
+                for (int idx = lane; idx < ml * npa; idx += 64) if (L->st.Pk[S::O_KP + idx] != 0.0) bad = true;
+            }
             sync();
         }
         for (int r = lane; r < RG; r += 64) {
@@ -646,6 +827,7 @@ struct Ipm2 {
             GAUX(cv, i) = c; GAUX(qd, i) = 0.0;
         }
         gsync();
+        return __builtin_amdgcn_ballot_w64(bad) != 0;
     }
 
     // ---------------- small dense helpers on LDS ----------------

@@ -1,5 +1,6 @@
 // Newton system of the structured IPM: factorisation sweep, solve sweeps, direction recovery.
-// Included by ipm2_kernel.hpp.  Algebra: oracle/ipm_struct.py (qd_factor / qd_solve / newton).
+// Included by ipm2_kernel.hpp.  Scalar mirror: oracle/cpu_ptr.cpp (CpuIpm::factor / newton_solve / finish_direction); the algebra is
+// derived in oracle/ipm_struct.py (qd_factor / qd_solve / newton).
 //
 // The sweeps over the horizon are dependency chains for the single wave that owns a problem, so the
 // per-node work is organised to minimise latency rather than flops:
@@ -150,16 +151,19 @@ __device__ __forceinline__ void Ipm2<M>::factor_pre(const double* w, double (&Dp
         const int kk = kv ? k : N - 1;
         const long rb = (long)kk * RS;
         const double* Pk_ = Pg + (long)kk * SR;
-        // rows of Z (column jc) and their weights
-        double z[NZR > 0 ? NZR : 1], om[NZR > 0 ? NZR : 1];
+        const double* Ck_ = Crec(kk);
+        // rows of Z (column jc) and their weights; the Kl entries come from the compact stage record (kl_at)
+        double z[NZR > 0 ? NZR : 1], om[NZR > 0 ? NZR : 1], kca[nsoc > 0 ? 4 * nsoc : 1];
+        for_rows<ns, ns + nl>([&](auto R) { constexpr int r = decltype(R)::value; z[r - ns] = kl_at<r>(Ck_, jc); });
+        for_rows<ns + nl, ml>([&](auto R) { constexpr int r = decltype(R)::value; kca[r - ns - nl] = kl_at<r>(Ck_, jc); });
 #pragma unroll
-        for (int i = 0; i < nl; i++) { z[i] = Pk_[S::O_KL + (ns + i) * nz + jc]; om[i] = w[rb + S::R_LIN + i]; }
+        for (int i = 0; i < nl; i++) om[i] = w[rb + S::R_LIN + i];
 #pragma unroll
         for (int c = 0; c < nsoc; c++) {
             const double* Wi = socW + ((long)kk * nsoc + c) * 36 + 16;
             double kc[4];
 #pragma unroll
-            for (int q = 0; q < 4; q++) kc[q] = Pk_[S::O_KL + (ns + nl + 4 * c + q) * nz + jc];
+            for (int q = 0; q < 4; q++) kc[q] = kca[4 * c + q];
 #pragma unroll
             for (int rr = 0; rr < 4; rr++) {
                 double acc = 0.0;
@@ -200,13 +204,16 @@ __device__ __forceinline__ void Ipm2<M>::factor_pre(const double* w, double (&Dp
         const double qd = Pk_[S::O_QD + jc];
 #pragma unroll
         for (int a_ = 0; a_ < nz; a_++) H0g[(long)kk * HS + a_ * nz + jc] = h[a_] + ((a_ == jc) ? qd : 0.0);
-        // arrow: C0_k[a = jc][j] and the p x p term
-        if (np > 0) {
+        // arrow: C0_k[a = jc][j] and the p x p term (a model without Kp: both are sums of exact zeros)
+        if constexpr (np > 0 && !PT::HASKP) {
+#pragma unroll
+            for (int j = 0; j < np; j++) gC0[(long)kk * nz * npa + jc * npa + j] = 0.0;
+        } else if constexpr (np > 0) {
             double kp[nl > 0 ? nl : 1][npa];
 #pragma unroll
             for (int i = 0; i < nl; i++)
 #pragma unroll
-                for (int j = 0; j < np; j++) kp[i][j] = Pk_[S::O_KP + (ns + i) * npa + j];
+                for (int j = 0; j < np; j++) kp[i][j] = Ck_[C_KP + (ns + i) * npa + j];
 #pragma unroll
             for (int j = 0; j < np; j++) {
                 double c0 = 0.0;
@@ -273,7 +280,6 @@ __device__ __forceinline__ void Ipm2<M>::factor_stage(int k, const double (&pH)[
     // the interior-node instantiation <MMID, MMID> of the hot loop is straight-line code
     constexpr bool MID = (MM == MMID) && (MMID < MNU);   // instantiated for interior nodes only
     double* gYcz = W + wo.Ycz; double* gYcnu = W + wo.Ycnu;
-    FPROF_BEGIN();
     // ---- Sz = H0_k + X'X  (X of the previous node is still in the factor record) ----
     // Matrix core: the rows of X_{k-1} are the K dimension of v_mfma_f64_16x16x4_f64 (A[i = lane & 15][k = lane >> 4] = X[r][i],
     // B[k][j = lane & 15] = X[r][j]; D row = (lane >> 4) + 4 reg, column = lane & 15), accumulated onto H0.
@@ -305,11 +311,9 @@ __device__ __forceinline__ void Ipm2<M>::factor_stage(int k, const double (&pH)[
         }
     }
     sync();
-    FPROF(0);
     // ---- Lz = chol(Sz) in registers (row per lane), written to the record as well ----
     double lz[nz], dz[nz];
     if (!chol_reg<nz, nz>(L->st.Sz, Li(), lane, lz, dz)) L->fail = 1;
-    FPROF(1);
     // ---- Y = Lz^-1 Dt' : lane c owns column c (c < MM) ; lane MM (np > 0) does the arrow column cb = Lz^-1 Cz ----
     // forward substitution inside the lane; L[j][q] is broadcast from the registers of lane j (round 6; before: uniform LDS reads of
     // the packed factor behind a barrier)
@@ -347,7 +351,6 @@ __device__ __forceinline__ void Ipm2<M>::factor_stage(int k, const double (&pH)[
             for (int j = 0; j < nz; j++) { L->cb[j * npa + jc_] = y[j]; gYcz[(long)k * nz * npa + j * npa + jc_] = y[j]; }
         }
     }
-    FPROF(3);
     // arrow right-hand side Ft - Y' cb on lane q < MM (consumed by the X stage below); cb = column of lane MM (np == 1)
     double tq = 0.0;
     if constexpr (np == 1) {
@@ -392,10 +395,8 @@ __device__ __forceinline__ void Ipm2<M>::factor_stage(int k, const double (&pH)[
         }
     }
     sync();
-    FPROF(4);
     double ln[MM], dn[MM];
     if (!chol_reg<MM, MNU>(L->st.Snu, Lni(MM), lane, ln, dn)) L->fail = 1;
-    FPROF(5);
     // ---- X = Ln^-1 Et : lane j owns column j (j < nz) ; arrow: ct = Ln^-1 (Ft - Y' cb) on lane nz (np == 1) ----
     {
         const int l = lane & 15;
@@ -427,7 +428,6 @@ __device__ __forceinline__ void Ipm2<M>::factor_stage(int k, const double (&pH)[
         }
     }
     sync();
-    FPROF(6);
     storeF(k);
 }
 
@@ -524,9 +524,6 @@ __device__ __forceinline__ void Ipm2<M>::factor(double* w)
         gsync();
     }
     PROF_ADD2(2, tick() - t0_);
-#ifdef SCP_FACTOR_PROF
-    if (lane == 0) for (int i = 0; i < 8; i++) if (i != 2 && i != 7) L->prof[i] += fprof_[i];
-#endif
 }
 
 // backward sweep for the np arrow columns held in (Ycz = b-hat, Ycnu = t-hat)
@@ -806,6 +803,7 @@ __device__ __forceinline__ void Ipm2<M>::newton_rhs(const double* w, const doubl
         const int kk = kv ? k : N - 1;
         const long rb = (long)kk * RS;
         const double* Pk_ = Pg + (long)kk * SR;
+        const double* Ck_ = Crec(kk);
         // ---- b_k[jc]: trust-region pair of component jc + group sums by row broadcast ----
         const double w1 = w[rb + S::R_TR0 + jc], w2 = w[rb + S::R_TR1 + jc], t1 = rtil[rb + S::R_TR0 + jc], t2 = rtil[rb + S::R_TR1 + jc];
         const double a1 = w1 + w2, a2 = w1 * t1 + w2 * t2;
@@ -817,10 +815,24 @@ __device__ __forceinline__ void Ipm2<M>::newton_rhs(const double* w, const doubl
         const bool jx = jc < nx;
         double acc = -Z((double*)rxv, kk, jc);
         acc += -(w1 * t1 - w2 * t2) + (w1 - w2) * (jx ? rthx : rthu) * fast_rcp(jx ? Wx : Wu);
+        if constexpr (PT::DENSE) {
 #pragma unroll
-        for (int i = 0; i < nl; i++) acc += Pk_[S::O_KL + (ns + i) * nz + jc] * (-w[rb + S::R_LIN + i] * rtil[rb + S::R_LIN + i]);
+            for (int i = 0; i < nl; i++) acc += Ck_[C_KL + (ns + i) * nz + jc] * (-w[rb + S::R_LIN + i] * rtil[rb + S::R_LIN + i]);
 #pragma unroll
-        for (int r = 0; r < 4 * nsoc; r++) acc += Pk_[S::O_KL + (ns + nl + r) * nz + jc] * tlv[(long)kk * 4 * nsoc + r];
+            for (int r = 0; r < 4 * nsoc; r++) acc += Ck_[C_KL + (ns + nl + r) * nz + jc] * tlv[(long)kk * 4 * nsoc + r];
+        } else {
+            // the slots of column jc among the linear and cone rows, in ascending row order; both kinds of factor are loaded
+            // (clamped index), the choice is a select
+            for_rows<0, PT::col_width(ns)>([&](auto Q) {
+                const int e = col_slot<ns, decltype(Q)::value>(jc), ee = e >= 0 ? e : ns * 8, r = ee >> 3, s_ = ee & 7;
+                const bool lin = r < ns + nl;
+                const long iw = rb + S::R_LIN + (lin ? r - ns : 0);
+                double kv = Ck_[C_KL + r * KW + s_], wl = w[iw], rl_ = rtil[iw], tcone = 0.0;
+                if constexpr (nsoc > 0) tcone = tlv[(long)kk * 4 * nsoc + (lin ? 0 : r - ns - nl)];
+                asm volatile("" : "+v"(kv), "+v"(wl), "+v"(rl_), "+v"(tcone));
+                acc += (e >= 0 ? kv : 0.0) * (lin ? -wl * rl_ : tcone);
+            });
+        }
         fb[(long)kk * nz + jc] = acc;
         // ---- t_k[cl]: penalised (nu) row cl of the node ----
         {
@@ -1045,6 +1057,7 @@ __device__ __forceinline__ void Ipm2<M>::newton_solve(double* w, double* rtil, d
 template <class M>
 __device__ __forceinline__ void Ipm2<M>::finish_direction(double* w, double* rtil, double* rxv, double* dxi, double* gd, double* dl)
 {
+    // The structural part of E / Kl / Kp is not read: dyn_row, loc_row (compact stage record).
     // Round 6: FLAT by row type like G_apply (before: one node at a time through LDS, 930 instructions and an exposed memory round
     // trip per node): every item reads what it needs straight from global memory, two items per lane in flight, stores last.
     const long long t0_ = tick();
@@ -1063,12 +1076,7 @@ __device__ __forceinline__ void Ipm2<M>::finish_direction(double* w, double* rti
                    __device__ __forceinline__ void store() const { *a = va; *g0 = vg0; *g1 = vg1; *d0 = vd0; *d1 = vd1; } };
         flat_items(N * nx, [&](int idx) {
             const int k = idx / nx, i = idx - k * nx, kn = k + 1 < N ? k + 1 : N - 1;
-            const double* Pk_ = Pg + (long)k * SR;
-            double acc = 0.0;
-#pragma unroll
-            for (int j = 0; j < nz; j++) acc += Pk_[S::O_D + i * nz + j] * Z(dxi, k, j) + Pk_[S::O_E + i * nz + j] * Z(dxi, kn, j);
-#pragma unroll
-            for (int j = 0; j < np; j++) acc += Pk_[S::O_FP + i * npa + j] * pv_[j];
+            const double acc = dyn_row(dxi, k, kn, i, pv_);
             const double w1 = ROW(w, k, i), w2 = ROW(w, k, nx + i), t1 = ROW(rtil, k, i), t2 = ROW(rtil, k, nx + i);
             const double rxa = AUX(rxv, k, S::A_Y + i), nv = nuv[(long)k * MNU + i];
             const Pair pr = pairA(w1, w2, t1, t2, rxa);
@@ -1084,12 +1092,7 @@ __device__ __forceinline__ void Ipm2<M>::finish_direction(double* w, double* rti
                    __device__ __forceinline__ void store() const { *a = va; *g0 = vg0; *g1 = vg1; *d0 = vd0; *d1 = vd1; } };
         flat_items(N * ns, [&](int idx) {
             const int k = idx / (ns > 0 ? ns : 1), i = idx - k * ns;
-            const double* Pk_ = Pg + (long)k * SR;
-            double acc = 0.0;
-#pragma unroll
-            for (int j = 0; j < nz; j++) acc += Pk_[S::O_KL + i * nz + j] * Z(dxi, k, j);
-#pragma unroll
-            for (int j = 0; j < np; j++) acc += Pk_[S::O_KP + i * npa + j] * pv_[j];
+            const double acc = loc_row<0, ns>(k, i, dxi, pv_);
             const double w1 = ROW(w, k, S::R_H0 + i), w2 = ROW(w, k, S::R_H1 + i), t1 = ROW(rtil, k, S::R_H0 + i), t2 = ROW(rtil, k, S::R_H1 + i);
             const double rxa = AUX(rxv, k, S::A_V + i), nv = nuv[(long)k * MNU + nx + i];
             const Pair pr = pairC(w1, w2, t1, t2, rxa);
@@ -1103,12 +1106,7 @@ __device__ __forceinline__ void Ipm2<M>::finish_direction(double* w, double* rti
         struct R { double *g0, *d0; double vg0, vd0; __device__ __forceinline__ void store() const { *g0 = vg0; *d0 = vd0; } };
         flat_items(N * nl, [&](int idx) {
             const int k = idx / (nl > 0 ? nl : 1), i = idx - k * nl;
-            const double* Pk_ = Pg + (long)k * SR;
-            double acc = 0.0;
-#pragma unroll
-            for (int j = 0; j < nz; j++) acc += Pk_[S::O_KL + (ns + i) * nz + j] * Z(dxi, k, j);
-#pragma unroll
-            for (int j = 0; j < np; j++) acc += Pk_[S::O_KP + (ns + i) * npa + j] * pv_[j];
+            const double acc = loc_row<ns, ns + nl>(k, ns + i, dxi, pv_);
             const int r = S::R_LIN + i;
             return R{&ROW(gd, k, r), &ROW(dl, k, r), acc, ROW(w, k, r) * (acc + ROW(rtil, k, r))};
         });
@@ -1119,18 +1117,13 @@ __device__ __forceinline__ void Ipm2<M>::finish_direction(double* w, double* rti
                    __device__ __forceinline__ void store() const { for (int q = 0; q < 4; q++) { g[q] = vg[q]; d[q] = vd[q]; } } };
         flat_items(N * nsoc, [&](int idx) {
             const int k = idx / NSOC1, c = idx - k * NSOC1;
-            const double* Pk_ = Pg + (long)k * SR;
             const double* Wi = socW + (long)idx * 36 + 16;
             R out_;
             double u[4], t1[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const int row = ns + nl + 4 * c + q;
-                double acc = 0.0;
-#pragma unroll
-                for (int j = 0; j < nz; j++) acc += Pk_[S::O_KL + row * nz + j] * Z(dxi, k, j);
-#pragma unroll
-                for (int j = 0; j < np; j++) acc += Pk_[S::O_KP + row * npa + j] * pv_[j];
+                const double acc = loc_row<ns + nl, ml>(k, row, dxi, pv_);
                 out_.vg[q] = -acc;
                 u[q] = -acc + ROW(rtil, k, S::R_SOC + 4 * c + q);
             }

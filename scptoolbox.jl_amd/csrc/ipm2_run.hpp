@@ -1,4 +1,5 @@
-// Main loop of the structured IPM (included by ipm2_kernel.hpp).  Mirrors oracle/ipm_struct.py::solve.
+// Main loop of the structured IPM (included by ipm2_kernel.hpp).  run() is mirrored statement by statement by the scalar CPU
+// twin oracle/cpu_ptr.cpp (CpuIpm::solve); the algebra is derived in oracle/ipm_struct.py::solve.
 #pragma once
 
 namespace scp {
@@ -193,7 +194,8 @@ __device__ __forceinline__ void Ipm2<M>::run()
     if (lane == 0) { L->fail = 0; for (int i = 0; i < 8; i++) L->prof[i] = 0; }
     for (int i = lane; i < GR; i += 64) L->G[i] = Pg[o.glob + i];
     gsync();
-    build_constants(hneg, cv, qd);
+    // a slab that violates the model's structural pattern is not solved: the node-parallel passes would compute something else
+    const bool pat_bad = build_constants(hneg, cv, qd);
 
     // Row-vector sweeps below are FLAT over the [N][RS] + [RG] layout and batched (flat<>): U*NA loads are in
     // flight per lane before the first store, which is what a single wave needs to stream at more than one
@@ -226,7 +228,7 @@ __device__ __forceinline__ void Ipm2<M>::run()
     // Mehrotra iterations, so that factor / newton_solve / finish_direction have a single (inlined) call site.
     // Warm start (scp_ptr_params.ipm_warm): attempt 0 starts from a snapshot of the previous launch (below); if that solve fails,
     // attempt 1 repeats it cold.  Same algebra as oracle/cpu_ptr.cpp (CpuIpm::solve).
-    int status = IPM_ITERLIM;
+    int status = pat_bad ? IPM_NUMERR : IPM_ITERLIM;
     int it = 0, best_it = 0, iters_total = 0;
     double best_merit = 1e300;
     double info_best[7] = {0, 0, 0, 0, 0, 0, 1e300};
@@ -269,7 +271,8 @@ __device__ __forceinline__ void Ipm2<M>::run()
     // scalar CPU restatement solve those instances, tests/test_failures_gpu.py; with refinement throughout this solver does too)
     bool robust = false;
     bool fell_back = false;   // the warm attempt from the very fine level failed and is being repeated from the next level
-    for (int attempt = try_warm ? 0 : 1; attempt < 3; attempt++) {
+    if (pat_bad && lane == 0) L->fail = 1;
+    for (int attempt = try_warm ? 0 : 1; attempt < 3 && !pat_bad; attempt++) {
     warm = attempt == 0;
     robust = attempt == 2;
     status = IPM_ITERLIM; best_it = 0; best_merit = 1e300; info_best[6] = 1e300; relgap_it = 1e300;

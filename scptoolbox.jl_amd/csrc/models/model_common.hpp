@@ -50,6 +50,14 @@ struct ModelDefaults {
     // are zero in the columns >= lu_lead too (block-diagonal A and Phi).  0 / false: no assumption.
     static constexpr int lu_lead = 0;
     static constexpr bool lu_decoupled = false;
+    // STRUCTURAL PATTERN of the stage-local rows [hinge (ns) | linear (nl) | cone (4 nsoc)] for the node-parallel passes of K3
+    // (ipm2_kernel.hpp, the compact stage record).  kl_width = 0: Kl dense.  kl_width = KW > 0: ELL form -- row r has at most KW
+    // entries that can be non-zero, kl_col(r, s) is the column of slot s (ascending within a row, -1 = padding slot); every other
+    // entry of Kl is exactly 0.0 at every node for every data.  has_kp = false: Kp is exactly 0.0 (s, the linear and the cone rows
+    // do not depend on p).  K3 verifies the pattern against the assembled slab in every launch and fails the solve where it is wrong.
+    static constexpr int kl_width = 0;
+    static constexpr int kl_col(int, int slot) { return slot; }
+    static constexpr bool has_kp = true;
     template <class PP>
     SCP_DEV static double time_dilation(const PP&, const double*) { return 0.0; }
 };

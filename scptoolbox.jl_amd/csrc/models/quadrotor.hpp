@@ -94,6 +94,18 @@ struct Quadrotor : ModelDefaults {
 
     // ---- subproblem side: test/examples/quadrotor/definition.jl ----
     static constexpr int ns = 2, nl = 3, nsoc = 1, ng = 2, nic = 6, ntc = 6, npp = 12;  // pp = [r0 v0 rf vf]
+    // pattern of Kl (ModelDefaults): the columns s_eval / lin_rows / soc_rows below can write, at most three per row; Kp = 0
+    static constexpr int kl_width = 3;
+    static constexpr bool has_kp = false;
+    static constexpr int kl_col(int row, int slot)
+    {
+        constexpr int a0 = nx, a1 = nx + 1, a2 = nx + 2, sg = nx + 3;
+        constexpr int T[ns + nl + 4 * nsoc][kl_width] = {
+            {0, 1, 2}, {0, 1, 2},                                           // obstacles: position
+            {sg, -1, -1}, {sg, -1, -1}, {a2, sg, -1},                       // sigma bounds, tilt (a_z, sigma)
+            {sg, -1, -1}, {a0, -1, -1}, {a1, -1, -1}, {a2, -1, -1}};        // ||a|| <= sigma
+        return T[row][slot];
+    }
     // s_i = 1 - ||H_i (r - c_i)||, C = -grad  (definition.jl:255-290, ellipsoid.jl:99-118)
     SCP_DEV static void s_eval(const Params& P, double, int, const double* x, const double*, const double*,
                                double* s, double* C, double* Dm, double* G)

@@ -136,6 +136,19 @@ struct RocketLanding : ModelDefaults {
 
     // ---- subproblem side (builder-defined) over definition.jl:84-130 ----
     static constexpr int ns = 2, nl = 6, nsoc = 2, ng = 2, nic = 7, ntc = 6, npp = 6;  // pp = [r0 v0]
+    // pattern of Kl (ModelDefaults): the columns s_eval / lin_rows / soc_rows below can write, at most two per row; Kp = 0
+    static constexpr int kl_width = 2;
+    static constexpr bool has_kp = false;
+    static constexpr int kl_col(int row, int slot)
+    {
+        constexpr int z = 6, a0 = nx, a1 = nx + 1, a2 = nx + 2, xi = nx + 3;
+        constexpr int T[ns + nl + 4 * nsoc][kl_width] = {
+            {z, xi}, {z, xi},                                   // thrust bounds: (ln m, xi)
+            {0, 2}, {0, 2}, {1, 2}, {1, 2}, {z, -1}, {a2, xi},  // glide slope (r), ln m >= ln m_dry, pointing (a_z, xi)
+            {-1, -1}, {3, -1}, {4, -1}, {5, -1},                // ||v|| <= v_max
+            {xi, -1}, {a0, -1}, {a1, -1}, {a2, -1}};            // ||a|| <= xi
+        return T[row][slot];
+    }
     // exact thrust bounds in log-mass form: rho_min e^-z - xi <= 0, xi - rho_max e^-z <= 0
     SCP_DEV static void s_eval(const Params& P, double, int, const double* x, const double* u, const double*,
                                double* s, double* C, double* Dm, double* G)

@@ -16,8 +16,6 @@ pbm = pkg.PTR.create(pars, traj, batch_capacity=B)
 sol, h = pkg.PTR.solve(pbm, pp)
 import os
 names = ["G", "GT", "factor", "rhs+fwd", "bwd", "arrow", "finish", "total"]
-if "fprof" in os.environ.get("SCP_MI355X_LIB", ""):
-    names = ["f:Ysoc+Sz+C0", "f:chol Sz", "factor(total)", "f:Y", "f:cf+Snu", "f:chol Snu", "f:X", "total"]
 if "profo" in os.environ.get("SCP_MI355X_LIB", ""):
     names = ["residual passes+snapshots", "nt_update", "combined rhs", "refinement residuals", "refinement updates", "step-length pass", "step trial+update", "total"]
 acc = np.zeros(8)

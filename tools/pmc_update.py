@@ -39,11 +39,11 @@ def main():
         hist = {k: v for k, v in old.items() if k.startswith("round") and isinstance(v, dict)}
         if "FETCH_SIZE_kB_per_sub_launch" in old:
             hist["round%s_final" % old.get("round", "?")] = {k: old[k] for k in ("FETCH_SIZE_kB_per_sub_launch", "WRITE_SIZE_kB_per_sub_launch", "source") if k in old}
-        db["rocket_landing"] = dict(round=6, N=100, kernel=fe[0], sub_launch_problems=sub, streams=streams,
+        db["rocket_landing"] = dict(round=7, N=100, kernel=fe[0], sub_launch_problems=sub, streams=streams,
                                     FETCH_SIZE_kB_per_sub_launch=fe[2], WRITE_SIZE_kB_per_sub_launch=wr[2], dispatches=fe[1],
                                     commit=commit, sources_sha16=bench.sources_sha16(bench.K3_SOURCES),
-                                    source="%s (rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes of `python bench.py "
-                                           "--steps 1 --warmup 0 --no-cpu-baseline --no-generic --no-solo`)" % os.path.relpath(path, ROOT),
+                                    source="%s (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, counter-only passes (no tracing), separate runs of `python bench.py "
+                                           "--full --steps 1 --warmup 0 --no-cpu-baseline --no-generic --no-solo --no-convergence`)" % os.path.relpath(path, ROOT),
                                     note="8 B/lane loads: the gfx950 x2 FETCH_SIZE correction for 16 B/lane streaming reads is not applied "
                                          "(uncalibrated width); counters are in kB", **hist)
     elif what == "k1v":        # python tools/pmc_update.py k1v <sq_counters.csv> <dispatches per kernel>: executed VALU instructions of the headline's discretize! launch
