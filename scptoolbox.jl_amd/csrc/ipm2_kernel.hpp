@@ -121,16 +121,16 @@ struct Ipm2Work {
     using PT = StagePat<M>;
     __host__ __device__ static long XI(int N) { return (long)N * (S::nz + S::AS) + S::npa + S::AG; }
     __host__ __device__ static long ROWS(int N) { return (long)N * S::RS + S::RG; }
-    // per-node factor record: [Li tri(nz) | Lni tri(MM) | X MM*nz | Y nz*MM | row coefficients MM*2]
+    // per-node factor record: [Li tri(nz) | Lni tri(MM) | X MM*nz | Y nz*MM] -- exactly what a chain sweep reads (the per-row
+    // elimination coefficients, which only factor and newton_rhs read, have an array of their own: Off::cf)
     // Packed per node type: MM = number of nu-rows of the node (MNU at the two boundary nodes, MNU_MID inside).
-    // Only the first f_used(MM) doubles of a record are ever written / read (327 of 592 for a rocket mid node).
+    // Only the first f_used(MM) doubles of a record are ever written / read (309 of 560 for a rocket mid node).
     // the two inverse Cholesky factors are lower triangular and stored packed by rows: entry (i, j<=i) at i(i+1)/2 + j
     __host__ __device__ static constexpr int tri(int n) { return n * (n + 1) / 2; }
     __host__ __device__ static constexpr int f_lni(int) { return tri(S::nz); }
     __host__ __device__ static constexpr int f_x(int MM) { return tri(S::nz) + tri(MM); }
     __host__ __device__ static constexpr int f_y(int MM) { return f_x(MM) + MM * S::nz; }
-    __host__ __device__ static constexpr int f_cf(int MM) { return f_y(MM) + S::nz * MM; }
-    __host__ __device__ static constexpr int f_used(int MM) { return f_cf(MM) + 2 * MM; }
+    __host__ __device__ static constexpr int f_used(int MM) { return f_y(MM) + S::nz * MM; }
     static constexpr int FR = (f_used(S::MNU) + 7) & ~7;
     static constexpr int HS = (S::nz * S::nz + 1) & ~1;   // stride of an H0 block
     struct Off {
@@ -138,6 +138,7 @@ struct Ipm2Work {
         long s, lam, rz, w, rtil, ds, dl, gd, r2, el, hneg, ge;    // row-vectors
         long socW;                                                // [N][nsoc][36]: W(16) Wi(16) lamt(4)
         long F, C0, Ycz, Ycnu, fb, ft, nuv;                       // newton (F: per-node factor records)
+        long cf;                                                  // [N][MNU][2]: per-row elimination coefficients (factor_pre -> factor, newton_rhs)
         long tl;                                                  // [N][4 nsoc]: W^-1 (W^-1 rtil) of the cone rows (newton_rhs)
         long H0;                                                  // [N][HS]: chain-independent part of Sz_k (factor_pre)
         long sc;                                                  // [N][SRC]: compact stage records (StagePat; build_constants)
@@ -161,6 +162,7 @@ struct Ipm2Work {
         o.Ycz = take((long)N * S::nz * S::npa); o.Ycnu = take((long)N * S::MNU * S::npa);
         o.fb = take((long)N * S::nz); o.ft = take((long)N * S::MNU);
         o.nuv = take((long)N * S::MNU);
+        o.cf = take((long)N * S::MNU * 2);
         o.tl = take((long)N * 4 * (S::nsoc > 0 ? S::nsoc : 1));
         o.H0 = take((long)N * HS);
         o.sc = take((long)N * PT::SRC);
@@ -315,6 +317,10 @@ struct Ipm2 {
     // are issued only for the two boundary nodes (wave-uniform branch)
     static constexpr int FU_MID = WK::f_used(MMID), FU_BND = WK::f_used(MNU);
     static constexpr int NPREF_MID = (FU_MID + 63) / 64;
+    // the loads of a record are clamped to its stride FR, so what they cover may overhang what is used; every index a sweep stages
+    // has a slot in Fpad (pad_off: a used entry its slot, the overhang a per-lane dump slot behind the FSLOTS used ones)
+    static_assert(FU_MID <= FU_BND && FU_BND <= FR && NPREF_MID <= NPREF, "factor record: interior part within the boundary part within the stride");
+    static_assert(FPAD >= FSLOTS * 16 + 64, "Fpad: one dump slot per lane behind the used slots");
     __device__ __forceinline__ bool bnd(int k) const { return k == 0 || k == N - 1; }
     __device__ __forceinline__ void prefetchF(int k)
     {
@@ -334,7 +340,7 @@ struct Ipm2 {
     __device__ __forceinline__ void storeF(int k)
     {
         double* dst = W + wo.F + (long)k * FR;
-        const int nu_ = bnd(k) ? WK::f_cf(MNU) : WK::f_cf(MMID);   // (the row coefficients behind it are written by factor_pre)
+        const int nu_ = bnd(k) ? FU_BND : FU_MID;
         for (int idx = lane; idx < nu_; idx += 64) dst[idx] = L->st.F[idx];
     }
     // views of the staged factor record; mm = nu-rows of the node the record belongs to (leading dimension of Lni, Y)
@@ -342,7 +348,6 @@ struct Ipm2 {
     __device__ __forceinline__ double* Lni(int mm) const { return L->st.F + WK::f_lni(mm); }
     __device__ __forceinline__ double* Xm(int mm) const { return L->st.F + WK::f_x(mm); }
     __device__ __forceinline__ double* Ym(int mm) const { return L->st.F + WK::f_y(mm); }
-    __device__ __forceinline__ double* Cf(int mm) const { return L->st.F + WK::f_cf(mm); }
     // row-record / cone-scaling / primal prefetch (one node ahead), committed to LDS at the top of the node
     __device__ __forceinline__ void pf_rows(double (&r)[NROWR], const double* v, int k) const
     {

@@ -251,7 +251,7 @@ __device__ __forceinline__ void Ipm2<M>::factor_pre(const double* w, double (&Dp
                 const double kap = (c_ish ? 1.0 : 4.0) * w1 * w2 * iWt;
                 cf0 = lv ? (c_ish ? w1 : (w1 - w2)) * iWt : 0.0;   // coefficient of rth in tau
                 cf1 = lv ? fast_rcp(kap) : 1.0;                     // 1/kappa (1 for absent rows: identity pivot)
-                double* cf = W + wo.F + (long)kk * FR + (bndk ? WK::f_cf(MNU) : WK::f_cf(MMID)) + c * 2;
+                double* cf = W + wo.cf + ((long)kk * MNU + c) * 2;
                 cf[0] = cf0; cf[1] = cf1;
             }
         }
@@ -449,19 +449,19 @@ __device__ __forceinline__ void Ipm2<M>::factor(double* w)
         for (int i = 0; i < npa * npa; i++) Dp[i] = wave_sum(Dp[i]);
     }
     // ---- chain: the first two and the last node are peeled off so that the hot loop holds a single instantiation ----
-    const double* H0g = W + wo.H0; const double* Fg = W + wo.F;
+    const double* H0g = W + wo.H0; const double* cfg = W + wo.cf;
     const int col_ = lane & 15, kq_ = lane >> 4;
     int offH[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) { const int a_ = kq_ + 4 * q; offH[q] = (a_ < nz ? a_ : nz - 1) * nz + (col_ < nz ? col_ : nz - 1); }
-    const int offCfM = WK::f_cf(MMID) + 2 * (col_ < MMID ? col_ : MMID - 1) + 1, offCfB = WK::f_cf(MNU) + 2 * (col_ < MNU ? col_ : MNU - 1) + 1;
+    const int offCfM = 2 * (col_ < MMID ? col_ : MMID - 1) + 1, offCfB = 2 * (col_ < MNU ? col_ : MNU - 1) + 1;
     const int offC0 = lane < nz * np ? lane : (nz * np > 0 ? nz * np - 1 : 0);
     double pH[4], pCf, pC0, cH[4], cCf = 0.0, cC0 = 0.0;
     auto pf_pre = [&](int k) {
         const double* hb = H0g + (long)k * HS;
 #pragma unroll
         for (int q = 0; q < 4; q++) pH[q] = hb[offH[q]];
-        pCf = Fg[(long)k * FR + (bnd(k) ? offCfB : offCfM)];
+        pCf = cfg[(long)k * MNU * 2 + (bnd(k) ? offCfB : offCfM)];
         pC0 = np > 0 ? gC0[(long)k * nz * npa + offC0] : 0.0;
     };
     static_assert(nz * npa <= 64, "one C0 entry per lane");
@@ -593,8 +593,8 @@ __device__ __forceinline__ void Ipm2<M>::solve_backward_cols()
 // Writes the MAIN part of dxi (dz, dp) and nu; finish_direction() completes aux / dlam.
 // ------------------------------------------------------------------------------------------------
 // ---- chain sweeps on the padded per-lane factor record (Lds::Fpad) ----
-// offset in Fpad of packed entry p of a factor record with MM nu-rows, for the forward (FWD) or the backward sweep; entries no
-// sweep reads (the row coefficients, padding) go to per-lane dump slots
+// offset in Fpad of packed entry p of a factor record with MM nu-rows, for the forward (FWD) or the backward sweep; what a load
+// covers beyond the record's used part (padding, the head of the next record) goes to per-lane dump slots
 template <class M>
 template <bool FWD, int MM>
 __device__ __forceinline__ int Ipm2<M>::pad_off(int p) const
@@ -849,7 +849,7 @@ __device__ __forceinline__ void Ipm2<M>::newton_rhs(const double* w, const doubl
             int ix = c_bc ? c_gx[gofs] : xa + c_ox;
             ia = lv ? ia : rbi; ib = lv ? ib : rbi; ix = lv ? ix : 0;
             const double v1 = w[ia], v2 = w[ib], u1 = rtil[ia], u2 = rtil[ib], rxa = rxv[ix];
-            const double* cf = W + wo.F + (long)kk * FR + (bndk ? WK::f_cf(MNU) : WK::f_cf(MMID)) + (lv ? c : 0) * 2;
+            const double* cf = W + wo.cf + ((long)kk * MNU + (lv ? c : 0)) * 2;
             const double cf0 = cf[0], cf1 = cf[1];
             const double r1 = v1 * u1, r2 = v2 * u2;
             const double rth = -rxa + r1 + r2;

@@ -39,7 +39,7 @@ def main():
         hist = {k: v for k, v in old.items() if k.startswith("round") and isinstance(v, dict)}
         if "FETCH_SIZE_kB_per_sub_launch" in old:
             hist["round%s_final" % old.get("round", "?")] = {k: old[k] for k in ("FETCH_SIZE_kB_per_sub_launch", "WRITE_SIZE_kB_per_sub_launch", "source") if k in old}
-        db["rocket_landing"] = dict(round=7, N=100, kernel=fe[0], sub_launch_problems=sub, streams=streams,
+        db["rocket_landing"] = dict(round=8, N=100, kernel=fe[0], sub_launch_problems=sub, streams=streams,
                                     FETCH_SIZE_kB_per_sub_launch=fe[2], WRITE_SIZE_kB_per_sub_launch=wr[2], dispatches=fe[1],
                                     commit=commit, sources_sha16=bench.sources_sha16(bench.K3_SOURCES),
                                     source="%s (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, counter-only passes (no tracing), separate runs of `python bench.py "
