@@ -132,11 +132,54 @@ struct Ipm2Work {
     __host__ __device__ static constexpr int f_y(int MM) { return f_x(MM) + MM * S::nz; }
     __host__ __device__ static constexpr int f_used(int MM) { return f_y(MM) + S::nz * MM; }
     static constexpr int FR = (f_used(S::MNU) + 7) & ~7;
-    static constexpr int HS = (S::nz * S::nz + 1) & ~1;   // stride of an H0 block
+    // H0 block of a node: the LOWER TRIANGLE packed by rows, entry (a, c <= a) at h0_off(a, c) -- the chain's Cholesky (chol_reg) consumes
+    // no entry above the diagonal, so none is stored.  h0_lane(lane, q): what lane `lane` loads into slot q of the MFMA accumulator
+    // (row (lane >> 4) + 4 q, column lane & 15, both clamped to the block); a slot above the diagonal takes the mirrored entry, whose
+    // value nobody consumes.
+    static constexpr int H0_DUMP = tri(S::nz);         // one slot behind the triangle: where factor_pre's lanes put what is not stored
+    static constexpr int HS = (tri(S::nz) + 2) & ~1;   // stride of an H0 block
+    __host__ __device__ static constexpr int h0_off(int a, int c) { return a * (a + 1) / 2 + c; }
+    __host__ __device__ static constexpr int h0_lane(int lane, int q)
+    {
+        const int a0 = (lane >> 4) + 4 * q, c0 = lane & 15, a = a0 < S::nz ? a0 : S::nz - 1, c = c0 < S::nz ? c0 : S::nz - 1;
+        return a >= c ? h0_off(a, c) : h0_off(c, a);
+    }
+    static constexpr bool h0_valid()
+    {
+        int seen[tri(S::nz)] = {};
+        for (int a = 0; a < S::nz; a++)
+            for (int c = 0; c <= a; c++) { const int o = h0_off(a, c); if (o < 0 || o >= tri(S::nz) || seen[o]++) return false; }
+        for (int o = 0; o < tri(S::nz); o++) if (seen[o] != 1) return false;
+        for (int lane = 0; lane < 64; lane++)
+            for (int q = 0; q < 4; q++) {
+                const int o = h0_lane(lane, q), a = (lane >> 4) + 4 * q, c = lane & 15;
+                if (o < 0 || o >= tri(S::nz)) return false;
+                if (a < S::nz && c <= a && o != h0_off(a, c)) return false;   // a consumed slot loads its own entry
+            }
+        return H0_DUMP >= tri(S::nz) && H0_DUMP < HS;   // the dump slot is no entry's slot and lies inside the block
+    }
+    // Cone scalings, per cone: [W lower (10) | W^-1 lower (10) | lamt (4)].  Both 4 x 4 blocks are symmetric bit for bit (nt_update builds
+    // entry (r, q) from wb[r] * wb[q], and a product does not depend on the order of its factors): the lower triangle, packed by rows,
+    // carries all of them, and entry (r, q) of either block is read at sym(r, q).
+    static constexpr int SW_W = 0, SW_WI = 10, SW_LT = 20, SOCR = 24;
+    __host__ __device__ static constexpr int sym(int r, int q) { return r >= q ? r * (r + 1) / 2 + q : q * (q + 1) / 2 + r; }
+    static constexpr bool sym_valid()
+    {
+        int seen[10] = {};
+        for (int r = 0; r < 4; r++)
+            for (int q = 0; q < 4; q++) {
+                const int o = sym(r, q);
+                if (o < 0 || o >= 10 || o != sym(q, r)) return false;
+                if (q <= r) seen[o]++;
+            }
+        for (int o = 0; o < 10; o++) if (seen[o] != 1) return false;
+        return SW_W + 10 <= SW_WI && SW_WI + 10 <= SW_LT && SW_LT + 4 <= SOCR;
+    }
+    static_assert(SOCR % 2 == 0, "cone records keep 16-byte alignment");
     struct Off {
         long xi, dxi, rx, exi, best, rxe, cv, qd;                  // xi-vectors
         long s, lam, rz, w, rtil, ds, dl, gd, r2, el, hneg, ge;    // row-vectors
-        long socW;                                                // [N][nsoc][36]: W(16) Wi(16) lamt(4)
+        long socW;                                                // [N][nsoc][SOCR]: W lower (10) | Wi lower (10) | lamt (4)
         long F, C0, Ycz, Ycnu, fb, ft, nuv;                       // newton (F: per-node factor records)
         long cf;                                                  // [N][MNU][2]: per-row elimination coefficients (factor_pre -> factor, newton_rhs)
         long tl;                                                  // [N][4 nsoc]: W^-1 (W^-1 rtil) of the cone rows (newton_rhs)
@@ -156,9 +199,9 @@ struct Ipm2Work {
         o.s = take(rows); o.lam = take(rows); o.rz = take(rows); o.w = take(rows); o.rtil = take(rows);
         o.ds = take(rows); o.dl = take(rows); o.gd = take(rows); o.r2 = take(rows); o.el = take(rows);
         o.hneg = take(rows); o.ge = take(rows);
-        o.socW = take((long)N * (S::nsoc > 0 ? S::nsoc : 1) * 36);
+        o.socW = take((long)N * (S::nsoc > 0 ? S::nsoc : 1) * SOCR);
         o.F = take((long)N * FR);
-        o.C0 = take((long)N * S::nz * S::npa);
+        o.C0 = take(PT::HASKP ? (long)N * S::nz * S::npa : 0);   // a model without Kp: C0 is a declared zero, neither stored nor read
         o.Ycz = take((long)N * S::nz * S::npa); o.Ycnu = take((long)N * S::MNU * S::npa);
         o.fb = take((long)N * S::nz); o.ft = take((long)N * S::MNU);
         o.nuv = take((long)N * S::MNU);
@@ -178,6 +221,10 @@ struct Ipm2 {
     using WK = Ipm2Work<M>;
     using PT = StagePat<M>;
     static_assert(PT::valid(), "kl_col: columns below nz, ascending within a row, padding slots last");
+    static_assert(WK::sym_valid(), "cone scalings: sym maps the lower triangle of a 4 x 4 block one to one onto its 10 slots, both orders of (r, q) alike");
+    static constexpr int SOCR = WK::SOCR, SW_W = WK::SW_W, SW_WI = WK::SW_WI, SW_LT = WK::SW_LT;
+    __host__ __device__ static constexpr int sym(int r, int q) { return WK::sym(r, q); }
+    static_assert(WK::h0_valid(),"H0: the packed lower triangle is a bijection onto [0, tri(nz)), every accumulator load stays inside it");
     static constexpr int KW = PT::KW, SRC = PT::SRC, C_EU = PT::C_EU, C_KL = PT::C_KL, C_KP = PT::C_KP;
     static constexpr int nx = S::nx, nu = S::nu, np = S::np, npa = S::npa, nz = S::nz, ns = S::ns, nl = S::nl,
                          nsoc = S::nsoc, ml = S::ml, ng = S::ng, nic = S::nic, ntc = S::ntc, nbc = S::nbc, RS = S::RS,
@@ -211,7 +258,6 @@ struct Ipm2 {
         double r0[RS], r1[RS];   // row staging
         double g0[RG], g1[RG];   // global-row staging
         double dcur[nx], dprev[nx];
-        double soc[NSOC1 * 36];
         double Ysoc[4 * NSOC1 * nz];
         double Cz[nz * npa], cb[nz * npa], ct[MNU * npa];
         double thp[MNU], nuk[MNU];
@@ -232,8 +278,8 @@ struct Ipm2 {
     double ttrp, cost_const;
     double pre[NPRE];
     double preF[NPREF];
-    static constexpr int NROWR = (RS + 63) / 64, NSOCR = (NSOC1 * 36 + 63) / 64;
-    double pR0[NROWR], pR1[NROWR], pS[NSOCR], pZ, pA, pN, pB1, pB2;
+    static constexpr int NROWR = (RS + 63) / 64;
+    double pR0[NROWR], pR1[NROWR], pZ, pA, pN, pB1, pB2;
 
     __device__ __forceinline__ long long tick() const { return SCP_TICK(); }
     // lsync: ordering point for LDS traffic inside the (single) wave.  LDS instructions of one wave execute
@@ -359,23 +405,6 @@ struct Ipm2 {
 #pragma unroll
         for (int i = 0; i < NROWR; i++) { const int idx = lane + 64 * i; if (idx < RS) dst[idx] = r[i]; }
     }
-    // cone scalings for the horizon sweeps: only W^-1 (entries [16, 32) of each 36-double cone record) is read there
-    static constexpr int NSOCW = (NSOC1 * 16 + 63) / 64;
-    __device__ __forceinline__ void pf_soc(int k)
-    {
-        const double* src = W + wo.socW + (long)k * nsoc * 36;
-#pragma unroll
-        for (int i = 0; i < NSOCW; i++) {
-            int idx = lane + 64 * i;
-            idx = idx < nsoc * 16 ? idx : (nsoc > 0 ? nsoc * 16 - 1 : 0);
-            pS[i] = src[(idx / 16) * 36 + 16 + idx % 16];
-        }
-    }
-    __device__ __forceinline__ void cm_soc()
-    {
-#pragma unroll
-        for (int i = 0; i < NSOCW; i++) { const int idx = lane + 64 * i; if (idx < nsoc * 16) L->soc[(idx / 16) * 36 + 16 + idx % 16] = pS[i]; }
-    }
     __device__ __forceinline__ void load_rows(double* dst, const double* v, int k) const
     {
         for (int r = lane; r < RS; r += 64) dst[r] = v[(long)k * RS + r];
@@ -412,6 +441,52 @@ struct Ipm2 {
             r0.store(); r1.store();
         }
     }
+    // ---------------- flat reductions that leave out the rows with a declared zero coefficient ----------------
+    // The flat reductions over (node, row) items (the p-part of GT_apply, arrow_dot) give item idx = k * NR + r to lane idx % 64, and a
+    // lane adds its items in ascending idx to a partial sum that starts at +0.0.  An item whose coefficient is a declared exact zero
+    // adds +-0.0, which leaves such a sum as it is, bit for bit (x + +-0.0 = x for x != 0, +0.0 + +-0.0 = +0.0, and a sum that
+    // starts at +0.0 never becomes -0.0).  ItemWalk steps through the lane's OWN items whose row lies in [LO, HI) and no others, in
+    // the same order, so the partial sums -- and the wave sum over them -- are the ones of the sweep over all items.
+    // skip(r): how many of the lane's next items (stride 64) to pass over from an item of row r; one nibble per row, no table in memory.
+    template <int NR, int LO, int HI>
+    struct ItemWalk {
+        static_assert(NR >= 1 && NR <= 32 && 0 <= LO && LO < HI && HI <= NR, "item walk: rows [LO, HI) of at most 32");
+        static constexpr int NEVER = 15;   // a lane whose rows never fall into [LO, HI) (64 % NR and NR share a factor)
+        static constexpr int skip(int r)
+        {
+            for (int t = 0; t < NR; t++) { const int q = (r + 64 * t) % NR; if (q >= LO && q < HI) return t; }
+            return NEVER;
+        }
+        static constexpr bool valid()
+        {
+            for (int r = 0; r < NR; r++) {
+                const int t = skip(r);
+                if (t == NEVER) { for (int u = 0; u < NR; u++) { const int q = (r + 64 * u) % NR; if (q >= LO && q < HI) return false; } }
+                else {
+                    if (t > 14) return false;
+                    const int q = (r + 64 * t) % NR;
+                    if (!(q >= LO && q < HI)) return false;
+                    for (int u = 0; u < t; u++) { const int p = (r + 64 * u) % NR; if (p >= LO && p < HI) return false; }
+                }
+            }
+            return true;
+        }
+        static constexpr unsigned long long word(int h)
+        {
+            unsigned long long w = 0;
+            for (int i = 0; i < 16; i++) w |= (unsigned long long)(16 * h + i < NR ? skip(16 * h + i) : NEVER) << (4 * i);
+            return w;
+        }
+        // the first item at or after item idx of this lane whose row is kept; a value >= cnt when there is none
+        __device__ __forceinline__ static int seek(int idx, int cnt)
+        {
+            const int r = idx % NR;
+            const unsigned long long w = r < 16 ? std::integral_constant<unsigned long long, word(0)>::value
+                                                : std::integral_constant<unsigned long long, word(1)>::value;
+            const int t = (int)((w >> (4 * (r & 15))) & 15ull);
+            return t == NEVER ? cnt : idx + 64 * t;
+        }
+    };
     // ---------------- compact stage record (StagePat): E's input block and the pattern's Kl / Kp entries ----------------
     __device__ __forceinline__ const double* Crec(int k) const { return W + wo.sc + (long)k * SRC; }
     // f(std::integral_constant<int, R>) for the rows R in [LO, HI): the row is a compile-time value in f
@@ -700,6 +775,31 @@ struct Ipm2 {
             for (int j = 0; j < npa; j++) pacc[j] = 0.0;
             constexpr int NR = nx + ml;
             const int cnt = N * NR;
+            if constexpr (!PT::HASKP) {
+                // Kp is a declared exact zero: of the NR rows of a node only the nx dynamics rows (Fp) can add anything but +-0.0.  Each
+                // lane walks its own dynamics items of the (node, row) item space, two in flight, in the order of the full sweep.
+                using Wk = ItemWalk<NR, 0, nx>;
+                static_assert(Wk::valid(), "item walk over the dynamics rows of [Fp; Kp]");
+                int idx = Wk::seek(lane, cnt);
+#pragma unroll 1
+                while (__builtin_amdgcn_ballot_w64(idx < cnt) != 0) {
+                    double m_[2], c_[2][npa];
+#pragma unroll
+                    for (int u = 0; u < 2; u++) {
+                        const bool ok = idx < cnt;
+                        const int k = ok ? idx / NR : N - 1, r = ok ? idx - k * NR : 0;
+                        const double fa = (ok && k < N - 1) ? 1.0 : 0.0;
+                        m_[u] = fa * (ROW(mu, k, r) - ROW(mu, k, nx + r));
+#pragma unroll
+                        for (int j = 0; j < np; j++) c_[u][j] = Pg[(long)k * SR + S::O_FP + r * npa + j];
+                        idx = ok ? Wk::seek(idx + 64, cnt) : idx;
+                    }
+#pragma unroll
+                    for (int u = 0; u < 2; u++)
+#pragma unroll
+                        for (int j = 0; j < np; j++) pacc[j] += c_[u][j] * m_[u];
+                }
+            } else {
 #pragma unroll 1
             for (int base = 0; base < cnt; base += 128) {
                 double m_[2], c_[2][npa];
@@ -723,6 +823,7 @@ struct Ipm2 {
                 for (int u = 0; u < 2; u++)
 #pragma unroll
                     for (int j = 0; j < np; j++) pacc[j] += c_[u][j] * m_[u];
+            }
             }
 #pragma unroll
             for (int j = 0; j < np; j++) {

@@ -131,7 +131,7 @@ __device__ __forceinline__ double bsub16(double v, const double (&lcol)[n], doub
 template <class M>
 __device__ __forceinline__ void Ipm2<M>::factor_pre(const double* w, double (&Dp)[npa * npa])
 {
-    double* H0g = W + wo.H0; double* gC0 = W + wo.C0;
+    double* H0g = W + wo.H0;
     const double* socW = W + wo.socW;
     const int g = lane >> 4, sl = lane & 15;
     const int jc = sl < nz ? sl : nz - 1;
@@ -160,15 +160,17 @@ __device__ __forceinline__ void Ipm2<M>::factor_pre(const double* w, double (&Dp
         for (int i = 0; i < nl; i++) om[i] = w[rb + S::R_LIN + i];
 #pragma unroll
         for (int c = 0; c < nsoc; c++) {
-            const double* Wi = socW + ((long)kk * nsoc + c) * 36 + 16;
-            double kc[4];
+            const double* Wi = socW + ((long)kk * nsoc + c) * SOCR + SW_WI;
+            double kc[4], wi[10];
+#pragma unroll
+            for (int q = 0; q < 10; q++) wi[q] = Wi[q];
 #pragma unroll
             for (int q = 0; q < 4; q++) kc[q] = kca[4 * c + q];
 #pragma unroll
             for (int rr = 0; rr < 4; rr++) {
                 double acc = 0.0;
 #pragma unroll
-                for (int q = 0; q < 4; q++) acc += Wi[rr * 4 + q] * kc[q];
+                for (int q = 0; q < 4; q++) acc += wi[sym(rr, q)] * kc[q];
                 z[nl + 4 * c + rr] = acc; om[nl + 4 * c + rr] = 1.0;
             }
         }
@@ -203,12 +205,17 @@ __device__ __forceinline__ void Ipm2<M>::factor_pre(const double* w, double (&Dp
         }
         const double qd = Pk_[S::O_QD + jc];
 #pragma unroll
-        for (int a_ = 0; a_ < nz; a_++) H0g[(long)kk * HS + a_ * nz + jc] = h[a_] + ((a_ == jc) ? qd : 0.0);
-        // arrow: C0_k[a = jc][j] and the p x p term (a model without Kp: both are sums of exact zeros)
-        if constexpr (np > 0 && !PT::HASKP) {
-#pragma unroll
-            for (int j = 0; j < np; j++) gC0[(long)kk * nz * npa + jc * npa + j] = 0.0;
-        } else if constexpr (np > 0) {
+        for (int a_ = 0; a_ < nz; a_++) {
+            // column jc of the lower triangle: rows a >= jc (packed, Ipm2Work::h0_off).  The entries above the diagonal go to the block's
+            // dump slot, which nobody reads: a select of the address, not a branch around the store -- branches split the body into
+            // blocks and the pass spills (336 -> 1008 B of scratch per lane, measured on the cross-compile)
+            const int off = a_ >= jc ? WK::h0_off(a_, jc) : WK::H0_DUMP;
+            H0g[(long)kk * HS + off] = h[a_] + ((a_ == jc) ? qd : 0.0);
+        }
+        // arrow: C0_k[a = jc][j] and the p x p term (a model without Kp: both are sums of exact zeros -- C0 is not stored, the chain
+        // and arrow_dot take it as the literal 0.0)
+        if constexpr (np > 0 && PT::HASKP) {
+            double* gC0 = W + wo.C0;
             double kp[nl > 0 ? nl : 1][npa];
 #pragma unroll
             for (int i = 0; i < nl; i++)
@@ -436,12 +443,12 @@ __device__ __forceinline__ void Ipm2<M>::factor(double* w)
 {
     const long long t0_ = tick();
     const double* socW = W + wo.socW;
-    double* gC0 = W + wo.C0; double* gYcz = W + wo.Ycz; double* gYcnu = W + wo.Ycnu;
+    double* gYcz = W + wo.Ycz; double* gYcnu = W + wo.Ycnu;
     double Dp[npa * npa];
 #pragma unroll
     for (int i = 0; i < npa * npa; i++) Dp[i] = 0.0;  // per-lane partial sums (factor_pre), reduced below
     load_grows(L->g0, w);
-    (void)socW; (void)gC0; (void)gYcz; (void)gYcnu;
+    (void)socW; (void)gYcz; (void)gYcnu;
     gsync();
     factor_pre(w, Dp);
     if (np > 0) {
@@ -450,19 +457,21 @@ __device__ __forceinline__ void Ipm2<M>::factor(double* w)
     }
     // ---- chain: the first two and the last node are peeled off so that the hot loop holds a single instantiation ----
     const double* H0g = W + wo.H0; const double* cfg = W + wo.cf;
-    const int col_ = lane & 15, kq_ = lane >> 4;
+    const int col_ = lane & 15;
     int offH[4];
 #pragma unroll
-    for (int q = 0; q < 4; q++) { const int a_ = kq_ + 4 * q; offH[q] = (a_ < nz ? a_ : nz - 1) * nz + (col_ < nz ? col_ : nz - 1); }
+    for (int q = 0; q < 4; q++) offH[q] = WK::h0_lane(lane, q);   // (a slot above the diagonal: the mirrored entry, never consumed)
     const int offCfM = 2 * (col_ < MMID ? col_ : MMID - 1) + 1, offCfB = 2 * (col_ < MNU ? col_ : MNU - 1) + 1;
-    const int offC0 = lane < nz * np ? lane : (nz * np > 0 ? nz * np - 1 : 0);
     double pH[4], pCf, pC0, cH[4], cCf = 0.0, cC0 = 0.0;
     auto pf_pre = [&](int k) {
         const double* hb = H0g + (long)k * HS;
 #pragma unroll
         for (int q = 0; q < 4; q++) pH[q] = hb[offH[q]];
         pCf = cfg[(long)k * MNU * 2 + (bnd(k) ? offCfB : offCfM)];
-        pC0 = np > 0 ? gC0[(long)k * nz * npa + offC0] : 0.0;
+        if constexpr (np > 0 && PT::HASKP) {
+            const int offC0 = lane < nz * np ? lane : nz * np - 1;
+            pC0 = (W + wo.C0)[(long)k * nz * npa + offC0];
+        } else pC0 = 0.0;   // no Kp: the arrow accumulation of the chain starts from the literal zero
     };
     static_assert(nz * npa <= 64, "one C0 entry per lane");
     // the chain reads D, E, Fp and the HINGE rows of Kl / Kp only (the linear and cone rows went into H0 / C0 in factor_pre): half of a stage record
@@ -770,16 +779,26 @@ __device__ __forceinline__ void Ipm2<M>::newton_rhs(const double* w, const doubl
     if (nsoc > 0) {
         for (int idx = lane; idx < N * nsoc; idx += 64) {
             const int k = idx / NSOC1, c = idx % NSOC1;
-            const double* Wi = socW + (long)idx * 36 + 16;
-            double wi[16], rt4[4], t1[4];
+            const double* Wi = socW + (long)idx * SOCR + SW_WI;
+            double wi[10], rt4[4], t1[4];
 #pragma unroll
-            for (int q = 0; q < 16; q++) wi[q] = Wi[q];
+            for (int q = 0; q < 10; q++) wi[q] = Wi[q];
 #pragma unroll
             for (int q = 0; q < 4; q++) rt4[q] = rtil[(long)k * RS + S::R_SOC + 4 * c + q];
 #pragma unroll
-            for (int r = 0; r < 4; r++) { double acc = 0.0; for (int q = 0; q < 4; q++) acc += wi[r * 4 + q] * rt4[q]; t1[r] = acc; }
+            for (int r = 0; r < 4; r++) {
+                double acc = 0.0;
 #pragma unroll
-            for (int r = 0; r < 4; r++) { double acc = 0.0; for (int q = 0; q < 4; q++) acc += wi[r * 4 + q] * t1[q]; tlv[(long)idx * 4 + r] = acc; }
+                for (int q = 0; q < 4; q++) acc += wi[sym(r, q)] * rt4[q];
+                t1[r] = acc;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                double acc = 0.0;
+#pragma unroll
+                for (int q = 0; q < 4; q++) acc += wi[sym(r, q)] * t1[q];
+                tlv[(long)idx * 4 + r] = acc;
+            }
         }
         gsync();
     }
@@ -802,7 +821,6 @@ __device__ __forceinline__ void Ipm2<M>::newton_rhs(const double* w, const doubl
         const bool kv = k < N;
         const int kk = kv ? k : N - 1;
         const long rb = (long)kk * RS;
-        const double* Pk_ = Pg + (long)kk * SR;
         const double* Ck_ = Crec(kk);
         // ---- b_k[jc]: trust-region pair of component jc + group sums by row broadcast ----
         const double w1 = w[rb + S::R_TR0 + jc], w2 = w[rb + S::R_TR1 + jc], t1 = rtil[rb + S::R_TR0 + jc], t2 = rtil[rb + S::R_TR1 + jc];
@@ -857,8 +875,10 @@ __device__ __forceinline__ void Ipm2<M>::newton_rhs(const double* w, const doubl
             const double tv = lv ? (-(r1 - (c_ish ? 0.0 : r2)) + cf0 * rth) * cf1 : 0.0;
             ft[(long)kk * MNU + c] = tv;
         }
-        // ---- arrow right-hand side: bp += Kp' tl over the linear and cone rows ----
-        if (np > 0) {
+        // ---- arrow right-hand side: bp += Kp' tl over the linear and cone rows (a model without Kp: every term is +-0.0 * tl, and bp,
+        // a sum that starts at +0.0, stays +0.0 -- nothing is loaded) ----
+        if constexpr (np > 0 && PT::HASKP) {
+            const double* Pk_ = Pg + (long)kk * SR;
             constexpr int NZR = nl + 4 * nsoc;
 #pragma unroll
             for (int r0_ = 0; r0_ < NZR; r0_ += 16) {
@@ -888,13 +908,45 @@ __device__ __forceinline__ void Ipm2<M>::newton_rhs(const double* w, const doubl
 // (node, row) items of the z rows, the dynamics and the hinge rows (coefficients straight from the slab / the C0 workspace, two items per
 // lane in flight, branch-free); the boundary-condition rows of the first and the last node come from the global record.  Per-lane
 // partial sums: the caller reduces (round 6; before: a node loop through LDS with 27 of 64 lanes busy).
+// A model without Kp (has_kp = false): C0 and the hinge rows' Kp are declared zeros, so of that item space only the dynamics rows
+// are visited -- by each lane in the order in which the full sweep gave them to it (ItemWalk) -- and neither C0 nor yz is read.
 template <class M>
 template <int NC>
 __device__ __forceinline__ void Ipm2<M>::arrow_dot(const double* yz, const double* yn, double (&acc)[npa * NC])
 {
-    const double* gC0 = W + wo.C0;
     constexpr int NR = nz + nx + ns;
     const int cnt = N * NR;
+    if constexpr (np > 0 && !PT::HASKP) {
+        // no Kp: the coefficient of a z row (C0) and of a hinge row (Kp) is a declared exact zero, and what such an item adds to a
+        // partial sum is +-0.0.  Each lane walks its own dynamics items (Fp) of the item space, in the order of the full sweep (ItemWalk).
+        using Wk = ItemWalk<NR, nz, nz + nx>;
+        static_assert(Wk::valid(), "item walk over the dynamics rows of [C0; Fp; Kp]");
+        int idx = Wk::seek(lane, cnt);
+#pragma unroll 1
+        while (__builtin_amdgcn_ballot_w64(idx < cnt) != 0) {
+            double cf_[2][npa], y_[2][NC];
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const bool ok = idx < cnt;
+                const int k = ok ? idx / NR : N - 1, c = ok ? idx - k * NR - nz : 0;
+                const double* cp = Pg + (long)k * SR + S::O_FP + c * npa;
+                const double* yp = yn + ((long)k * MNU + c) * NC;
+                const double f = (ok && k < N - 1) ? 1.0 : 0.0;   // (no dynamics rows at the last node)
+#pragma unroll
+                for (int j = 0; j < np; j++) cf_[u][j] = f * cp[j];
+#pragma unroll
+                for (int q = 0; q < NC; q++) y_[u][q] = yp[q];
+                idx = ok ? Wk::seek(idx + 64, cnt) : idx;
+            }
+#pragma unroll
+            for (int u = 0; u < 2; u++)
+#pragma unroll
+                for (int p1 = 0; p1 < np; p1++)
+#pragma unroll
+                    for (int q = 0; q < NC; q++) acc[p1 * NC + q] += cf_[u][p1] * y_[u][q];
+        }
+    } else {
+    const double* gC0 = W + wo.C0;
 #pragma unroll 1
     for (int base = 0; base < cnt; base += 128) {
         double cf_[2][npa], y_[2][NC];
@@ -917,6 +969,7 @@ __device__ __forceinline__ void Ipm2<M>::arrow_dot(const double* yz, const doubl
             for (int p1 = 0; p1 < np; p1++)
 #pragma unroll
                 for (int q = 0; q < NC; q++) acc[p1 * NC + q] += cf_[u][p1] * y_[u][q];
+    }
     }
     for (int which = 0; which < 2; which++) {
         const int k = which == 0 ? 0 : N - 1, nb = which == 0 ? nic : ntc;
@@ -994,7 +1047,7 @@ __device__ __forceinline__ void Ipm2<M>::newton_solve(double* w, double* rtil, d
 #pragma unroll
     for (int j = 0; j < npa; j++) dp[j] = 0.0;
     if (np > 0) {
-        const double* gC0 = W + wo.C0; const double* gYcz = W + wo.Ycz; const double* gYcnu = W + wo.Ycnu;
+        const double* gYcz = W + wo.Ycz; const double* gYcnu = W + wo.Ycnu;
         (void)gYcz; (void)gYcnu;
         {
             double acc1[npa];
@@ -1117,9 +1170,11 @@ __device__ __forceinline__ void Ipm2<M>::finish_direction(double* w, double* rti
                    __device__ __forceinline__ void store() const { for (int q = 0; q < 4; q++) { g[q] = vg[q]; d[q] = vd[q]; } } };
         flat_items(N * nsoc, [&](int idx) {
             const int k = idx / NSOC1, c = idx - k * NSOC1;
-            const double* Wi = socW + (long)idx * 36 + 16;
+            const double* Wi = socW + (long)idx * SOCR + SW_WI;
             R out_;
-            double u[4], t1[4];
+            double u[4], t1[4], wi[10];
+#pragma unroll
+            for (int q = 0; q < 10; q++) wi[q] = Wi[q];
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const int row = ns + nl + 4 * c + q;
@@ -1128,9 +1183,19 @@ __device__ __forceinline__ void Ipm2<M>::finish_direction(double* w, double* rti
                 u[q] = -acc + ROW(rtil, k, S::R_SOC + 4 * c + q);
             }
 #pragma unroll
-            for (int q = 0; q < 4; q++) { double acc = 0.0; for (int q2 = 0; q2 < 4; q2++) acc += Wi[q * 4 + q2] * u[q2]; t1[q] = acc; }
+            for (int q = 0; q < 4; q++) {
+                double acc = 0.0;
 #pragma unroll
-            for (int q = 0; q < 4; q++) { double acc = 0.0; for (int q2 = 0; q2 < 4; q2++) acc += Wi[q * 4 + q2] * t1[q2]; out_.vd[q] = acc; }
+                for (int q2 = 0; q2 < 4; q2++) acc += wi[sym(q, q2)] * u[q2];
+                t1[q] = acc;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                double acc = 0.0;
+#pragma unroll
+                for (int q2 = 0; q2 < 4; q2++) acc += wi[sym(q, q2)] * t1[q2];
+                out_.vd[q] = acc;
+            }
             out_.g = &ROW(gd, k, S::R_SOC + 4 * c); out_.d = &ROW(dl, k, S::R_SOC + 4 * c);
             return out_;
         });

@@ -24,23 +24,31 @@ __device__ __forceinline__ void Ipm2<M>::nt_update(double* s, double* lam)
 #pragma unroll
         for (int q = 1; q < 4; q++) wb[q] = (sb[q] - zb[q]) / (2 * gamma);
         const double eta = sqrt(sres / zres);
-        double* Wm = socW + (long)idx * 36;
-        double* Wi = Wm + 16;
-        double* lt = Wm + 32;
+        // packed record (Ipm2Work): entry (r, q) of W and of W^-1 equals entry (q, r) bit for bit -- wb[r] * wb[q] is the same product in
+        // either order, every other entry is a copy of wb -- so only q <= r is computed and stored
+        double* Wm = socW + (long)idx * SOCR + SW_W;
+        double* Wi = socW + (long)idx * SOCR + SW_WI;
+        double* lt = socW + (long)idx * SOCR + SW_LT;
+        double wm[10];
 #pragma unroll
         for (int r = 0; r < 4; r++)
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
+            for (int q = 0; q <= r; q++) {
                 double v;
                 if (r == 0 && q == 0) v = wb[0];
-                else if (r == 0) v = wb[q];
                 else if (q == 0) v = wb[r];
                 else v = (r == q ? 1.0 : 0.0) + wb[r] * wb[q] / (1.0 + wb[0]);
-                Wm[r * 4 + q] = v * eta;
-                Wi[r * 4 + q] = ((r == 0) != (q == 0) ? -v : v) / eta;
+                wm[sym(r, q)] = v * eta;
+                Wm[sym(r, q)] = wm[sym(r, q)];
+                Wi[sym(r, q)] = ((r == 0) != (q == 0) ? -v : v) / eta;
             }
 #pragma unroll
-        for (int r = 0; r < 4; r++) { double acc = 0.0; for (int q = 0; q < 4; q++) acc += Wm[r * 4 + q] * zv[q]; lt[r] = acc; }
+        for (int r = 0; r < 4; r++) {
+            double acc = 0.0;
+#pragma unroll
+            for (int q = 0; q < 4; q++) acc += wm[sym(r, q)] * zv[q];
+            lt[r] = acc;
+        }
         if (!(sres > 0.0) || !(zres > 0.0) || !isfinite(eta)) L->fail = 1;
     }
     gsync();
@@ -51,9 +59,10 @@ __device__ __forceinline__ void Ipm2<M>::nt_identity()
 {
     double* socW = W + wo.socW;
     for (int idx = lane; idx < N * nsoc; idx += 64) {
-        double* Wm = socW + (long)idx * 36;
-        for (int q = 0; q < 16; q++) { Wm[q] = (q % 5 == 0) ? 1.0 : 0.0; Wm[16 + q] = Wm[q]; }
-        for (int q = 0; q < 4; q++) Wm[32 + q] = 0.0;
+        double* Wm = socW + (long)idx * SOCR;
+        for (int r = 0; r < 4; r++)
+            for (int q = 0; q <= r; q++) { Wm[SW_W + sym(r, q)] = (r == q) ? 1.0 : 0.0; Wm[SW_WI + sym(r, q)] = (r == q) ? 1.0 : 0.0; }
+        for (int q = 0; q < 4; q++) Wm[SW_LT + q] = 0.0;
     }
     gsync();
 }
@@ -414,20 +423,20 @@ __device__ __forceinline__ void Ipm2<M>::run()
                 });
                 for (int idx = lane; idx < ncone; idx += 64) {
                     const int b0 = cone_base(idx);
-                    const double* Wm = socW + (long)idx * 36;
-                    double dsv_[4], dlv_[4], rzv[4], Wv[36];
+                    const double* Wm = socW + (long)idx * SOCR;
+                    double dsv_[4], dlv_[4], rzv[4], Wv[SOCR];
 #pragma unroll
                     for (int q = 0; q < 4; q++) { dsv_[q] = ds[b0 + q]; dlv_[q] = dl[b0 + q]; rzv[q] = rz[b0 + q]; }
 #pragma unroll
-                    for (int q = 0; q < 36; q++) Wv[q] = Wm[q];
-                    const double* Wi = Wv + 16;
-                    const double* lt = Wv + 32;
+                    for (int q = 0; q < SOCR; q++) Wv[q] = Wm[q];
+                    const double* Wi = Wv + SW_WI;
+                    const double* lt = Wv + SW_LT;
                     double u1[4], u2[4], dsv[4];
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
                         double a1 = 0.0, a2 = 0.0;
 #pragma unroll
-                        for (int q2 = 0; q2 < 4; q2++) { a1 += Wi[q * 4 + q2] * dsv_[q2]; a2 += Wv[q * 4 + q2] * dlv_[q2]; }
+                        for (int q2 = 0; q2 < 4; q2++) { a1 += Wi[sym(q, q2)] * dsv_[q2]; a2 += Wv[SW_W + sym(q, q2)] * dlv_[q2]; }
                         u1[q] = a1; u2[q] = a2;
                     }
                     dsv[0] = sigma * mu - (lt[0] * lt[0] + lt[1] * lt[1] + lt[2] * lt[2] + lt[3] * lt[3]) -
@@ -443,7 +452,7 @@ __device__ __forceinline__ void Ipm2<M>::run()
                     for (int q = 0; q < 4; q++) {
                         double acc = 0.0;
 #pragma unroll
-                        for (int q2 = 0; q2 < 4; q2++) acc += Wv[q * 4 + q2] * uu[q2];
+                        for (int q2 = 0; q2 < 4; q2++) acc += Wv[SW_W + sym(q, q2)] * uu[q2];
                         rtil[b0 + q] = rzv[q] + acc;
                     }
                 }
@@ -476,19 +485,24 @@ __device__ __forceinline__ void Ipm2<M>::run()
                     }
                     for (int idx = lane; idx < ncone; idx += 64) {
                         const int b0 = cone_base(idx);
-                        const double* Wm = socW + (long)idx * 36;
-                        double dlv_[4], t1[4], Wv[16];
+                        const double* Wm = socW + (long)idx * SOCR + SW_W;
+                        double dlv_[4], t1[4], Wv[10];
 #pragma unroll
-                        for (int q = 0; q < 16; q++) Wv[q] = Wm[q];
+                        for (int q = 0; q < 10; q++) Wv[q] = Wm[q];
 #pragma unroll
                         for (int q = 0; q < 4; q++) dlv_[q] = dl[b0 + q];
 #pragma unroll
-                        for (int q = 0; q < 4; q++) { double acc = 0.0; for (int q2 = 0; q2 < 4; q2++) acc += Wv[q * 4 + q2] * dlv_[q2]; t1[q] = acc; }
+                        for (int q = 0; q < 4; q++) {
+                            double acc = 0.0;
+#pragma unroll
+                            for (int q2 = 0; q2 < 4; q2++) acc += Wv[sym(q, q2)] * dlv_[q2];
+                            t1[q] = acc;
+                        }
 #pragma unroll
                         for (int rr = 0; rr < 4; rr++) {
                             double acc = 0.0;
 #pragma unroll
-                            for (int q = 0; q < 4; q++) acc += Wv[rr * 4 + q] * t1[q];
+                            for (int q = 0; q < 4; q++) acc += Wv[sym(rr, q)] * t1[q];
                             const double r_ = rtil[b0 + rr] + gd[b0 + rr] - acc;
                             r2[b0 + rr] = r_; n2 += r_ * r_;
                         }
