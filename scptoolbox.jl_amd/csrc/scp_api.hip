@@ -1,5 +1,5 @@
 // C-ABI implementation (include/scp_mi355x.h) of the MI355X-native SCP inner loop: model queries, the handle's life cycle and
-// services (scp_handle.hpp), discretize! and propagate (K1), the handle-level continuous-time audit.
+// services (scp_handle.hpp), discretize! and propagate (K1).  The handle-level audit entry points stand in audit_entry.hip.
 // gfx950 only: no CUDA shims, no dual paths.
 #include <algorithm>
 #include <cmath>
@@ -9,10 +9,6 @@
 #include <vector>
 
 #include "scp_handle.hpp"
-#include "audit_kernel.hpp"
-#include "lqr_kernel.hpp"
-#include "cov_kernel.hpp"
-#include "mc_kernel.hpp"
 #include "discretize_kernel.hpp"
 
 using namespace scp;
@@ -313,27 +309,13 @@ extern "C" int scp_problem_set_model_par(scp_handle h, const double* model_par)
     return SCP_OK;
 }
 
-// every device buffer of h->lqr
-static std::vector<void*> lqr_buffers(scp_problem* h)
-{
-    scp_problem::Lqr& q = h->lqr;
-    return {q.dyn.A, q.dyn.Bm, q.dyn.Bp, q.dyn.F, q.dyn.r, q.dyn.E, q.dyn.defect, q.feas, q.K, q.Kin, q.info, q.w};
-}
-
 extern "C" int scp_problem_destroy(scp_handle h)
 {
     if (!h) return SCP_ERR_BAD_ARGUMENT;
     (void)hipSetDevice(h->device);
     if (h->guess.sg) starship_guess_free(h->guess.sg);
     for (void* p : h->allocs) (void)hipFree(p);
-    for (double* p : {h->audit.flights, h->audit.dx0, h->audit.ugain, h->audit.ubias})
-        if (p) (void)hipFree(p);
-    for (void* p : lqr_buffers(h))
-        if (p) (void)hipFree(p);
-    for (double* p : {h->cov.rows, h->cov.Hf, h->cov.rec, h->cov.sig, h->cov.nodes, h->cov.w})
-        if (p) (void)hipFree(p);
-    for (double* p : {h->mc.part, h->mc.moments, h->mc.stat, h->mc.w})
-        if (p) (void)hipFree(p);
+    audit_release(h);
     for (auto& st : h->timing.stamps_free) { (void)hipEventDestroy(st.a); (void)hipEventDestroy(st.b); }
     for (auto& st : h->timing.stamps_pending) { (void)hipEventDestroy(st.a); (void)hipEventDestroy(st.b); }
     if (h->timing.ev0) (void)hipEventDestroy(h->timing.ev0);
@@ -576,560 +558,4 @@ extern "C" int scp_propagate_batch_host(scp_handle h, int B, const double* xd, c
     if (rc != SCP_OK) return rc;
     HIP_TRY(h, e);
     return SCP_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// continuous-time audit (audit_kernel.hpp; the kernels live in audit_api.hip)
-// ------------------------------------------------------------------------------------------
-
-// what every audit entry point refuses, and the O(B) buffers of the call; the interval audit flies IMPULSE handles too
-static int audit_begin(scp_problem* h, int res, const double* audit, bool foh_only = true)
-{
-    if (!h) return SCP_ERR_BAD_ARGUMENT;
-    if (foh_only && h->method != SCP_FOH) { h->err = "audit: FOH handles only (an IMPULSE solution has no continuous input to fly)"; return SCP_ERR_UNSUPPORTED; }
-    if (h->info.np_node > 0) {
-        h->err = "audit: models with node parameters are not supported (a row of X at node k reads that node's own slack; between the nodes there is none)";
-        return SCP_ERR_UNSUPPORTED;
-    }
-    if (res < 2 || !audit) { h->err = "audit: res >= 2 and an output array are required"; return SCP_ERR_BAD_ARGUMENT; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->audit.rec) TRY(dalloc(h, &h->audit.rec, (size_t)SCP_AUDIT_WIDTH * h->cap));
-    if (!h->audit.mask) TRY(dalloc(h, &h->audit.mask, (size_t)h->cap));
-    if (!h->audit.pp) TRY(dalloc(h, &h->audit.pp, (size_t)(h->info.npp > 0 ? h->info.npp : 1) * h->cap));
-    return SCP_OK;
-}
-
-// the kernel between the handle's two events, the records to the host, the device time
-static int audit_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, int res, double viol_tol,
-                     double* audit, double* seconds)
-{
-    AuditArgs a;
-    a.B = B; a.N = h->N; a.res = res; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p; a.pp = d_pp; a.Sx = h->d_Sx;
-    a.mask = mask; a.audit = h->audit.rec;
-    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
-    const int rc = audit_launch(h->model_id, h->par.data(), a, h->stream);
-    if (rc != SCP_OK) { h->err = "audit: kernel launch failed"; return rc; }
-    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(audit, h->audit.rec, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    stamps_collect(h);
-    return elapsed_out(h, seconds);
-}
-
-// the host variants' input: trajectories into the solution buffers, pp into the audit's own buffer (the run's pp is left alone)
-static int audit_stage_host(scp_problem* h, int B, const double* xd, const double* ud, const double* p, const double* pp)
-{
-    if (B < 1 || !xd || !ud || (h->npt > 0 && !p) || (h->info.npp > 0 && !pp)) { h->err = "audit: missing input"; return SCP_ERR_BAD_ARGUMENT; }
-    if (B > h->cap) { h->err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
-    TRY(upload_traj(h, B, xd, ud, p, h->traj.sol_xd, h->traj.sol_ud, h->traj.sol_p));
-    if (h->info.npp > 0)
-        HIP_TRY(h, hipMemcpyAsync(h->audit.pp, pp, sizeof(double) * h->info.npp * (size_t)B, hipMemcpyHostToDevice, h->stream));
-    return SCP_OK;
-}
-
-extern "C" int scp_audit_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
-                                    int res, double viol_tol, double* audit, double* seconds)
-{
-    TRY(audit_begin(h, res, audit));
-    TRY(audit_stage_host(h, B, xd, ud, p, pp));
-    return audit_run(h, B, traj_sol(h), h->audit.pp, nullptr, res, viol_tol, audit, seconds);
-}
-
-// the batch a resident audit flies: what the owning run's get_host returns (structured PTR: the last solution; the generic loops:
-// the reference until the first iteration), that run's pp, and in h->audit.mask its solved instances
-struct AuditSource { int B; Traj tr; const double* d_pp; };
-static int audit_resident_source(scp_problem* h, const char* no_run, AuditSource* src)
-{
-    const scp_sub* s = h->run.sub;
-    if (h->run.kind == RUN_NONE || (h->run.kind != RUN_PTR && !s)) { h->err = no_run; return SCP_ERR_BAD_ARGUMENT; }
-    const SubRun r = h->run.kind == RUN_PTR ? SubRun{h->ptr.B, true, h->ptr.d_pp, h->ptr.scp_status} : sub_run(s);
-    src->B = r.B;
-    src->tr = r.iterated ? traj_sol(h) : traj_ref(h);
-    src->d_pp = r.d_pp;
-    if (audit_mask_from_status(r.status, h->audit.mask, src->B, h->stream) != SCP_OK) {
-        h->err = "audit: kernel launch failed";
-        return SCP_ERR_HIP;
-    }
-    return SCP_OK;
-}
-
-extern "C" int scp_audit_resident(scp_handle h, int res, double viol_tol, double* audit, double* seconds)
-{
-    TRY(audit_begin(h, res, audit));
-    AuditSource src;
-    TRY(audit_resident_source(h, "scp_audit_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
-    return audit_run(h, src.B, src.tr, src.d_pp, h->audit.mask, res, viol_tol, audit, seconds);
-}
-
-// interval-parallel audit: the flight kernel and the ordered fold between the handle's two events, then the copies
-static int audit_intervals_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, int res, double viol_tol,
-                               double* audit, double* intervals, double* seconds)
-{
-    const size_t nrec = (size_t)SCP_AUDIT_INTERVAL_WIDTH * (h->N - 1);
-    if (!h->audit.intervals) TRY(dalloc(h, &h->audit.intervals, nrec * h->cap));
-    AuditIntervalArgs a;
-    a.B = B; a.N = h->N; a.sub = audit_interval_sub(h->N, res); a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
-    a.pp = d_pp; a.Sx = h->d_Sx; a.mask = mask; a.intervals = h->audit.intervals; a.audit = h->audit.rec;
-    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
-    const int rc = audit_intervals_launch(h->model_id, h->par.data(), (int)h->method, a, h->stream);
-    if (rc != SCP_OK) {
-        h->err = rc == SCP_ERR_HIP ? "audit: kernel launch failed" : "audit: IMPULSE handle of a model without an impulsive-input form";
-        return rc;
-    }
-    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(audit, h->audit.rec, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    if (intervals)
-        HIP_TRY(h, hipMemcpyAsync(intervals, h->audit.intervals, sizeof(double) * nrec * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    stamps_collect(h);
-    return elapsed_out(h, seconds);
-}
-
-extern "C" int scp_audit_intervals_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p,
-                                              const double* pp, int res, double viol_tol, double* audit, double* intervals,
-                                              double* seconds)
-{
-    TRY(audit_begin(h, res, audit, false));
-    TRY(audit_stage_host(h, B, xd, ud, p, pp));
-    return audit_intervals_run(h, B, traj_sol(h), h->audit.pp, nullptr, res, viol_tol, audit, intervals, seconds);
-}
-
-extern "C" int scp_audit_intervals_resident(scp_handle h, int res, double viol_tol, double* audit, double* intervals, double* seconds)
-{
-    TRY(audit_begin(h, res, audit, false));
-    AuditSource src;
-    TRY(audit_resident_source(h, "scp_audit_intervals_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
-    return audit_intervals_run(h, src.B, src.tr, src.d_pp, h->audit.mask, res, viol_tol, audit, intervals, seconds);
-}
-
-// dispersed-flight audit: D off-nominal flights per problem and their ordered fold (audit_kernel.hpp)
-static int audit_dispersed_begin(scp_problem* h, int res, int D, unsigned flags, const double* summary)
-{
-    TRY(audit_begin(h, res, summary));
-    if (D < 1 || (flags & ~SCP_DISP_SHARED) != 0u) { h->err = "audit: D >= 1 and no flag bit but SCP_DISP_SHARED are required"; return SCP_ERR_BAD_ARGUMENT; }
-    return SCP_OK;
-}
-
-// the flight records and the staged dispersions for D flights of every problem the handle can hold
-static int audit_dispersed_reserve(scp_problem* h, int D)
-{
-    scp_problem::Audit& A = h->audit;
-    if (D <= A.disp_D) return SCP_OK;
-    for (double** p : {&A.flights, &A.dx0, &A.ugain, &A.ubias}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    A.disp_D = 0;
-    const size_t n = (size_t)D * (size_t)h->cap * sizeof(double);
-    if (hipMalloc((void**)&A.flights, SCP_AUDIT_WIDTH * n) != hipSuccess || hipMalloc((void**)&A.dx0, (size_t)h->info.nx * n) != hipSuccess ||
-        hipMalloc((void**)&A.ugain, (size_t)h->info.nu * n) != hipSuccess || hipMalloc((void**)&A.ubias, (size_t)h->info.nu * n) != hipSuccess) {
-        (void)hipGetLastError();
-        for (double** p : {&A.flights, &A.dx0, &A.ugain, &A.ubias}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        h->err = "audit: the buffers of " + std::to_string(D) + " flights per problem could not be allocated";
-        return SCP_ERR_ALLOC;
-    }
-    A.disp_D = D;
-    return SCP_OK;
-}
-
-// The run of a D-flight audit (dispersed, tracking): the dispersions to the device, `launch` -- the two kernels of the audit, given
-// the staged arrays (nullptr where the caller passed none) and the shared flag -- between the handle's two events, then the copies.
-template <class Launch>
-static int audit_flights_run(scp_problem* h, int B, int D, const double* dx0, const double* ugain, const double* ubias, unsigned flags,
-                             double* summary, double* flights, double* seconds, Launch&& launch)
-{
-    TRY(audit_dispersed_reserve(h, D));
-    const bool shared = (flags & SCP_DISP_SHARED) != 0u;
-    const size_t cols = shared ? (size_t)D : (size_t)D * (size_t)B;
-    if (dx0) HIP_TRY(h, hipMemcpyAsync(h->audit.dx0, dx0, sizeof(double) * h->info.nx * cols, hipMemcpyHostToDevice, h->stream));
-    if (ugain) HIP_TRY(h, hipMemcpyAsync(h->audit.ugain, ugain, sizeof(double) * h->info.nu * cols, hipMemcpyHostToDevice, h->stream));
-    if (ubias) HIP_TRY(h, hipMemcpyAsync(h->audit.ubias, ubias, sizeof(double) * h->info.nu * cols, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
-    const int rc = launch(shared ? 1 : 0, dx0 ? h->audit.dx0 : nullptr, ugain ? h->audit.ugain : nullptr, ubias ? h->audit.ubias : nullptr);
-    if (rc != SCP_OK) { h->err = "audit: kernel launch failed"; return rc; }
-    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(summary, h->audit.rec, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    if (flights)
-        HIP_TRY(h, hipMemcpyAsync(flights, h->audit.flights, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)D * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    stamps_collect(h);
-    return elapsed_out(h, seconds);
-}
-
-static int audit_dispersed_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, int res, double viol_tol,
-                               int D, const double* dx0, const double* ugain, const double* ubias, unsigned flags,
-                               const double* par_true, double* summary, double* flights, double* seconds)
-{
-    return audit_flights_run(h, B, D, dx0, ugain, ubias, flags, summary, flights, seconds,
-                             [&](int shared, const double* d_dx0, const double* d_ugain, const double* d_ubias) {
-        AuditDispersedArgs a;
-        a.B = B; a.N = h->N; a.res = res; a.D = D; a.shared = shared; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
-        a.pp = d_pp; a.Sx = h->d_Sx; a.dx0 = d_dx0; a.ugain = d_ugain; a.ubias = d_ubias; a.mask = mask; a.flights = h->audit.flights;
-        a.audit = h->audit.rec;
-        // the truth model: the blob the flights are flown with; like the handle's own it is taken as given
-        return audit_dispersed_launch(h->model_id, par_true ? par_true : h->par.data(), a, h->stream);
-    });
-}
-
-extern "C" int scp_audit_dispersed_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
-                                              int res, double viol_tol, int D, const double* dx0, const double* ugain,
-                                              const double* ubias, unsigned flags, const double* par_true, double* summary,
-                                              double* flights, double* seconds)
-{
-    TRY(audit_dispersed_begin(h, res, D, flags, summary));
-    TRY(audit_stage_host(h, B, xd, ud, p, pp));
-    return audit_dispersed_run(h, B, traj_sol(h), h->audit.pp, nullptr, res, viol_tol, D, dx0, ugain, ubias, flags, par_true, summary,
-                               flights, seconds);
-}
-
-extern "C" int scp_audit_dispersed_resident(scp_handle h, int res, double viol_tol, int D, const double* dx0, const double* ugain,
-                                            const double* ubias, unsigned flags, const double* par_true, double* summary,
-                                            double* flights, double* seconds)
-{
-    TRY(audit_dispersed_begin(h, res, D, flags, summary));
-    AuditSource src;
-    TRY(audit_resident_source(h, "scp_audit_dispersed_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
-    return audit_dispersed_run(h, src.B, src.tr, src.d_pp, h->audit.mask, res, viol_tol, D, dx0, ugain, ubias, flags, par_true, summary,
-                               flights, seconds);
-}
-
-// ------------------------------------------------------------------------------------------
-// LQR gains on the discretisation (lqr_kernel.hpp; the kernels live in lqr_api.hip) and the closed-loop tracking audit
-// ------------------------------------------------------------------------------------------
-
-// the buffers of h->lqr but Kin for every problem the handle can hold: all or none
-static int lqr_reserve(scp_problem* h)
-{
-    scp_problem::Lqr& q = h->lqr;
-    if (q.K) return SCP_OK;
-    const size_t nx = h->info.nx, nu = h->info.nu, npF = h->info.npF > 0 ? h->info.npF : 1, M = h->N - 1, cap = h->cap, D = sizeof(double);
-    const bool ok = hipMalloc((void**)&q.dyn.A, nx * nx * M * cap * D) == hipSuccess && hipMalloc((void**)&q.dyn.Bm, nx * nu * M * cap * D) == hipSuccess &&
-                    hipMalloc((void**)&q.dyn.Bp, nx * nu * M * cap * D) == hipSuccess && hipMalloc((void**)&q.dyn.F, nx * npF * M * cap * D) == hipSuccess &&
-                    hipMalloc((void**)&q.dyn.r, nx * M * cap * D) == hipSuccess && hipMalloc((void**)&q.dyn.E, nx * nx * M * cap * D) == hipSuccess &&
-                    hipMalloc((void**)&q.dyn.defect, nx * M * cap * D) == hipSuccess && hipMalloc((void**)&q.feas, cap * sizeof(int)) == hipSuccess &&
-                    hipMalloc((void**)&q.info, SCP_LQR_INFO_WIDTH * cap * D) == hipSuccess &&
-                    hipMalloc((void**)&q.w, (2 * nx + nu) * D) == hipSuccess && hipMalloc((void**)&q.K, nu * nx * M * cap * D) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        for (void** p : {(void**)&q.dyn.A, (void**)&q.dyn.Bm, (void**)&q.dyn.Bp, (void**)&q.dyn.F, (void**)&q.dyn.r, (void**)&q.dyn.E,
-                         (void**)&q.dyn.defect, (void**)&q.feas, (void**)&q.info, (void**)&q.w, (void**)&q.K}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        h->err = "lqr: the discretisation and gain buffers could not be allocated";
-        return SCP_ERR_ALLOC;
-    }
-    return SCP_OK;
-}
-
-// what both gains entry points refuse (the audit's refusals, and the weights)
-static int lqr_begin(scp_problem* h, const double* qx, const double* ru, const double* qf, const double* info)
-{
-    TRY(audit_begin(h, 2, info));
-    if (!lqr_weights_ok(h->info.nx, h->info.nu, qx, ru, qf)) {
-        h->err = "lqr: qx >= 0, qf >= 0 and ru > 0, all finite, are required";
-        return SCP_ERR_BAD_ARGUMENT;
-    }
-    return lqr_reserve(h);
-}
-
-// discretize! about `tr` into the buffers of h->lqr and the Riccati kernel between the handle's two events, then the copies
-static int lqr_run(scp_problem* h, int B, const Traj& tr, const int* mask, const double* qx, const double* ru, const double* qf,
-                   double* K, double* info, double* seconds)
-{
-    scp_problem::Lqr& q = h->lqr;
-    const size_t nx = h->info.nx, nu = h->info.nu;
-    q.B = 0;
-    std::vector<double> w(2 * nx + nu);
-    std::copy(qx, qx + nx, w.begin()); std::copy(ru, ru + nu, w.begin() + nx); std::copy(qf, qf + nx, w.begin() + nx + nu);
-    HIP_TRY(h, hipMemcpyAsync(q.w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
-    TRY(discretize_dev(h, B, tr.xd, tr.ud, tr.p, q.dyn, q.feas, mask));
-    LqrArgs a;
-    a.B = B; a.N = h->N; a.A = q.dyn.A; a.Bm = q.dyn.Bm; a.Bp = q.dyn.Bp; a.qx = q.w; a.ru = q.w + nx; a.qf = q.w + nx + nu; a.mask = mask;
-    a.K = q.K; a.info = q.info;
-    const int rc = lqr_launch((int)nx, (int)nu, a, h->stream);
-    if (rc != SCP_OK) { h->err = "lqr: kernel launch failed"; return rc; }
-    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(info, q.info, sizeof(double) * SCP_LQR_INFO_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    if (K) HIP_TRY(h, hipMemcpyAsync(K, q.K, sizeof(double) * nu * nx * (size_t)(h->N - 1) * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));      // w is on this stack frame
-    stamps_collect(h);
-    q.B = B;
-    return elapsed_out(h, seconds);
-}
-
-extern "C" int scp_lqr_gains_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* qx,
-                                        const double* ru, const double* qf, double* K, double* info, double* seconds)
-{
-    TRY(lqr_begin(h, qx, ru, qf, info));
-    if (B < 1 || !xd || !ud || (h->npt > 0 && !p)) { h->err = "lqr: missing input"; return SCP_ERR_BAD_ARGUMENT; }
-    if (B > h->cap) { h->err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
-    TRY(upload_traj(h, B, xd, ud, p, h->traj.sol_xd, h->traj.sol_ud, h->traj.sol_p));
-    return lqr_run(h, B, traj_sol(h), nullptr, qx, ru, qf, K, info, seconds);
-}
-
-extern "C" int scp_lqr_gains_resident(scp_handle h, const double* qx, const double* ru, const double* qf, double* K, double* info,
-                                      double* seconds)
-{
-    TRY(lqr_begin(h, qx, ru, qf, info));
-    AuditSource src;
-    TRY(audit_resident_source(h, "scp_lqr_gains_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
-    return lqr_run(h, src.B, src.tr, h->audit.mask, qx, ru, qf, K, info, seconds);
-}
-
-static int audit_tracking_begin(scp_problem* h, int steps, int D, unsigned flags, const double* summary)
-{
-    TRY(audit_dispersed_begin(h, 2, D, flags, summary));
-    if (steps < 1) { h->err = "audit: steps >= 1 is required"; return SCP_ERR_BAD_ARGUMENT; }
-    return SCP_OK;
-}
-
-// the gains of the call on the device: the caller's, staged, or the resident ones when they were made for this B
-static int audit_tracking_gains(scp_problem* h, int B, const double* K, const double** d_K)
-{
-    if (K) {
-        if (!h->lqr.Kin && hipMalloc((void**)&h->lqr.Kin, sizeof(double) * h->info.nu * h->info.nx * (size_t)(h->N - 1) * (size_t)h->cap) != hipSuccess) {
-            (void)hipGetLastError();
-            h->lqr.Kin = nullptr;
-            h->err = "audit: the buffer of the gains passed by the caller could not be allocated";
-            return SCP_ERR_ALLOC;
-        }
-        HIP_TRY(h, hipMemcpyAsync(h->lqr.Kin, K, sizeof(double) * h->info.nu * h->info.nx * (size_t)(h->N - 1) * (size_t)B, hipMemcpyHostToDevice, h->stream));
-        *d_K = h->lqr.Kin;
-        return SCP_OK;
-    }
-    if (h->lqr.B == 0) { h->err = "audit: K is NULL and the handle holds no gains; call scp_lqr_gains_batch_host or scp_lqr_gains_resident first"; return SCP_ERR_BAD_ARGUMENT; }
-    if (h->lqr.B != B) {
-        h->err = "audit: K is NULL and the resident gains were made for B = " + std::to_string(h->lqr.B) + ", not " + std::to_string(B);
-        return SCP_ERR_BAD_ARGUMENT;
-    }
-    *d_K = h->lqr.K;
-    return SCP_OK;
-}
-
-static int audit_tracking_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, const double* K, int steps,
-                              double viol_tol, int D, const double* dx0, const double* ugain, const double* ubias, unsigned flags,
-                              const double* par_true, double* summary, double* flights, double* seconds)
-{
-    const double* d_K = nullptr;
-    TRY(audit_tracking_gains(h, B, K, &d_K));
-    return audit_flights_run(h, B, D, dx0, ugain, ubias, flags, summary, flights, seconds,
-                             [&](int shared, const double* d_dx0, const double* d_ugain, const double* d_ubias) {
-        AuditTrackingArgs a;
-        a.B = B; a.N = h->N; a.steps = steps; a.D = D; a.shared = shared; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
-        a.pp = d_pp; a.Sx = h->d_Sx; a.Su = h->d_Su; a.K = d_K; a.dx0 = d_dx0; a.ugain = d_ugain; a.ubias = d_ubias; a.mask = mask;
-        a.flights = h->audit.flights; a.audit = h->audit.rec;
-        return audit_tracking_launch(h->model_id, par_true ? par_true : h->par.data(), a, h->stream);
-    });
-}
-
-extern "C" int scp_audit_tracking_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
-                                             const double* K, int steps, double viol_tol, int D, const double* dx0, const double* ugain,
-                                             const double* ubias, unsigned flags, const double* par_true, double* summary,
-                                             double* flights, double* seconds)
-{
-    TRY(audit_tracking_begin(h, steps, D, flags, summary));
-    TRY(audit_stage_host(h, B, xd, ud, p, pp));
-    return audit_tracking_run(h, B, traj_sol(h), h->audit.pp, nullptr, K, steps, viol_tol, D, dx0, ugain, ubias, flags, par_true, summary,
-                              flights, seconds);
-}
-
-extern "C" int scp_audit_tracking_resident(scp_handle h, const double* K, int steps, double viol_tol, int D, const double* dx0,
-                                           const double* ugain, const double* ubias, unsigned flags, const double* par_true,
-                                           double* summary, double* flights, double* seconds)
-{
-    TRY(audit_tracking_begin(h, steps, D, flags, summary));
-    AuditSource src;
-    TRY(audit_resident_source(h, "scp_audit_tracking_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
-    return audit_tracking_run(h, src.B, src.tr, src.d_pp, h->audit.mask, K, steps, viol_tol, D, dx0, ugain, ubias, flags, par_true, summary,
-                              flights, seconds);
-}
-
-// ------------------------------------------------------------------------------------------
-// closed-loop covariance audit (cov_kernel.hpp; the kernels live in cov_api.hip)
-// ------------------------------------------------------------------------------------------
-
-// the buffers of h->cov for every problem the handle can hold: all or none
-static int cov_reserve(scp_problem* h)
-{
-    scp_problem::Cov& c = h->cov;
-    if (c.rows) return SCP_OK;
-    const size_t nx = h->info.nx, nu = h->info.nu, nrow = (size_t)h->info.ns + h->info.nl + h->info.nsoc, ntc = h->info.ntc, N = h->N,
-                 cap = h->cap, D = sizeof(double);
-    const bool ok = hipMalloc((void**)&c.rows, std::max<size_t>((nx + 1) * nrow * N * cap, 1) * D) == hipSuccess &&
-                    hipMalloc((void**)&c.Hf, std::max<size_t>(ntc * nx * cap, 1) * D) == hipSuccess &&
-                    hipMalloc((void**)&c.rec, SCP_COV_WIDTH * cap * D) == hipSuccess && hipMalloc((void**)&c.sig, nx * N * cap * D) == hipSuccess &&
-                    hipMalloc((void**)&c.nodes, SCP_COV_NODE_WIDTH * N * cap * D) == hipSuccess && hipMalloc((void**)&c.w, (2 * nx + nu) * D) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        for (double** p : {&c.rows, &c.Hf, &c.rec, &c.sig, &c.nodes, &c.w}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        h->err = "audit: the row table and the records of the covariance audit could not be allocated";
-        return SCP_ERR_ALLOC;
-    }
-    return SCP_OK;
-}
-
-// what both covariance entry points refuse (the audit's refusals, and the dispersions), and the buffers of the call
-static int cov_begin(scp_problem* h, const double* sig0, const double* sigu, const double* sigw, double nsig, const double* summary)
-{
-    TRY(audit_begin(h, 2, summary));
-    if (!cov_sigmas_ok(h->info.nx, h->info.nu, sig0, sigu, sigw, nsig)) {
-        h->err = "audit: sig0 >= 0, sigu >= 0, sigw >= 0, all finite, and a finite nsig > 0 are required";
-        return SCP_ERR_BAD_ARGUMENT;
-    }
-    TRY(lqr_reserve(h));
-    return cov_reserve(h);
-}
-
-// discretize! about `tr` into the buffers of h->lqr, the row pre-pass and the chain between the handle's two events, then the copies
-static int cov_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, const double* K, const double* sig0,
-                   const double* sigu, const double* sigw, double nsig, double* summary, double* sig, double* nodes, double* seconds)
-{
-    scp_problem::Lqr& q = h->lqr;
-    scp_problem::Cov& c = h->cov;
-    const size_t nx = h->info.nx, nu = h->info.nu, N = h->N;
-    const double* d_K = nullptr;
-    TRY(audit_tracking_gains(h, B, K, &d_K));
-    std::vector<double> w(2 * nx + nu);
-    std::copy(sig0, sig0 + nx, w.begin()); std::copy(sigu, sigu + nu, w.begin() + nx); std::copy(sigw, sigw + nx, w.begin() + nx + nu);
-    HIP_TRY(h, hipMemcpyAsync(c.w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
-    TRY(discretize_dev(h, B, tr.xd, tr.ud, tr.p, q.dyn, q.feas, mask));
-    CovArgs a;
-    a.B = B; a.N = h->N; a.nrow[0] = h->info.ns; a.nrow[1] = h->info.nl; a.nrow[2] = h->info.nsoc; a.ntc = h->info.ntc; a.nsig = nsig;
-    a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p; a.pp = d_pp; a.A = q.dyn.A; a.Bm = q.dyn.Bm; a.Bp = q.dyn.Bp; a.K = d_K;
-    a.Sx = h->d_Sx; a.Su = h->d_Su; a.sig0 = c.w; a.sigu = c.w + nx; a.sigw = c.w + nx + nu; a.mask = mask;
-    a.rows = c.rows; a.Hf = c.Hf; a.summary = c.rec; a.sig = sig ? c.sig : nullptr; a.nodes = nodes ? c.nodes : nullptr;
-    const int rc = cov_launch(h->model_id, h->par.data(), a, h->stream);
-    if (rc != SCP_OK) { h->err = "audit: kernel launch failed"; return rc; }
-    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(summary, c.rec, sizeof(double) * SCP_COV_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    if (sig) HIP_TRY(h, hipMemcpyAsync(sig, c.sig, sizeof(double) * nx * N * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    if (nodes) HIP_TRY(h, hipMemcpyAsync(nodes, c.nodes, sizeof(double) * SCP_COV_NODE_WIDTH * N * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));      // w is on this stack frame
-    stamps_collect(h);
-    return elapsed_out(h, seconds);
-}
-
-extern "C" int scp_audit_covariance_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
-                                               const double* K, const double* sig0, const double* sigu, const double* sigw, double nsig,
-                                               double* summary, double* sig, double* nodes, double* seconds)
-{
-    TRY(cov_begin(h, sig0, sigu, sigw, nsig, summary));
-    TRY(audit_stage_host(h, B, xd, ud, p, pp));
-    return cov_run(h, B, traj_sol(h), h->audit.pp, nullptr, K, sig0, sigu, sigw, nsig, summary, sig, nodes, seconds);
-}
-
-extern "C" int scp_audit_covariance_resident(scp_handle h, const double* K, const double* sig0, const double* sigu, const double* sigw,
-                                             double nsig, double* summary, double* sig, double* nodes, double* seconds)
-{
-    TRY(cov_begin(h, sig0, sigu, sigw, nsig, summary));
-    AuditSource src;
-    TRY(audit_resident_source(h, "scp_audit_covariance_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
-    return cov_run(h, src.B, src.tr, src.d_pp, h->audit.mask, K, sig0, sigu, sigw, nsig, summary, sig, nodes, seconds);
-}
-
-// ------------------------------------------------------------------------------------------
-// Monte-Carlo audit (mc_kernel.hpp; the kernels live in mc_api.hip)
-// ------------------------------------------------------------------------------------------
-
-// the buffers of h->mc for W wavefronts per problem and every problem the handle can hold: all or none
-static int mc_reserve(scp_problem* h, int W)
-{
-    scp_problem::Mc& c = h->mc;
-    if (W <= c.W) return SCP_OK;
-    for (double** p : {&c.part, &c.moments, &c.stat, &c.w}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    c.W = 0;
-    const size_t nx = h->info.nx, nu = h->info.nu, nv = 1 + 2 * nx + nu, N = h->N, cap = h->cap, D = sizeof(double);
-    const bool ok = hipMalloc((void**)&c.part, nv * N * (size_t)W * cap * D) == hipSuccess && hipMalloc((void**)&c.moments, nv * N * cap * D) == hipSuccess &&
-                    hipMalloc((void**)&c.stat, SCP_MC_STAT_WIDTH * cap * D) == hipSuccess && hipMalloc((void**)&c.w, (2 * nx + nu) * D) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        for (double** p : {&c.part, &c.moments, &c.stat, &c.w}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        h->err = "audit: the partial sums and the records of the Monte-Carlo audit could not be allocated";
-        return SCP_ERR_ALLOC;
-    }
-    c.W = W;
-    return SCP_OK;
-}
-
-// what both Monte-Carlo entry points refuse (the tracking audit's refusals, D < 2, the dispersions, a NULL stat)
-static int mc_begin(scp_problem* h, int steps, int D, const double* sig0, const double* sigu, const double* sigw, const double* summary,
-                    const double* stat)
-{
-    TRY(audit_tracking_begin(h, steps, D, 0u, summary));
-    if (D < 2 || !stat) { h->err = "audit: D >= 2 flights and the stat array are required"; return SCP_ERR_BAD_ARGUMENT; }
-    if (!mc_sigmas_ok(h->info.nx, h->info.nu, sig0, sigu, sigw)) {
-        h->err = "audit: sig0 >= 0, sigu >= 0, sigw >= 0, all finite, are required";
-        return SCP_ERR_BAD_ARGUMENT;
-    }
-    return SCP_OK;
-}
-
-// the three kernels between the handle's two events, then the copies
-static int mc_run(scp_problem* h, int B, const Traj& tr, const double* d_pp, const int* mask, const double* K, int steps, double viol_tol,
-                  int D, uint64_t seed, const double* sig0, const double* sigu, const double* sigw, double* summary, double* stat,
-                  double* moments, double* flights, double* seconds)
-{
-    scp_problem::Mc& c = h->mc;
-    const size_t nx = h->info.nx, nu = h->info.nu, nv = 1 + 2 * nx + nu, N = h->N;
-    const int W = (D + 63) / 64;
-    const double* d_K = nullptr;
-    TRY(audit_tracking_gains(h, B, K, &d_K));
-    TRY(audit_dispersed_reserve(h, D));
-    TRY(mc_reserve(h, W));
-    std::vector<double> w(2 * nx + nu);
-    std::copy(sig0, sig0 + nx, w.begin()); std::copy(sigu, sigu + nu, w.begin() + nx); std::copy(sigw, sigw + nx, w.begin() + nx + nu);
-    HIP_TRY(h, hipMemcpyAsync(c.w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, h->stream));
-    McArgs a;
-    a.B = B; a.N = h->N; a.steps = steps; a.D = D; a.W = W; a.seed = seed; a.viol_tol = viol_tol; a.xd = tr.xd; a.ud = tr.ud; a.p = tr.p;
-    a.pp = d_pp; a.Sx = h->d_Sx; a.Su = h->d_Su; a.K = d_K; a.sig0 = c.w; a.sigu = c.w + nx; a.sigw = c.w + nx + nu; a.mask = mask;
-    a.flights = h->audit.flights; a.audit = h->audit.rec; a.part = c.part; a.moments = c.moments; a.stat = c.stat;
-    HIP_TRY(h, hipEventRecord(h->timing.ev0, h->stream));
-    const int rc = mc_launch(h->model_id, h->par.data(), a, h->stream);
-    if (rc != SCP_OK) { h->err = "audit: kernel launch failed"; return rc; }
-    HIP_TRY(h, hipEventRecord(h->timing.ev1, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(summary, h->audit.rec, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(stat, c.stat, sizeof(double) * SCP_MC_STAT_WIDTH * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    if (moments) HIP_TRY(h, hipMemcpyAsync(moments, c.moments, sizeof(double) * nv * N * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    if (flights)
-        HIP_TRY(h, hipMemcpyAsync(flights, h->audit.flights, sizeof(double) * SCP_AUDIT_WIDTH * (size_t)D * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));      // w is on this stack frame
-    stamps_collect(h);
-    return elapsed_out(h, seconds);
-}
-
-extern "C" int scp_audit_montecarlo_batch_host(scp_handle h, int B, const double* xd, const double* ud, const double* p, const double* pp,
-                                               const double* K, int steps, double viol_tol, int D, uint64_t seed, const double* sig0,
-                                               const double* sigu, const double* sigw, double* summary, double* stat, double* moments,
-                                               double* flights, double* seconds)
-{
-    TRY(mc_begin(h, steps, D, sig0, sigu, sigw, summary, stat));
-    TRY(audit_stage_host(h, B, xd, ud, p, pp));
-    return mc_run(h, B, traj_sol(h), h->audit.pp, nullptr, K, steps, viol_tol, D, seed, sig0, sigu, sigw, summary, stat, moments, flights,
-                  seconds);
-}
-
-extern "C" int scp_audit_montecarlo_resident(scp_handle h, const double* K, int steps, double viol_tol, int D, uint64_t seed,
-                                             const double* sig0, const double* sigu, const double* sigw, double* summary, double* stat,
-                                             double* moments, double* flights, double* seconds)
-{
-    TRY(mc_begin(h, steps, D, sig0, sigu, sigw, summary, stat));
-    AuditSource src;
-    TRY(audit_resident_source(h, "scp_audit_montecarlo_resident: no run owns the handle's trajectory buffers; start one with its init", &src));
-    return mc_run(h, src.B, src.tr, src.d_pp, h->audit.mask, K, steps, viol_tol, D, seed, sig0, sigu, sigw, summary, stat, moments, flights,
-                  seconds);
 }

@@ -1,7 +1,7 @@
 // The problem handle of the C-ABI library (include/scp_mi355x.h) as its translation units share it: internal, not installed.
 //
-//   scp_api.hip      model queries, handle life cycle, kernel time stamps, discretize! and propagate (K1), scp_audit_*, scp_lqr_gains_*
-//                    (the kernels of the last two live in audit_api.hip, lqr_api.hip, cov_api.hip and mc_api.hip)
+//   scp_api.hip      model queries, handle life cycle, kernel time stamps, discretize! and propagate (K1)
+//   audit_entry.hip  scp_audit_* and scp_lqr_gains_* (their kernels live in audit_api.hip, lqr_api.hip, cov_api.hip and mc_api.hip)
 //   ptr_api.hip      structured PTR path (K2-K4)
 //   guess_api.hip    initial guesses (every model's straight line, the Starship reference guess)
 //   scp_generic.hip  subproblem handles (scp_sub) and the SCvx / GuSTO / generic-PTR loops
@@ -77,7 +77,7 @@ struct scp_problem {
         int bits = 64;     // arithmetic of discretize! (scp_set_discretize_precision): 64 = reference, 32 = tolerance check
     } disc;
 
-    // ---- scp_api.hip: continuous-time audit (scp_audit_*): records [SCP_AUDIT_WIDTH cap], mask [cap], the host variant's pp
+    // ---- audit_entry.hip: continuous-time audit (scp_audit_*): records [SCP_AUDIT_WIDTH cap], mask [cap], the host variant's pp
     // [npp cap]; lazily built ----
     struct Audit {
         double *rec = nullptr, *pp = nullptr;
@@ -85,36 +85,41 @@ struct scp_problem {
         int* mask = nullptr;
         // scp_audit_dispersed_*: flight records [SCP_AUDIT_WIDTH disp_D cap] and the staged dispersions dx0 [nx disp_D cap],
         // ugain, ubias [nu disp_D cap]; built on first use and rebuilt when a call asks for more flights than disp_D.  Not in
-        // h->allocs: audit_dispersed_reserve frees what it replaces, scp_problem_destroy the last set
+        // h->allocs: flights_reserve frees what it replaces, audit_release the last set
         double *flights = nullptr, *dx0 = nullptr, *ugain = nullptr, *ubias = nullptr;
         int disp_D = 0;
     } audit;
 
-    // ---- scp_api.hip: LQR gains (scp_lqr_gains_*) and the gains a tracking audit is handed (scp_audit_tracking_*).  dyn / feas:
+    // ---- audit_entry.hip: LQR gains (scp_lqr_gains_*) and the gains a tracking audit is handed (scp_audit_tracking_*).  dyn / feas:
     // a discretisation of its own, so that no run's buffer is written; K [nu nx (N-1) cap] the resident gains, made for batch B
-    // (0 = none); Kin the same size for gains passed by the caller; info [SCP_LQR_INFO_WIDTH cap]; w = qx [nx], ru [nu], qf [nx].
-    // Built on first use (Kin by the first tracking audit that is handed gains, the rest together by the first gains call), not in
-    // h->allocs: scp_problem_destroy frees them ----
+    // (0 = none); Kin the same size for gains passed by the caller; info [SCP_LQR_INFO_WIDTH cap]; w = qx [nx], ru [nu], qf [nx],
+    // uploaded from w_host.  Built on first use (Kin by the first tracking audit that is handed gains, the rest together by the first
+    // gains call), not in h->allocs: audit_release frees them ----
     struct Lqr {
         DynBuf dyn;
         int* feas = nullptr;
         double *K = nullptr, *Kin = nullptr, *info = nullptr, *w = nullptr;
+        std::vector<double> w_host;
         int B = 0;
     } lqr;
 
-    // ---- scp_api.hip: covariance audit (scp_audit_covariance_*): the row table rows [(nx+1) nrow N cap], Hf [ntc nx cap], the
-    // records rec [SCP_COV_WIDTH cap], sig [nx N cap], nodes [SCP_COV_NODE_WIDTH N cap] and w = sig0 [nx], sigu [nu], sigw [nx].
-    // Built together on first use, not in h->allocs: scp_problem_destroy frees them.  The discretisation and the gains are h->lqr's ----
+    // ---- audit_entry.hip: covariance audit (scp_audit_covariance_*): the row table rows [(nx+1) nrow N cap], Hf [ntc nx cap], the
+    // records rec [SCP_COV_WIDTH cap], sig [nx N cap], nodes [SCP_COV_NODE_WIDTH N cap] and w = sig0 [nx], sigu [nu], sigw [nx],
+    // uploaded from w_host.  Built together on first use, not in h->allocs: audit_release frees them.  The discretisation and the
+    // gains are h->lqr's ----
     struct Cov {
         double *rows = nullptr, *Hf = nullptr, *rec = nullptr, *sig = nullptr, *nodes = nullptr, *w = nullptr;
+        std::vector<double> w_host;
     } cov;
 
-    // ---- scp_api.hip: Monte-Carlo audit (scp_audit_montecarlo_*): the wavefront partials part [NV N W cap] with NV = 1 + 2 nx + nu,
-    // the node records moments [NV N cap], stat [SCP_MC_STAT_WIDTH cap] and w = sig0 [nx], sigu [nu], sigw [nx].  Built together on
-    // first use and rebuilt when a call needs more than W wavefronts per problem, not in h->allocs: scp_problem_destroy frees them.
+    // ---- audit_entry.hip: Monte-Carlo audit (scp_audit_montecarlo_*): the wavefront partials part [NV N W cap] with NV = 1 + 2 nx + nu,
+    // the node records moments [NV N cap], stat [SCP_MC_STAT_WIDTH cap] and w = sig0 [nx], sigu [nu], sigw [nx], uploaded from
+    // w_host.  Built together on first use and rebuilt when a call needs more than W wavefronts per problem, not in h->allocs:
+    // audit_release frees them.
     // The flight records are h->audit's, the gains h->lqr's ----
     struct Mc {
         double *part = nullptr, *moments = nullptr, *stat = nullptr, *w = nullptr;
+        std::vector<double> w_host;
         int W = 0;
     } mc;
 
@@ -246,6 +251,9 @@ int upload_traj(scp_problem* h, int B, const double* xd, const double* ud, const
 int download_traj(scp_problem* h, int B, bool from_sol, double* xd, double* ud, double* p, double* defect);
 int feas_out(scp_problem* h, int B, const int* dfeas, uint8_t* feas);
 int set_active_all(scp_problem* h, int* active, int B);
+
+// ---- audit_entry.hip: every buffer of h->audit outside h->allocs and of h->lqr, h->cov and h->mc freed (scp_problem_destroy) ----
+void audit_release(scp_problem* h);
 
 // ---- guess_api.hip: traj.guess(N) of the handle's model on the device (guess_kernel.hpp); the end of h->guess.sg (scp_problem_destroy) ----
 struct GuessArgs;
