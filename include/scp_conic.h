@@ -89,13 +89,13 @@ const char *scp_conic_last_error(scp_conic_handle h);
 /* symbolic statistics: stats[0] = nnz(L), [1] = multiply-adds per numeric factorisation, [2] = KKT dimension,
  * [3] = nnz(Gt) (cone rows unioned per column), [4] = device bytes per problem, [5] / [6] = elimination levels of the
  * factorisation / of the backward substitution (barriers per sweep), [7] = worker waves per group of 64 problems,
- * [8] = nested-dissection depth of the ordering in use (0: sequential minimum degree), [9] = problems re-solved so far by
- * the sequential fallback schedule, [10] = problems solved so far, [11] = elimination levels of the fallback schedule
- * (0: none kept or switched off), [12] = problems the fallback pass left with a usable solution or a certificate,
- * [13..15] = 0 (reserved).  Ordering: SCP_CONIC_ORDER = auto (default: the cheaper of the sequential minimum-degree order and
- * the nested dissection of the chain of node blocks, priced for the batch capacity's launch geometry; a dissection keeps
- * the sequential schedule as a per-problem fallback for ITERLIM / NUMERR exits, dropped once it stops rescuing them, made
- * the primary schedule when it rescues most of a launch) | nd | seq. */
+ * [8] = nested-dissection depth of the ordering in use (0: sequential minimum degree), [9] = problems given further attempts
+ * so far, [10] = problems solved so far, [11] = 0 (there is no second schedule), [12] = problems that further attempts left
+ * with a usable solution or a certificate, [13..15] = 0 (reserved).  Ordering: SCP_CONIC_ORDER = auto (default: the cheaper of
+ * the sequential minimum-degree order and the nested dissection of the chain of node blocks, priced for the batch capacity's
+ * launch geometry) | nd | seq; that one schedule serves every launch.  Further attempts: a problem that ends ITERATION_LIMIT /
+ * NUMERICAL_ERROR is solved again on the same schedule with a larger static regularisation, r <- min(max(10 r, 1e-7), 1e-4),
+ * at most twice, until nothing is left to re-solve or everything was rescued; they depend on that problem's own exits only. */
 int scp_conic_stats(scp_conic_handle h, long long stats[16]);
 
 /*

@@ -14,9 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "../include/scp_conic.h"
-#include "../scptoolbox.jl_amd/csrc/conic_ipm.hpp"
-#include "../scptoolbox.jl_amd/csrc/conic_symbolic.hpp"
+#include "../scptoolbox.jl_amd/csrc/conic_bind.hpp"
 
 using namespace scp::conic;
 
@@ -81,14 +79,23 @@ struct ThreadCtx {
     bool any(bool v) const { const double r = sum(v ? 1.0 : 0.0); return r > 0.0; }
 };
 
-static Csc make_csc(int nrow, int ncol, const int* p, const int* i)
+static int env_int(const char* name, int unset)
 {
-    Csc M;
-    M.nrow = nrow; M.ncol = ncol;
-    if (p == nullptr) { M.p.assign(ncol + 1, 0); return M; }
-    M.p.assign(p, p + ncol + 1);
-    if (M.p[ncol] > 0) M.i.assign(i, i + M.p[ncol]);
-    return M;
+    const char* v = std::getenv(name);
+    return v ? std::atoi(v) : unset;
+}
+
+// The schedule of a pattern under CONIC_HOST_ORDER = seq (default) | nd | best.  "nd" / "best": what Engine::create does
+// (analyse_auto: the cheapest dissection; "best" may also keep the sequential order); a caller's perm goes before either.
+static Symbolic host_analyse(int n, int p, int m, int l, const std::vector<int>& q, const int* Pp, const int* Pi, const int* Ap,
+                             const int* Ai, const int* Gp, const int* Gi, const int* perm)
+{
+    const char* om = std::getenv("CONIC_HOST_ORDER");
+    const std::string order = om ? om : "seq";
+    const Csc P = make_csc(n, n, Pp, Pi), A = make_csc(p, n, Ap, Ai), G = make_csc(m, n, Gp, Gi);
+    if (perm == nullptr && (order == "nd" || order == "best"))
+        return analyse_auto(n, p, m, l, q, P, A, G, env_int("CONIC_HOST_WORKERS", 256), order == "best");
+    return analyse(n, p, m, l, q, P, A, G, perm);      // sequential minimum degree, or the caller's order
 }
 
 // Work profile of a schedule, per elimination level: [columns, row entries (pivot sums = forward substitution terms), longest
@@ -101,15 +108,7 @@ extern "C" int conic_host_schedule_profile(int n, int p, int m, int l, int ncone
 {
     Symbolic S;
     try {
-        const char* om = std::getenv("CONIC_HOST_ORDER");
-        const std::string order = om ? om : "seq";
-        const std::vector<int> qv(q, q + ncones);
-        if (order == "nd" || order == "best")
-            S = analyse_auto(n, p, m, l, qv, make_csc(n, n, Pp, Pi), make_csc(p, n, Ap, Ai), make_csc(m, n, Gp, Gi),
-                             std::getenv("CONIC_HOST_WORKERS") ? std::atoi(std::getenv("CONIC_HOST_WORKERS")) : 256, order == "best",
-                             nullptr, nullptr);
-        else
-            S = analyse(n, p, m, l, qv, make_csc(n, n, Pp, Pi), make_csc(p, n, Ap, Ai), make_csc(m, n, Gp, Gi), nullptr, false, ORDER_SEQUENTIAL);
+        S = host_analyse(n, p, m, l, std::vector<int>(q, q + ncones), Pp, Pi, Ap, Ai, Gp, Gi, nullptr);
     } catch (const std::exception&) {
         return -1;
     }
@@ -154,56 +153,17 @@ extern "C" int conic_host_solve(int n, int p, int m, int l, int ncones, const in
                                 const double* Px, unsigned shared_mask, const scp_conic_opts* opts, double* x, double* y,
                                 double* z, double* s, int32_t* status, int32_t* iters, double* info, long long* stats)
 {
+    ConeKinds K{std::vector<int>()};
     Symbolic S;
-    std::vector<int> ctype(ncones > 0 ? ncones : 1, 0), cexp(ncones > 0 ? ncones : 1, -1);
-    int nexp = 0;
     try {
-        const char* om = std::getenv("CONIC_HOST_ORDER");
-        const std::string order = om ? om : "seq";
-        std::vector<int> qv(q, q + ncones);
-        for (int c = 0; c < ncones; c++) if (qv[c] == -3) { qv[c] = 3; ctype[c] = 1; cexp[c] = nexp++; }      // exponential cones
-        // "nd" / "best": what Engine::create does (analyse_auto: the cheapest dissection; "best" may also keep the sequential order)
-        if (perm == nullptr && (order == "nd" || order == "best"))
-            S = analyse_auto(n, p, m, l, qv, make_csc(n, n, Pp, Pi), make_csc(p, n, Ap, Ai), make_csc(m, n, Gp, Gi),
-                             std::getenv("CONIC_HOST_WORKERS") ? std::atoi(std::getenv("CONIC_HOST_WORKERS")) : 256, order == "best",
-                             nullptr, nullptr);
-        else
-            S = analyse(n, p, m, l, qv, make_csc(n, n, Pp, Pi), make_csc(p, n, Ap, Ai), make_csc(m, n, Gp, Gi), perm,
-                        std::getenv("CONIC_FREE_ORDER") != nullptr, ORDER_SEQUENTIAL);
+        K = ConeKinds(std::vector<int>(q, q + ncones));
+        S = host_analyse(n, p, m, l, K.q, Pp, Pi, Ap, Ai, Gp, Gi, perm);
     } catch (const std::exception&) {
         return 1;
     }
-    const CsrView Gr = csr_view(S.G);
-    std::vector<int2_> pairs(S.pair_a.size());
-    for (size_t i = 0; i < pairs.size(); i++) { pairs[i].a = S.pair_a[i]; pairs[i].b = S.pair_b[i]; }
-    std::vector<long long> pair_p(S.pair_p.begin(), S.pair_p.end());
+    const SchedAux aux(S);
     Sched D;
-    D.n = n; D.p = p; D.m = m; D.l = l; D.nk = S.nk; D.ncone = ncones;
-    D.nnzG = S.G.nnz(); D.nnzGt = S.Gt.nnz(); D.nnzA = S.A.nnz(); D.nnzP = S.P.nnz(); D.nnzL = S.Lp[S.nk];
-    D.njob = (int)S.job_gt0.size(); D.nlp = (int)S.lp_gt.size();
-    D.q = S.q.data(); D.cone_off = S.cone_off.data(); D.ctype = ctype.data(); D.cexp = cexp.data(); D.nexp = nexp;
-    D.Gp = S.G.p.data(); D.Gi = S.G.i.data(); D.Gr_p = Gr.p.data(); D.Gr_j = Gr.j.data(); D.Gr_pos = Gr.pos.data();
-    D.Gtp = S.Gt.p.data(); D.Gti = S.Gt.i.data(); D.Gtr_p = S.Gtr.p.data(); D.Gtr_j = S.Gtr.j.data(); D.Gtr_pos = S.Gtr.pos.data();
-    D.Ap = S.A.p.data(); D.Ai = S.A.i.data(); D.Ar_p = S.Ar.p.data(); D.Ar_j = S.Ar.j.data(); D.Ar_pos = S.Ar.pos.data();
-    D.Pf_p = S.Pfull.p.data(); D.Pf_j = S.Pfull.j.data(); D.Pf_pos = S.Pfull.pos.data();
-    D.kk_p = S.kk_p.data(); D.kk_src = S.kk_src.data(); D.kk_idx = S.kk_idx.data(); D.kk_col = S.kk_col.data();
-    D.kk_long = S.kk_long.data(); D.nkk_long = (int)S.kk_long.size(); D.kk_long_thr = Symbolic::KK_LONG;
-    D.job_gt0 = S.job_gt0.data(); D.job_cone = S.job_cone.data(); D.job_src_p = S.job_src_p.data();
-    D.job_src_row = S.job_src_row.data(); D.job_src_g = S.job_src_g.data(); D.lp_gt = S.lp_gt.data(); D.lp_g = S.lp_g.data();
-    D.perm = S.perm.data();
-    D.Lp = S.Lp.data(); D.Li = S.Li.data(); D.l_src = S.l_src.data(); D.l_src_idx = S.l_src_idx.data();
-    D.d_src = S.d_src.data(); D.d_src_idx = S.d_src_idx.data(); D.d_kind = S.d_kind.data();
-    D.pair_p = pair_p.data(); D.pairs = pairs.data();
-    D.row_p = S.row_p.data(); D.row_k = S.row_k.data(); D.row_pos = S.row_pos.data();
-    D.nlev = (int)S.lev_p.size() - 1; D.nrlev = (int)S.rlev_p.size() - 1;
-    D.lev_p = S.lev_p.data(); D.lev_cols = S.lev_cols.data(); D.lev_ent_p = S.lev_ent_p.data(); D.lev_ent = S.lev_ent.data();
-    D.ent_col = S.ent_col.data(); D.rlev_p = S.rlev_p.data(); D.rlev_cols = S.rlev_cols.data();
-    std::vector<long long> eq0(S.echunk_q0.begin(), S.echunk_q0.end()), eq1(S.echunk_q1.begin(), S.echunk_q1.end());
-    D.max_chunks = S.max_chunks;
-    D.lev_nshort = S.lev_nshort.data(); D.rchunk_p = S.rchunk_p.data(); D.rchunk_r0 = S.rchunk_r0.data(); D.rchunk_r1 = S.rchunk_r1.data();
-    D.col_c0 = S.col_c0.data(); D.col_c1 = S.col_c1.data();
-    D.lev_ent_nshort = S.lev_ent_nshort.data(); D.echunk_p = S.echunk_p.data(); D.ent_c0 = S.ent_c0.data(); D.ent_c1 = S.ent_c1.data();
-    D.echunk_q0 = eq0.data(); D.echunk_q1 = eq1.data();
+    bind_schedule(S, K, aux, D, [](const auto& v) { return v.data(); });      // the solver reads the vectors where they are
     if (stats) { stats[0] = D.nnzL; stats[1] = S.flops; stats[2] = D.nk; stats[3] = D.nnzGt; stats[4] = S.nd_depth; stats[5] = D.nlev; stats[6] = D.nrlev;
         long mx = 0; for (int j = 0; j < S.nk; j++) mx = std::max<long>(mx, S.row_p[j + 1] - S.row_p[j]);
         stats[7] = mx; }
@@ -214,14 +174,7 @@ extern "C" int conic_host_solve(int n, int p, int m, int l, int ncones, const in
     }
     if (B <= 0) return 0;
 
-    Opts o = default_opts();
-    if (opts) {
-        o.max_iter = opts->max_iter; o.feastol = opts->feastol; o.abstol = opts->abstol; o.reltol = opts->reltol;
-        o.reg = opts->reg; o.dyn_eps = opts->dyn_eps; o.dyn_delta = opts->dyn_delta; o.nref = opts->nref;
-        o.ref_tol = opts->ref_tol; o.step = opts->step;
-    }
-    o.fine = 0;
-    if (!(o.reg >= 0.0)) { o.reg = auto_reg(S.n_free, S.n, S.m, S.q.empty() && S.P.i.empty(), nexp > 0); o.fine = o.reg < 1e-9; }
+    const Opts o = resolve_auto_reg(opts_from_abi(opts), S, K.nexp);
     const long BS = B;
     // inputs: [len, B] column-major -> interleaved [len][BS]
     auto interleave = [&](const double* src, long len, bool shared) {
@@ -234,11 +187,9 @@ extern "C" int conic_host_solve(int n, int p, int m, int l, int ncones, const in
     std::vector<double> ci = interleave(c, n, shared_mask & SCP_CONIC_SHARED_C), bi = interleave(b, p, shared_mask & SCP_CONIC_SHARED_B),
                         hi = interleave(hvec, m, shared_mask & SCP_CONIC_SHARED_H), Gi_ = interleave(Gx, D.nnzG, shared_mask & SCP_CONIC_SHARED_G),
                         Ai_ = interleave(Ax, D.nnzA, shared_mask & SCP_CONIC_SHARED_A), Pi_ = interleave(Px, D.nnzP, shared_mask & SCP_CONIC_SHARED_P);
-    const long nk = D.nk;
-    const long work_len = D.nnzGt + 2L * D.nnzL + nk + 5 * nk + D.max_chunks + 6L * m + ncones + 9L * nexp + n + p;
-    std::vector<double> work((size_t)work_len * BS, 0.0), xs((size_t)std::max(n, 1) * BS), ys((size_t)std::max(p, 1) * BS),
+    std::vector<double> work((size_t)work_len(D) * BS, 0.0), xs((size_t)std::max(n, 1) * BS), ys((size_t)std::max(p, 1) * BS),
         zs((size_t)std::max(m, 1) * BS), ss((size_t)std::max(m, 1) * BS);
-    const int workers = std::getenv("CONIC_HOST_WORKERS") ? std::atoi(std::getenv("CONIC_HOST_WORKERS")) : 1;
+    const int workers = env_int("CONIC_HOST_WORKERS", 1);
 #pragma omp parallel for schedule(dynamic) if (workers <= 1)
     for (int t = 0; t < B; t++) {
         Prob Q;
@@ -248,14 +199,9 @@ extern "C" int conic_host_solve(int n, int p, int m, int l, int ncones, const in
         Q.Ax = cb(Ai_, shared_mask & SCP_CONIC_SHARED_A); Q.Px = cb(Pi_, shared_mask & SCP_CONIC_SHARED_P);
         Q.x = BV{xs.data() + t, BS}; Q.y = BV{ys.data() + t, BS}; Q.z = BV{zs.data() + t, BS}; Q.s = BV{ss.data() + t, BS};
         double* w = work.data();
-        auto take = [&](long len) { BV v{w + t, BS}; w += len * BS; return v; };
-        Q.Gt = take(D.nnzGt); Q.Lx = take(D.nnzL); Q.Ux = take(D.nnzL); Q.Dinv = take(nk);
-        Q.rhs = take(nk); Q.sol = take(nk); Q.res = take(nk); Q.cor = take(nk); Q.tmp = take(nk);
-        Q.part = take(D.max_chunks);
-        Q.lam = take(m); Q.wsc = take(m); Q.ds = take(m); Q.dz = take(m); Q.corr = take(m); Q.rz = take(m);
-        Q.eta = take(ncones + 9L * nexp); Q.rx = take(n); Q.ry = take(p);
+        carve_work(D, Q, [&](long len) { BV v{w + t, BS}; w += len * BS; return v; });
         Result R;
-        const int coop = std::getenv("CONIC_HOST_COOP") ? std::atoi(std::getenv("CONIC_HOST_COOP")) : 0;
+        const int coop = env_int("CONIC_HOST_COOP", 0);
         if (workers <= 1 && coop > 1) {
             SerialCoopCtx cx; cx.vw = coop;
             Solver<SerialCoopCtx> sv(D, Q, o, cx);

@@ -48,8 +48,9 @@ def ip(a):
 
 
 def solve(c, G, h, l, q, A=None, b=None, P=None, B=None, values=None, shared_mask=0, perm=None, **optkw):
-    """CONIC_HOST_ORDER = auto emulates Engine::launch (conic_api.hip): nested-dissection schedule first, every problem it
-    does not bring to OPTIMAL / a certificate re-solved with the sequential schedule.  See _solve."""
+    """CONIC_HOST_ORDER = auto is a policy of this host binding alone, pinned by the tests that use it; it does not emulate the
+    device engine (which keeps one schedule and re-solves with a larger regularisation): nested-dissection schedule first, then
+    every problem that did not end OPTIMAL or with a certificate is solved again with the sequential schedule.  See _solve."""
     mode = os.environ.get("CONIC_HOST_ORDER", "seq")
     if mode != "auto" or perm is not None:
         return _solve(c, G, h, l, q, A, b, P, B, values, shared_mask, perm, **optkw)

@@ -98,8 +98,6 @@ struct DevCtx {
     __device__ __forceinline__ bool any(bool v) const { return __syncthreads_or(v ? 1 : 0) != 0; }
 };
 
-constexpr int CONIC_MAX_WAVES = 16;
-
 // Workgroup = (64 / SUB) problems x NW worker waves (blockDim.x = 64 NW); see conic_ipm.hpp.
 // Two register budgets: MAXW = 16 (1024 threads, 128 VGPRs) and MAXW = 8 (512 threads, 256 VGPRs: no spills).
 template <int MAXW, int SUB>
@@ -200,33 +198,6 @@ static int upload(Engine& E, const std::vector<T>& v, const T** out)
     return SCP_OK;
 }
 
-// the factorisation part of a schedule (everything that depends on the ordering)
-static int upload_factor_schedule(Engine& E, const Symbolic& S, Sched& D)
-{
-    std::vector<int2_> pairs(S.pair_a.size());
-    for (size_t i = 0; i < pairs.size(); i++) { pairs[i].a = S.pair_a[i]; pairs[i].b = S.pair_b[i]; }
-    std::vector<long long> pair_p(S.pair_p.begin(), S.pair_p.end());
-    int rc;
-#define UP(vec, field) if ((rc = upload(E, vec, &D.field)) != SCP_OK) return rc
-    D.nnzL = S.Lp[S.nk];
-    UP(S.perm, perm);
-    UP(S.Lp, Lp); UP(S.Li, Li); UP(S.l_src, l_src); UP(S.l_src_idx, l_src_idx); UP(S.d_src, d_src); UP(S.d_src_idx, d_src_idx);
-    UP(S.d_kind, d_kind);
-    UP(pair_p, pair_p); UP(pairs, pairs);
-    UP(S.row_p, row_p); UP(S.row_k, row_k); UP(S.row_pos, row_pos);
-    D.nlev = (int)S.lev_p.size() - 1; D.nrlev = (int)S.rlev_p.size() - 1;
-    UP(S.lev_p, lev_p); UP(S.lev_cols, lev_cols); UP(S.lev_ent_p, lev_ent_p); UP(S.lev_ent, lev_ent); UP(S.ent_col, ent_col);
-    UP(S.rlev_p, rlev_p); UP(S.rlev_cols, rlev_cols);
-    std::vector<long long> q0(S.echunk_q0.begin(), S.echunk_q0.end()), q1(S.echunk_q1.begin(), S.echunk_q1.end());
-    D.max_chunks = S.max_chunks;
-    UP(S.lev_nshort, lev_nshort); UP(S.rchunk_p, rchunk_p); UP(S.rchunk_r0, rchunk_r0); UP(S.rchunk_r1, rchunk_r1);
-    UP(S.col_c0, col_c0); UP(S.col_c1, col_c1);
-    UP(S.lev_ent_nshort, lev_ent_nshort); UP(S.echunk_p, echunk_p); UP(S.ent_c0, ent_c0); UP(S.ent_c1, ent_c1);
-    UP(q0, echunk_q0); UP(q1, echunk_q1);
-#undef UP
-    return SCP_OK;
-}
-
 // problems per wave = 64 / SUB by batch size
 // (round 5: one workgroup per problem up to 768 problems, 320 before -- with the cooperative item groups that geometry solves the
 //  free-flyer N = 200 program at batch 512 in 3.9 s per launch against 7.0 s with 16 sub-workers; equal at 1 024, slower at 2 048)
@@ -242,17 +213,10 @@ int Engine::create(int n, int p, int m, int l, const std::vector<int>& q_in, con
         err = "SCP_CONIC_SUB = " + std::to_string(sub_workers) + ": sub-workers per wave must be 1, 4, 16 or 64 (unset or <= 0: by batch size)";
         return SCP_ERR_BAD_ARGUMENT;
     }
-    // q[c] > 0: second-order cone of that dimension; q[c] = -3: exponential cone (include/scp_conic.h).  For the symbolic
-    // analysis an exponential cone is a dense 3-row block like a second-order cone of dimension 3.
-    std::vector<int> q(q_in), ctype(q_in.size(), 0), cexp(q_in.size(), -1);
-    int nexp = 0;
-    for (size_t c = 0; c < q.size(); c++) {
-        if (q[c] == -3) { q[c] = 3; ctype[c] = 1; cexp[c] = nexp++; }
-        else if (q[c] < 1) { err = "cone dimension < 1 (an exponential cone is q = -3)"; return SCP_ERR_BAD_ARGUMENT; }
-    }
+    const ConeKinds K(q_in);
+    for (int d : K.q) if (d < 1) { err = "cone dimension < 1 (an exponential cone is q = -3)"; return SCP_ERR_BAD_ARGUMENT; }
     const char* om = std::getenv("SCP_CONIC_ORDER");
     const std::string order = om ? om : "auto";
-    const bool free_order = std::getenv("SCP_CONIC_FREE_ORDER") != nullptr;
     try {
         // Round 2 kept pure LPs (Starship: no second-order cone, no quadratic cost) on the sequential order: their node
         // blocks P + Gt'Gt are numerically singular late in a run and the nested order then broke down in overflowing pivots
@@ -262,16 +226,11 @@ int Engine::create(int n, int p, int m, int l, const std::vector<int>& q_in, con
         // Which order: the cheaper schedule of the two by schedule_cost (conic_symbolic.hpp, analyse_auto) -- the nested order
         // only pays where the dissection finds the chain (quadrotor GuSTO N = 30, slack-free form: it did not with the first
         // threshold and the run cost 3 x the sequential schedule; measured in profiles/README.md, round 3).
-        const bool try_nd = perm == nullptr && !free_order && order != "seq";
-        if (try_nd) {
-            bool nested = false;
-            const int waves = waves_per_group < 1 ? 1 : (waves_per_group > CONIC_MAX_WAVES ? CONIC_MAX_WAVES : waves_per_group);
-            const int workers = waves * (sub_workers > 0 ? sub_workers : default_sub_workers(capacity));   // lanes per problem
-            sym = analyse_auto(n, p, m, l, q, P, A, G, workers, order != "nd", &sym_fb, &nested);
-            has_fb = nested && order != "nd";
+        if (perm == nullptr && order != "seq") {
+            const int workers = waves() * (sub_workers > 0 ? sub_workers : default_sub_workers(capacity));   // lanes per problem
+            sym = analyse_auto(n, p, m, l, K.q, P, A, G, workers, order != "nd");
         } else {
-            sym = analyse(n, p, m, l, q, P, A, G, perm, free_order, ORDER_SEQUENTIAL);
-            has_fb = false;
+            sym = analyse(n, p, m, l, K.q, P, A, G, perm);      // sequential minimum degree, or the caller's order
         }
     } catch (const std::exception& e) {
         err = e.what();
@@ -283,40 +242,16 @@ int Engine::create(int n, int p, int m, int l, const std::vector<int>& q_in, con
     device = dev;
     ENG_TRY(hipSetDevice(dev));
     cap = capacity; BS = (capacity + 63) & ~63;
-    const Symbolic& S = sym;
     Sched& D = sched;
-    D.n = n; D.p = p; D.m = m; D.l = l; D.nk = S.nk; D.ncone = (int)q.size(); D.nexp = nexp;
-    D.nnzG = G.nnz(); D.nnzGt = S.Gt.nnz(); D.nnzA = A.nnz(); D.nnzP = P.nnz();
-    D.njob = (int)S.job_gt0.size(); D.nlp = (int)S.lp_gt.size();
-    const CsrView Gr = csr_view(G);
-    int rc;
-#define UP(vec, field) if ((rc = upload(*this, vec, &D.field)) != SCP_OK) return rc
-    UP(S.q, q); UP(S.cone_off, cone_off); UP(ctype, ctype); UP(cexp, cexp);
-    UP(G.p, Gp); UP(G.i, Gi); UP(Gr.p, Gr_p); UP(Gr.j, Gr_j); UP(Gr.pos, Gr_pos);
-    UP(S.Gt.p, Gtp); UP(S.Gt.i, Gti); UP(S.Gtr.p, Gtr_p); UP(S.Gtr.j, Gtr_j); UP(S.Gtr.pos, Gtr_pos);
-    UP(A.p, Ap); UP(A.i, Ai); UP(S.Ar.p, Ar_p); UP(S.Ar.j, Ar_j); UP(S.Ar.pos, Ar_pos);
-    UP(S.Pfull.p, Pf_p); UP(S.Pfull.j, Pf_j); UP(S.Pfull.pos, Pf_pos);
-    UP(S.kk_p, kk_p); UP(S.kk_src, kk_src); UP(S.kk_idx, kk_idx); UP(S.kk_col, kk_col);
-    UP(S.kk_long, kk_long); D.nkk_long = (int)S.kk_long.size(); D.kk_long_thr = Symbolic::KK_LONG;
-    UP(S.job_gt0, job_gt0); UP(S.job_cone, job_cone); UP(S.job_src_p, job_src_p); UP(S.job_src_row, job_src_row);
-    UP(S.job_src_g, job_src_g); UP(S.lp_gt, lp_gt); UP(S.lp_g, lp_g);
-#undef UP
-    if ((rc = upload_factor_schedule(*this, S, D)) != SCP_OK) return rc;
-    long nnzL_max = D.nnzL, chunks_max = D.max_chunks;
-    if (has_fb) {     // same program, same pattern arrays; only the factorisation schedule differs
-        // the sequential schedule is built and uploaded only for the diagnostic mode that uses it (SCP_CONIC_FALLBACK=seq);
-        // the default second attempt runs on the primary schedule with a larger static regularisation (launch())
-        const char* fbm = std::getenv("SCP_CONIC_FALLBACK");
-        if (fbm && std::string(fbm) == "seq") {
-            sched_fb = D;
-            if ((rc = upload_factor_schedule(*this, sym_fb, sched_fb)) != SCP_OK) return rc;
-            nnzL_max = std::max<long>(nnzL_max, sched_fb.nnzL);
-            chunks_max = std::max<long>(chunks_max, sched_fb.max_chunks);
-        } else {
-            sym_fb = Symbolic();      // (the host copy is not needed in the default mode)
-        }
-    }
-    {   // mask / counter of the further attempts (launch()): for every schedule since round 5
+    int rc = SCP_OK;
+    // every vector of the schedule becomes a device allocation of its own (after a failure the remaining ones are skipped)
+    bind_schedule(sym, K, SchedAux(sym), D, [&](const auto& v) {
+        decltype(v.data()) d = nullptr;
+        if (rc == SCP_OK) rc = upload(*this, v, &d);
+        return d;
+    });
+    if (rc != SCP_OK) return rc;
+    {   // mask / counter of the further attempts (launch())
         void* dm = nullptr;
         if (hipMalloc(&dm, sizeof(int) * ((size_t)BS + 1)) != hipSuccess) { err = "hipMalloc (fallback mask)"; return SCP_ERR_ALLOC; }
         allocs.push_back(dm);
@@ -331,20 +266,19 @@ int Engine::create(int n, int p, int m, int l, const std::vector<int>& q_in, con
         *ptr = (double*)d;
         return SCP_OK;
     };
-    const long nnzG = D.nnzG, nnzA = D.nnzA, nnzP = D.nnzP, nnzGt = D.nnzGt, nnzL = nnzL_max, nk = D.nk, nc = D.ncone;
+    const long nnzG = D.nnzG, nnzA = D.nnzA, nnzP = D.nnzP, wlen = work_len(D);
 #define DA(ptr, len) if ((rc = dalloc(&ptr, (len))) != SCP_OK) return rc
     DA(c, (long)n * BS); DA(b, (long)p * BS); DA(h, (long)m * BS); DA(Gx, nnzG * BS); DA(Ax, nnzA * BS); DA(Px, nnzP * BS);
     DA(c_sh, n); DA(b_sh, p); DA(h_sh, m); DA(Gx_sh, nnzG); DA(Ax_sh, nnzA); DA(Px_sh, nnzP);
     DA(x, (long)n * BS); DA(y, (long)p * BS); DA(z, (long)m * BS); DA(s, (long)m * BS);
-    const long work_len = nnzGt + 2 * nnzL + nk + 5 * nk + chunks_max + 6 * (long)m + nc + 9L * nexp + n + p;
-    DA(work, work_len * BS);
+    DA(work, wlen * BS);
     DA(info, 8L * BS);
 #undef DA
     void* d = nullptr;
     if (hipMalloc(&d, sizeof(int) * 2 * BS) != hipSuccess) { err = "hipMalloc (status)"; return SCP_ERR_ALLOC; }
     allocs.push_back(d);
     status = (int*)d; iters = status + BS;
-    bytes_per_problem = 8LL * (2 * (n + p + 2L * m) + nnzG + nnzA + nnzP + work_len + 8);
+    bytes_per_problem = 8LL * (2 * (n + p + 2L * m) + nnzG + nnzA + nnzP + wlen + 8);
     return SCP_OK;
 }
 
@@ -354,7 +288,7 @@ void Engine::destroy()
     allocs.clear();
 }
 
-// mask[t] = 1 for the problems of the primary pass that must be re-solved with the sequential schedule
+// mask[t] = 1 for the problems of the pass before that get a further attempt (Engine::launch)
 __global__ void fallback_mask_kernel(const int* status, const int* active, int* mask, int* count, int B)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -362,13 +296,13 @@ __global__ void fallback_mask_kernel(const int* status, const int* active, int* 
     const bool live = active == nullptr || active[t] != 0;
     const int st = status[t];
     // only UNSAFE exits are re-solved: ALMOST_OPTIMAL is a usable solution for the SCP loops (unsafe_solution, scp.jl:965-980)
-    // and the sequential pass overwrites x / y / z / s -- re-solving it could turn a usable solution into a failure
+    // and a further attempt overwrites x / y / z / s -- re-solving it could turn a usable solution into a failure
     const int need = live && (st == ST_ITERLIM || st == ST_NUMERR) ? 1 : 0;
     mask[t] = need;
     if (need) atomicAdd(count, 1);
 }
 
-// count[0] += problems of the fallback pass that left it with a usable solution or a certificate
+// count[0] += problems of a further attempt that left it with a usable solution or a certificate
 __global__ void fallback_rescued_kernel(const int* status, const int* mask, int* count, int B)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -377,10 +311,10 @@ __global__ void fallback_rescued_kernel(const int* status, const int* mask, int*
     if (st != ST_ITERLIM && st != ST_NUMERR) atomicAdd(count, 1);
 }
 
-static int launch_one(Engine& E, const Sched& D, hipStream_t stream, int B, const Opts& oe, unsigned shared_mask, const int* active)
+static int launch_one(Engine& E, hipStream_t stream, int B, const Opts& oe, unsigned shared_mask, const int* active)
 {
-    const int BS = E.BS;
-    const int waves = E.waves_per_group < 1 ? 1 : (E.waves_per_group > CONIC_MAX_WAVES ? CONIC_MAX_WAVES : E.waves_per_group);
+    const Sched& D = E.sched;
+    const int BS = E.BS, waves = E.waves();
     ProbBase PB;
     auto il = [&](double* ptr) { return Arr{ptr, (long)BS, 1}; };
     auto sh = [&](double* ptr) { return Arr{ptr, 1, 0}; };
@@ -403,12 +337,7 @@ static int launch_one(Engine& E, const Sched& D, hipStream_t stream, int B, cons
     // N = 100 at 256 problems was bandwidth-bound on bytes it never used).  The arrays live and die inside one launch.
     const bool problem_major = sub == 64;
     double* w = E.work;
-    auto take = [&](long len) { Arr a = problem_major ? Arr{w, 1, len} : il(w); w += len * BS; return a; };
-    PB.Gt = take(D.nnzGt); PB.Lx = take(D.nnzL); PB.Ux = take(D.nnzL); PB.Dinv = take(D.nk);
-    PB.rhs = take(D.nk); PB.sol = take(D.nk); PB.res = take(D.nk); PB.cor = take(D.nk); PB.tmp = take(D.nk);
-    PB.part = take(D.max_chunks);
-    PB.lam = take(D.m); PB.wsc = take(D.m); PB.ds = take(D.m); PB.dz = take(D.m); PB.corr = take(D.m); PB.rz = take(D.m);
-    PB.eta = take(D.ncone + 9L * D.nexp); PB.rx = take(D.n); PB.ry = take(D.p);
+    carve_work(D, PB, [&](long len) { Arr a = problem_major ? Arr{w, 1, len} : il(w); w += len * BS; return a; });
     const int ppw = 64 / sub;
     const dim3 grid((B + ppw - 1) / ppw), block(64 * waves);
     int* status = E.status; int* iters = E.iters; double* info = E.info;
@@ -426,12 +355,9 @@ static int launch_one(Engine& E, const Sched& D, hipStream_t stream, int B, cons
 int Engine::launch(hipStream_t stream, int B, const Opts& o, unsigned shared_mask, const int* active)
 {
     if (B < 1 || B > cap) { err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
-    Opts oe = o;
-    oe.fine = 0;
-    if (!(oe.reg >= 0.0)) { oe.reg = auto_reg(sym.n_free, sym.n, sym.m, sym.q.empty() && sym.P.i.empty(), sched.nexp > 0); oe.fine = oe.reg < 1e-9; }
+    const Opts oe = resolve_auto_reg(o, sym, sched.nexp);
     n_launched += B;
-    if (launch_one(*this, sched, stream, B, oe, shared_mask, active) != SCP_OK) { err = "conic_ipm_kernel launch failed"; return SCP_ERR_HIP; }
-    if (!fb_mask) return SCP_OK;
+    if (launch_one(*this, stream, B, oe, shared_mask, active) != SCP_OK) { err = "conic_ipm_kernel launch failed"; return SCP_ERR_HIP; }
     // (the count of unusable exits is read back after every launch: one 4-byte copy and a stream synchronisation per conic launch --
     // the callers synchronise on the same stream right after, for the solution they asked for)
     // ---- further attempts for the problems that ended ITERATION_LIMIT / NUMERICAL_ERROR (ALMOST_OPTIMAL is usable and kept) ----
@@ -441,13 +367,11 @@ int Engine::launch(hipStream_t stream, int B, const Opts& o, unsigned shared_mas
     // solved.  Round 5: TWO further attempts, 10 x and 100 x the first one's regularisation (round 4: one, at
     // 100 x): quadrotor GuSTO instance 21 at lambda = 1.25e6 ends ITERATION_LIMIT / ALMOST_OPTIMAL with 51 dynamic regularisations
     // at 1e-8 depending on the order of the sums, OPTIMAL in 28 iterations with 2 at 1e-7 in EVERY order, and stalls at 1e-6; and
-    // for every schedule, not only the nested ones (the attempt no longer needs a second schedule).  A problem's attempts depend on
-    // ITS OWN exits only (batch independence).  SCP_CONIC_FALLBACK=seq: the sequential schedule as the one further attempt.
-    static const bool fb_seq = std::getenv("SCP_CONIC_FALLBACK") && std::string(std::getenv("SCP_CONIC_FALLBACK")) == "seq";
+    // for every schedule, not only the nested ones.  A problem's attempts depend on ITS OWN exits only (batch independence).
     // The ladder climbs from the attempt before it: r1 = max(10 reg, 1e-7), r2 = min(10 r1, 1e-4) -- with 10 x / 100 x of the
     // FIRST value both clamped to the 1e-7 floor, the 1e-10 class repeated the same solve twice and never reached 1e-6.
     double reg_prev = oe.reg;
-    for (int att = 0; att < (fb_seq ? 1 : 2); att++) {
+    for (int att = 0; att < 2; att++) {
         ENG_TRY(hipMemsetAsync(fb_count, 0, sizeof(int), stream));
         hipLaunchKernelGGL(fallback_mask_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, status, active, fb_mask, fb_count, B);
         int nfb = 0;
@@ -456,13 +380,10 @@ int Engine::launch(hipStream_t stream, int B, const Opts& o, unsigned shared_mas
         if (nfb == 0) return SCP_OK;
         if (att == 0) n_fallback += nfb;
         Opts o2 = oe;
-        if (!fb_seq) {
-            o2.reg = std::min(std::max(reg_prev * 10.0, 1e-7), 1e-4);
-            if (o2.reg <= reg_prev) return SCP_OK;      // nothing left to try (the previous attempt already ran at the cap)
-            reg_prev = o2.reg;
-        }
-        if (fb_seq && !has_fb) return SCP_OK;
-        if (launch_one(*this, fb_seq ? sched_fb : sched, stream, B, o2, shared_mask, fb_mask) != SCP_OK) { err = "conic_ipm_kernel (further attempt) launch failed"; return SCP_ERR_HIP; }
+        o2.reg = std::min(std::max(reg_prev * 10.0, 1e-7), 1e-4);
+        if (o2.reg <= reg_prev) return SCP_OK;      // nothing left to try (the previous attempt already ran at the cap)
+        reg_prev = o2.reg;
+        if (launch_one(*this, stream, B, o2, shared_mask, fb_mask) != SCP_OK) { err = "conic_ipm_kernel (further attempt) launch failed"; return SCP_ERR_HIP; }
         // what did the attempt buy?  (a problem is rescued when it now holds a usable solution or a certificate)
         ENG_TRY(hipMemsetAsync(fb_count, 0, sizeof(int), stream));
         hipLaunchKernelGGL(fallback_rescued_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, status, fb_mask, fb_count, B);
@@ -470,11 +391,16 @@ int Engine::launch(hipStream_t stream, int B, const Opts& o, unsigned shared_mas
         ENG_TRY(hipMemcpyAsync(&nres, fb_count, sizeof(int), hipMemcpyDeviceToHost, stream));
         ENG_TRY(hipStreamSynchronize(stream));
         n_rescued += nres;
-        // Only the diagnostic sequential mode still adopts the sequential schedule when that is what rescues a launch.
-        if (fb_seq && 4L * nfb > B && 2L * nres > nfb) { sched = sched_fb; sym = sym_fb; has_fb = false; }
         if (nres == nfb) return SCP_OK;
     }
     return SCP_OK;
+}
+
+void Engine::stats(long long out[16]) const
+{
+    out[0] = sched.nnzL; out[1] = sym.flops; out[2] = sched.nk; out[3] = sched.nnzGt; out[4] = bytes_per_problem;
+    out[5] = sched.nlev; out[6] = sched.nrlev; out[7] = waves_per_group; out[8] = sym.nd_depth;
+    out[9] = n_fallback; out[10] = n_launched; out[11] = 0; out[12] = n_rescued; out[13] = out[14] = out[15] = 0;
 }
 
 }  // namespace conic
@@ -492,23 +418,20 @@ struct scp_conic {
 
 extern "C" void scp_conic_default_opts(scp_conic_opts* o)
 {
-    if (!o) return;
-    const Opts d = default_opts();
-    o->max_iter = d.max_iter; o->feastol = d.feastol; o->abstol = d.abstol; o->reltol = d.reltol; o->reg = d.reg;
-    o->dyn_eps = d.dyn_eps; o->dyn_delta = d.dyn_delta; o->nref = d.nref; o->ref_tol = d.ref_tol; o->step = d.step;
+    if (o) opts_to_abi(default_opts(), o);
 }
 
 extern "C" const char* scp_conic_last_error(scp_conic_handle h) { return h ? h->err.c_str() : "null handle"; }
 
-static Csc make_csc(int nrow, int ncol, const int* p, const int* i)
+// everything a handle owns, whatever part of it exists
+static void release(scp_conic* h)
 {
-    Csc M;
-    M.nrow = nrow; M.ncol = ncol;
-    if (p == nullptr) { M.p.assign(ncol + 1, 0); return M; }
-    M.p.assign(p, p + ncol + 1);
-    const int nnz = M.p[ncol] > 0 ? M.p[ncol] : 0;
-    if (nnz > 0 && i != nullptr) M.i.assign(i, i + nnz);
-    return M;
+    h->eng.destroy();
+    if (h->stage) (void)hipFree(h->stage);
+    if (h->ev0) (void)hipEventDestroy(h->ev0);
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
 }
 
 extern "C" int scp_conic_create(int n, int p, int m, int l, int ncones, const int* q, const int* Pp, const int* Pi,
@@ -534,16 +457,7 @@ extern "C" int scp_conic_create(int n, int p, int m, int l, int ncones, const in
         h->stage_len = mx * h->eng.cap;
         if (hipMalloc((void**)&h->stage, sizeof(double) * std::max<long>(h->stage_len, 1)) != hipSuccess) rc = SCP_ERR_ALLOC;
     }
-    if (rc != SCP_OK) {
-        // creation failed: report through the return code only (the handle is not handed out)
-        h->eng.destroy();
-        if (h->stage) (void)hipFree(h->stage);
-        if (h->ev0) (void)hipEventDestroy(h->ev0);
-        if (h->ev1) (void)hipEventDestroy(h->ev1);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
-        delete h;
-        return rc;
-    }
+    if (rc != SCP_OK) { release(h); return rc; }   // report through the return code only (the handle is not handed out)
     *out = h;
     return SCP_OK;
 }
@@ -553,24 +467,14 @@ extern "C" int scp_conic_destroy(scp_conic_handle h)
     if (!h) return SCP_ERR_BAD_ARGUMENT;
     (void)hipSetDevice(h->eng.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->eng.destroy();
-    if (h->stage) (void)hipFree(h->stage);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    release(h);
     return SCP_OK;
 }
 
 extern "C" int scp_conic_stats(scp_conic_handle h, long long stats[16])
 {
     if (!h || !stats) return SCP_ERR_BAD_ARGUMENT;
-    stats[0] = h->eng.sched.nnzL; stats[1] = h->eng.sym.flops; stats[2] = h->eng.sched.nk; stats[3] = h->eng.sched.nnzGt;
-    stats[4] = h->eng.bytes_per_problem;
-    stats[5] = h->eng.sched.nlev; stats[6] = h->eng.sched.nrlev; stats[7] = h->eng.waves_per_group;
-    stats[8] = h->eng.sym.nd_depth; stats[9] = h->eng.n_fallback; stats[10] = h->eng.n_launched;
-    stats[11] = h->eng.has_fb ? h->eng.sched_fb.nlev : 0;
-    stats[12] = h->eng.n_rescued; stats[13] = stats[14] = stats[15] = 0;
+    h->eng.stats(stats);
     return SCP_OK;
 }
 
@@ -617,13 +521,8 @@ extern "C" int scp_conic_solve_batch_host(scp_conic_handle h, int B, const doubl
     if (B > E.cap) { h->err = "batch size exceeds batch_capacity"; return SCP_ERR_BATCH_TOO_LARGE; }
     CH_TRY(hipSetDevice(E.device));
     const Sched& D = E.sched;
-    Opts o = default_opts();
-    if (opts) {
-        if (opts->max_iter < 0 || opts->nref < 0) { h->err = "bad solver options"; return SCP_ERR_BAD_ARGUMENT; }
-        o.max_iter = opts->max_iter; o.feastol = opts->feastol; o.abstol = opts->abstol; o.reltol = opts->reltol;
-        o.reg = opts->reg; o.dyn_eps = opts->dyn_eps; o.dyn_delta = opts->dyn_delta; o.nref = opts->nref;
-        o.ref_tol = opts->ref_tol; o.step = opts->step;
-    }
+    if (opts && (opts->max_iter < 0 || opts->nref < 0)) { h->err = "bad solver options"; return SCP_ERR_BAD_ARGUMENT; }
+    const Opts o = opts_from_abi(opts);
     int rc;
     // every put reuses the staging buffer: stream order keeps them apart
     if ((rc = put_array(h, c, E.c, E.c_sh, D.n, B, shared_mask & SCP_CONIC_SHARED_C)) != SCP_OK) return rc;

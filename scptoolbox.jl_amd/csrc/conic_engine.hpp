@@ -8,26 +8,23 @@
 #include <string>
 #include <vector>
 
-#include "conic_ipm.hpp"
-#include "conic_symbolic.hpp"
+#include "conic_bind.hpp"
 
 namespace scp {
 namespace conic {
 
+constexpr int CONIC_MAX_WAVES = 16;
+
 struct Engine {
     Symbolic sym;
     Sched sched{};           // device pointers
-    // Ordering (conic_symbolic.hpp): the primary schedule is the NESTED-DISSECTION one when the program has the chain
-    // structure (5-10x fewer elimination levels = workgroup barriers).  Its pivots are less protected than those of the
-    // sequential order on degenerate LPs (Starship), so a second, sequential schedule is kept: every problem the primary
-    // pass does not bring to OPTIMAL (or to an infeasibility certificate) is re-solved with it in a second launch, and the
-    // engine switches to the sequential schedule for good when that happens to more than a quarter of a batch.
-    // SCP_CONIC_ORDER = seq | nd | auto (default auto).
-    Symbolic sym_fb;
-    Sched sched_fb{};
-    bool has_fb = false;
+    // Ordering (conic_symbolic.hpp): ONE schedule -- the nested dissection when the program has the chain structure and it is
+    // the cheaper one for the launch geometry (5-10x fewer elimination levels = workgroup barriers), the sequential minimum
+    // degree otherwise.  SCP_CONIC_ORDER = seq | nd | auto (default auto).  A problem that ends ITERATION_LIMIT /
+    // NUMERICAL_ERROR is solved again on the same schedule with a larger static regularisation (launch(): at most two further
+    // attempts); fb_mask marks those problems, fb_count counts them.
     int *fb_mask = nullptr, *fb_count = nullptr;
-    long long n_fallback = 0, n_launched = 0, n_rescued = 0;   // problems re-solved by the fallback pass / solved / rescued by it
+    long long n_fallback = 0, n_launched = 0, n_rescued = 0;   // problems given a further attempt / solved / rescued by one
     int cap = 0, BS = 0;     // batch capacity, interleave stride (cap rounded up to 64)
     int device = 0;
     // worker waves per group of 64 problems (1..16): tuning aid SCP_CONIC_WAVES, default 16 (a full 1024-thread workgroup)
@@ -54,6 +51,10 @@ struct Engine {
     // enqueue the solve of problems [0, B) on `stream`; shared_mask as in scp_conic.h; active: optional int[B]
     // (problems with active[t] == 0 are skipped)
     int launch(hipStream_t stream, int B, const Opts& o, unsigned shared_mask, const int* active = nullptr);
+    // worker waves of a launch: waves_per_group within what the kernel has instantiations for
+    int waves() const { return waves_per_group < 1 ? 1 : (waves_per_group > CONIC_MAX_WAVES ? CONIC_MAX_WAVES : waves_per_group); }
+    // the record of scp_conic_stats (include/scp_conic.h)
+    void stats(long long out[16]) const;
 };
 
 // [len, B] column-major (batch last) <-> interleaved [len][BS]; device pointers

@@ -304,7 +304,7 @@ enum Ordering : int { ORDER_SEQUENTIAL = 0, ORDER_NESTED = 1 };
 //   2. then variables x and equality multipliers y together by minimum degree, a y being eligible only once one of its
 //      variables has been eliminated (its pivot is then -d - a^2/D_x).
 // The fill stays within a few percent of the unconstrained ordering (eliminating ALL x before the y would make the
-// Schur complement on y dense).  free_order = true gives the plain rule.
+// Schur complement on y dense).
 // Static regularisation when the caller leaves it to the solver (opts.reg < 0).  Programs in which every variable sits in
 // a cone row or has a quadratic cost (all SCP subproblems: trust-region rows) get 1e-10: the pivots are dominated by
 // P + Gt'Gt.  (1e-8 until round 5.  On the equality block the refinement against the unregularised matrix contracts by
@@ -332,7 +332,7 @@ inline double auto_reg(int n_free, int n, int m, bool pure_lp, bool has_exp = fa
 // nd_dense_factor / seen_ranks: see analyse_auto below (a dissection whose ranks are already in seen_ranks is not analysed
 // again: the function returns early with nd_depth = -1).
 inline Symbolic analyse(int n, int p, int m, int l, const std::vector<int>& q, const Csc& P, const Csc& A, const Csc& G,
-                        const int* user_perm = nullptr, bool free_order = false, int ordering = ORDER_SEQUENTIAL,
+                        const int* user_perm = nullptr, int ordering = ORDER_SEQUENTIAL,
                         double nd_dense_factor = 4.0, std::vector<std::vector<int>>* seen_ranks = nullptr)
 {
     Symbolic S;
@@ -422,7 +422,6 @@ inline Symbolic analyse(int n, int p, int m, int l, const std::vector<int>& q, c
     }
     for (auto& v : adj) { std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); }
     if (user_perm) S.perm.assign(user_perm, user_perm + nk);
-    else if (free_order) S.perm = min_degree(nk, adj);
     else {
         std::vector<int> cls(nk);
         for (int v = 0; v < nk; v++) cls[v] = v < n ? 1 : (v < n + p ? 2 : 0);
@@ -621,17 +620,21 @@ inline double schedule_cost(const Symbolic& S, int workers)
 // block is large -- it then ties the whole horizon into one component and the dissection finds no chain, or a useless one
 // of depth 2 whose separators fill in: measured on the slack-free GuSTO program, 20 x the multiply-adds at the same
 // level count).  Trying 4, 2 and 1.25 and pricing the results costs a few symbolic analyses at create time.
-// best_is_nested: the winner is a dissection (the caller keeps the sequential schedule as its fallback).
+// allow_sequential = false: a dissection whenever one is found, whatever it costs.
+// The two unnamed trailing arguments are accepted and IGNORED.  They were the out-parameters of the retired second schedule
+// (the sequential analysis, "the winner is a dissection"); nothing is returned through them any more.  The slots stay only so
+// that the previous revision of the host twin (oracle/conic_host.cpp), which passes NULL for both, still compiles when its
+// tests are run against this header to show that a new build computes what the old one did.
 inline Symbolic analyse_auto(int n, int p, int m, int l, const std::vector<int>& q, const Csc& P, const Csc& A, const Csc& G,
-                             int workers, bool allow_sequential, Symbolic* sequential_out, bool* best_is_nested)
+                             int workers, bool allow_sequential, const void* = nullptr, const void* = nullptr)
 {
     // the candidate orders are independent analyses of the same pattern: one host thread each (create of the free-flyer N = 200
     // template: four analyses of a KKT pattern with 3e5 factor entries -- the wall time of `create` is the slowest one, not the sum)
-    auto fut_seq = std::async(std::launch::async, [&] { return analyse(n, p, m, l, q, P, A, G, nullptr, false, ORDER_SEQUENTIAL); });
+    auto fut_seq = std::async(std::launch::async, [&] { return analyse(n, p, m, l, q, P, A, G, nullptr, ORDER_SEQUENTIAL); });
     const double factors[3] = {4.0, 2.0, 1.25};
     std::future<Symbolic> fut_nd[3];
     for (int i = 0; i < 3; i++)
-        fut_nd[i] = std::async(std::launch::async, [&, i] { return analyse(n, p, m, l, q, P, A, G, nullptr, false, ORDER_NESTED, factors[i], nullptr); });
+        fut_nd[i] = std::async(std::launch::async, [&, i] { return analyse(n, p, m, l, q, P, A, G, nullptr, ORDER_NESTED, factors[i], nullptr); });
     Symbolic seq = fut_seq.get();
     Symbolic best;
     bool have = false;
@@ -641,8 +644,6 @@ inline Symbolic analyse_auto(int n, int p, int m, int l, const std::vector<int>&
         if (!have || schedule_cost(S, workers) < schedule_cost(best, workers)) { best = std::move(S); have = true; }    // (ties keep the earlier factor, as before)
     }
     const bool nested = have && (!allow_sequential || schedule_cost(best, workers) < schedule_cost(seq, workers));
-    if (best_is_nested) *best_is_nested = nested;
-    if (sequential_out) *sequential_out = seq;
     return nested ? best : seq;
 }
 

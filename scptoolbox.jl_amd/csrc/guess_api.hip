@@ -86,7 +86,7 @@ static int starship_guess_dev(scp_problem* h, int B, const double* d_pp, double*
             std::copy(o, o + 36, lti.begin() + (size_t)c * 36);
         }
         g->chunk = std::min(h->cap, 256);
-        conic::Csc Pm; Pm.nrow = g->pat.n; Pm.ncol = g->pat.n; Pm.p.assign(g->pat.n + 1, 0);
+        const conic::Csc Pm = conic::make_csc(g->pat.n, g->pat.n, nullptr, nullptr);   // no quadratic cost
         int rc = g->eng.create(g->pat.n, g->pat.p, g->pat.m, g->pat.l, g->pat.q, Pm, g->pat.A, g->pat.G, nullptr, g->chunk * SG_NCAND, h->device);
         if (rc != SCP_OK) { h->err = "starship guess: " + g->eng.err; return rc; }
         TRY(sg_upload(h, g, &g->a_kind, g->pat.a_kind)); TRY(sg_upload(h, g, &g->a_i, g->pat.a_i)); TRY(sg_upload(h, g, &g->a_j, g->pat.a_j));

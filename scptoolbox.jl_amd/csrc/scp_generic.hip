@@ -367,11 +367,7 @@ extern "C" const char* scp_sub_last_error(scp_sub_handle s) { return s ? s->err.
 extern "C" int scp_sub_stats(scp_sub_handle s, long long stats[16])
 {
     if (!s || !stats) return SCP_ERR_BAD_ARGUMENT;
-    const scp::conic::Engine& E = s->eng;
-    stats[0] = E.sched.nnzL; stats[1] = E.sym.flops; stats[2] = E.sched.nk; stats[3] = E.sched.nnzGt; stats[4] = E.bytes_per_problem;
-    stats[5] = E.sched.nlev; stats[6] = E.sched.nrlev; stats[7] = E.waves_per_group; stats[8] = E.sym.nd_depth;
-    stats[9] = E.n_fallback; stats[10] = E.n_launched; stats[11] = E.has_fb ? E.sched_fb.nlev : 0;
-    stats[12] = E.n_rescued; stats[13] = stats[14] = stats[15] = 0;
+    s->eng.stats(stats);
     return SCP_OK;
 }
 
@@ -402,17 +398,10 @@ extern "C" int scp_sub_create(scp_handle h, const scp_sub_template* T, scp_sub_h
     s->lay = scp::src_layout(h->info, h->N, T->nscal);
     s->nsrc = (int)s->lay.off[scp::SEG_COUNT];
     if (T->nsrc != s->nsrc) { s->err = "template source length does not match scp_sub_source_layout"; return fail(SCP_ERR_BAD_ARGUMENT); }
-    auto csc = [](int nrow, int ncol, const int* p, const int* i) {
-        scp::conic::Csc M;
-        M.nrow = nrow; M.ncol = ncol;
-        if (!p) { M.p.assign(ncol + 1, 0); return M; }
-        M.p.assign(p, p + ncol + 1);
-        if (M.p[ncol] > 0 && i) M.i.assign(i, i + M.p[ncol]);
-        return M;
-    };
+    using scp::conic::make_csc;
     std::vector<int> q(T->q, T->q + T->ncones);
-    int rc = s->eng.create(T->n, T->p, T->m, T->l, q, csc(T->n, T->n, T->Pp, T->Pi), csc(T->p, T->n, T->Ap, T->Ai),
-                           csc(T->m, T->n, T->Gp, T->Gi), nullptr, h->cap, h->device);
+    int rc = s->eng.create(T->n, T->p, T->m, T->l, q, make_csc(T->n, T->n, T->Pp, T->Pi), make_csc(T->p, T->n, T->Ap, T->Ai),
+                           make_csc(T->m, T->n, T->Gp, T->Gi), nullptr, h->cap, h->device);
     if (rc != SCP_OK) { s->err = s->eng.err; return fail(rc); }
     const scp::conic::Sched& D = s->eng.sched;
     const scp_affine_map* src_maps[6] = {&T->c, &T->b, &T->h, &T->Gx, &T->Ax, &T->Px};
@@ -523,17 +512,6 @@ static int sub_solve_dev(scp_sub* s, int B, const scp::conic::Opts& o, const int
     return SCP_OK;
 }
 
-static scp::conic::Opts sub_opts(const scp_conic_opts* opts)
-{
-    scp::conic::Opts o = scp::conic::default_opts();
-    if (opts) {
-        o.max_iter = opts->max_iter; o.feastol = opts->feastol; o.abstol = opts->abstol; o.reltol = opts->reltol;
-        o.reg = opts->reg; o.dyn_eps = opts->dyn_eps; o.dyn_delta = opts->dyn_delta; o.nref = opts->nref;
-        o.ref_tol = opts->ref_tol; o.step = opts->step;
-    }
-    return o;
-}
-
 static int sub_put_scal(scp_sub* s, int B, const double* scal)
 {
     if (s->nscal == 0) return SCP_OK;
@@ -571,7 +549,7 @@ extern "C" int scp_sub_solve_batch_host(scp_sub_handle s, int B, const double* x
     int rc;
     if ((rc = sub_fill_sources(s, B, nullptr)) != SCP_OK) return rc;
     if ((rc = sub_put_scal(s, B, scal)) != SCP_OK) return rc;
-    if ((rc = sub_solve_dev(s, B, sub_opts(opts), nullptr)) != SCP_OK) return rc;
+    if ((rc = sub_solve_dev(s, B, scp::conic::opts_from_abi(opts), nullptr)) != SCP_OK) return rc;
     SUB_TRY(hipEventRecord(h->timing.ev1, h->stream));
     SUB_CALL(download_traj(h, B, true, x, u, p, defect));
     if (status) SUB_TRY(hipMemcpyAsync(status, s->eng.status, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
@@ -753,7 +731,7 @@ static int loop_begin(scp_sub* s, scp_sub* proj, RunKind loop, int B, int iter_m
     int rc;
     if ((rc = sub_loop_state(s, iter_max)) != SCP_OK) return rc;
     h->run = Run{loop, s};   // takes the trajectory buffers over; the projection below (sub_solve_dev) leaves that alone
-    s->B = B; s->iter = 0; s->iter_max = iter_max; s->opts = sub_opts(&solver); s->q_exit = q_exit; s->q_tr = q_tr;
+    s->B = B; s->iter = 0; s->iter_max = iter_max; s->opts = scp::conic::opts_from_abi(&solver); s->q_exit = q_exit; s->q_tr = q_tr;
     SUB_CALL(upload_traj(h, B, xd, ud, p, h->traj.ref_xd, h->traj.ref_ud, h->traj.ref_p));
     if (h->info.npp > 0) {
         SUB_TRY(hipMemcpyAsync(s->d_pp, pp, sizeof(double) * h->info.npp * B, hipMemcpyHostToDevice, h->stream));
@@ -1261,7 +1239,7 @@ extern "C" int scp_ptr_generic_continue(scp_sub_handle s, const scp_ptr_generic_
     SUB_TRY(hipSetDevice(h->device));
     if (pars) {
         if ((rc = sub_loop_state(s, pars->iter_max)) != SCP_OK) return rc;
-        s->pg = *pars; s->iter_max = pars->iter_max; s->opts = sub_opts(&pars->solver); s->q_exit = s->q_tr = pars->q_exit;
+        s->pg = *pars; s->iter_max = pars->iter_max; s->opts = scp::conic::opts_from_abi(&pars->solver); s->q_exit = s->q_tr = pars->q_exit;
     }
     const int B = s->B;
     scp::PtrgContinueArgs a;
