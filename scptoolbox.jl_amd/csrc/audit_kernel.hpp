@@ -40,13 +40,6 @@ struct AuditArgs {
 int audit_launch(int model_id, const double* model_par, const AuditArgs& a, hipStream_t stream);
 int audit_mask_from_status(const int* status, int* mask, int B, hipStream_t stream);
 
-// Julia LinRange(a,b,n)[j] (0-based j): the `linrange` of discretize_kernel.hpp, callable from the host twin too
-SCP_DEV double audit_linrange(double a, double b, int n, int j)
-{
-    const double tt = (double)j / (double)(n - 1);
-    return (1.0 - tt) * a + tt * b;
-}
-
 // what the samples of one flight (audit_flight_one) or of one interval (audit_interval_one) accumulate
 struct AuditAcc {
     double s_max = -INFINITY, t_s = 0.0, l_max = -INFINITY, t_l = 0.0, c_max = -INFINITY, t_c = 0.0, n_viol = 0.0;
@@ -242,14 +235,14 @@ SCP_DEV void audit_flight_one(const typename M::Params& par, int N, int res_or_s
     for (int i = 0; i < nu; i++) { ug[i] = gain != nullptr ? gain[i] : 1.0; ubs[i] = bias != nullptr ? bias[i] : 0.0; du[i] = 0.0; wk[i] = 0.0; }
     // u(t) and f(t, x): propagate_foh_kernel's own, then the mode's feedback, gain and bias
     auto input = [&](double t, double (&u)[nu]) {
-        const double g0 = audit_linrange(0.0, 1.0, N, 0), g1 = audit_linrange(0.0, 1.0, N, N - 1);
+        const double g0 = linrange(0.0, 1.0, N, 0), g1 = linrange(0.0, 1.0, N, N - 1);
         t = fmax(g0, fmin(g1, t));
         int k = (int)floor(t * (N - 1));
         k = k < 0 ? 0 : (k > N ? N : k);
-        while (k < N && t > audit_linrange(0.0, 1.0, N, k)) k++;
-        while (k > 0 && !(t > audit_linrange(0.0, 1.0, N, k - 1))) k--;
+        while (k < N && t > linrange(0.0, 1.0, N, k)) k++;
+        while (k > 0 && !(t > linrange(0.0, 1.0, N, k - 1))) k--;
         if (k == 0) k = 1;
-        const double ta = audit_linrange(0.0, 1.0, N, k - 1), tb = audit_linrange(0.0, 1.0, N, k);
+        const double ta = linrange(0.0, 1.0, N, k - 1), tb = linrange(0.0, 1.0, N, k);
         const double c = (tb - t) / (tb - ta);
 #pragma unroll
         for (int i = 0; i < nu; i++) {
@@ -279,8 +272,8 @@ SCP_DEV void audit_flight_one(const typename M::Params& par, int N, int res_or_s
         // 1-based index of the last grid node <= t, decided against the exact grid values (N at t = 1)
         int k = (int)floor(t * (N - 1)) + 1;
         k = k < 1 ? 1 : (k > N ? N : k);
-        while (k < N && !(audit_linrange(0.0, 1.0, N, k) > t)) k++;
-        while (k > 1 && audit_linrange(0.0, 1.0, N, k - 1) > t) k--;
+        while (k < N && !(linrange(0.0, 1.0, N, k) > t)) k++;
+        while (k > 1 && linrange(0.0, 1.0, N, k - 1) > t) k--;
         double u[nu];
         input(t, u);
         return audit_sample<M>(par, t, k, x, u, pb, viol_tol, Qu, lu, lx, acc);
@@ -332,12 +325,12 @@ SCP_DEV void audit_flight_one(const typename M::Params& par, int N, int res_or_s
     };
 
     if constexpr (tracking) node(1);
-    gam_prev = sample(audit_linrange(0.0, 1.0, res, 0));
+    gam_prev = sample(linrange(0.0, 1.0, res, 0));
     for (int j = 1; j < res; j++) {
         if constexpr (tracking) {
             if (j > 1 && (j - 1) % steps == 0) node((j - 1) / steps + 1);
         }
-        const double t = audit_linrange(0.0, 1.0, res, j - 1), tp = audit_linrange(0.0, 1.0, res, j), h = tp - t;
+        const double t = linrange(0.0, 1.0, res, j - 1), tp = linrange(0.0, 1.0, res, j), h = tp - t;
         double k1[nx], k2[nx], k3[nx], k4[nx], tmp[nx];
         f(t, x, k1);
 #pragma unroll
@@ -447,7 +440,7 @@ SCP_DEV void audit_interval_one(const typename M::Params& par, int N, int sub, i
     static_assert(M::np_node == 0, "a row of node k would read that node's own parameters: undefined between the nodes");
     static_assert(!IMP || M::has_impulse, "the model has no impulsive-input form");
     constexpr int nx = M::nx, nu = M::nu, np = M::np, npa = np > 0 ? np : 1, npF = M::npF, npFa = npF > 0 ? npF : 1;
-    const double t0 = audit_linrange(0.0, 1.0, N, k0), t1 = audit_linrange(0.0, 1.0, N, k0 + 1);
+    const double t0 = linrange(0.0, 1.0, N, k0), t1 = linrange(0.0, 1.0, N, k0 + 1);
 
     double x[nx], ua[nu], ub[nu];
 #pragma unroll
@@ -495,9 +488,9 @@ SCP_DEV void audit_interval_one(const typename M::Params& par, int N, int sub, i
         return audit_sample<M>(par, t, k, x, u, pb, viol_tol, Qu, lu, lx, acc);
     };
 
-    double gam_prev = sample(audit_linrange(t0, t1, sub, 0), k0 + 1), cost_int = 0.0;
+    double gam_prev = sample(linrange(t0, t1, sub, 0), k0 + 1), cost_int = 0.0;
     for (int j = 1; j < sub; j++) {
-        const double t = audit_linrange(t0, t1, sub, j - 1), tp = audit_linrange(t0, t1, sub, j), h = tp - t;
+        const double t = linrange(t0, t1, sub, j - 1), tp = linrange(t0, t1, sub, j), h = tp - t;
         double k1[nx], k2[nx], k3[nx], k4[nx], tmp[nx];
         f(t, x, k1);
 #pragma unroll

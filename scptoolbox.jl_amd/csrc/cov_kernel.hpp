@@ -69,7 +69,7 @@ SCP_DEV void cov_rows_one(const typename M::Params& par, int N, int k, const dou
     constexpr int nx = M::nx, nu = M::nu, nz = nx + nu, np = M::np, npa = np > 0 ? np : 1, nw = nx + 1;
     constexpr int ns = M::ns, nsa = ns > 0 ? ns : 1, nl = M::nl, nla = nl > 0 ? nl : 1, nsoc = M::nsoc, nsoca = nsoc > 0 ? nsoc : 1;
     constexpr int ntc = M::ntc, ntca = ntc > 0 ? ntc : 1;
-    const double t = audit_linrange(0.0, 1.0, N, k - 1);
+    const double t = linrange(0.0, 1.0, N, k - 1);
     const bool hold = k < N;
     double x[nx], u[nu], z[nz], Kk[nu * nx];
 #pragma unroll

@@ -56,13 +56,6 @@ struct DiscArgs {
     const int* mask; // optional [B]: problems with mask[b] == 0 are skipped (converged in the SCP loop)
 };
 
-// Julia LinRange(a,b,n)[j] (0-based j), Base `lerpi`: (1-j/(n-1))*a + (j/(n-1))*b
-__device__ __forceinline__ double linrange(double a, double b, int n, int j)
-{
-    const double tt = (double)j / (double)(n - 1);
-    return (1.0 - tt) * a + tt * b;
-}
-
 enum Role { R_PHI = 0, R_BM = 1, R_BP = 2, R_F = 3, R_R = 4, R_E = 5, R_IDLE = 6 };
 
 // 1 / a for the pivots of the cooperative LU.  Default: the IEEE division.  -DSCP_K1_RCP: hardware estimate + two Newton steps (7
@@ -109,6 +102,43 @@ struct DiscLayout {
     static_assert(NCOL <= 64, "augmented matrix wider than a wavefront");
     static constexpr int GROUPS_PER_BLOCK = 256 / G;
 };
+
+// The forms of discretize! a model can be launched with beside the reference form K1 (discretize_foh_kernel<M>), which every model has:
+// discretize_dev (scp_api.hip) instantiates the kernels of these forms and no others.  The fp32 variant of K1 goes by M::has_fp32, the
+// IMPULSE kernels (discretize_foh_kernel<M, true>, propagate_impulse_kernel) by M::has_impulse.
+template <class M>
+struct DiscForms {
+    static constexpr bool k1v = M::const_jacobian && M::var_form_max_step > 0.0;         // discretize_foh_var_kernel
+    static constexpr bool k1x = !M::const_jacobian && M::var_form_max_phys_step > 0.0;   // discretize_foh_varx_kernel, disc_split_kernel
+};
+
+// ------------------------------------------------------------------------------------------------
+// Steps of the reference's text that the forms of discretize! below (K1, K1v, K1x) share, each written once.  Everything is inlined.
+// A step is shared only where every kernel keeps its instruction stream, compared per kernel with tools/kernel_set.py diff: the
+// residual, the destination pointers, the defect tail and the RK4 steps are still written out per kernel because a common body
+// changed register allocation or operand order in some instantiation (profiles/k1_kernel_set.txt lists which).
+// ------------------------------------------------------------------------------------------------
+
+// u(t) on [t0, t1]: linterp on the 2-point grid (helper.jl:107-118), saturating t
+template <int NU, class T>
+__device__ __forceinline__ void foh_input(T t, T t0, T t1, const T (&u0)[NU], const T (&u1)[NU], T (&u)[NU])
+{
+    const T tc = fmax(t0, fmin(t1, t));
+    const T cc = (t1 - tc) / (t1 - t0);
+#pragma unroll
+    for (int i = 0; i < NU; i++) u[i] = cc * u0[i] + ((T)1 - cc) * u1[i];
+}
+
+// entry i of column `col` of a column-major NX x NC matrix held in registers: `col` is a run-time value, so the column is picked by a
+// chain of selects, never by an index into the array
+template <int NX, int NC, class T>
+__device__ __forceinline__ T column_entry(const T (&mat)[NX * NC], int i, int col)
+{
+    T v = 0.0;
+#pragma unroll
+    for (int j = 0; j < NC; j++) v = (col == j) ? mat[i + NX * j] : v;
+    return v;
+}
 
 // T: the arithmetic type of the whole integration (state, Phi, the LU, the RK4 accumulators, the model evaluation).
 // T = double is the reference's arithmetic (basic_types.jl:31); T = float is the "fp64 vs fp32 tolerance check" variant
@@ -171,12 +201,7 @@ __global__ __launch_bounds__(256) void discretize_foh_kernel(DiscArgs a, typenam
         for (int i = 0; i < nx; i++) x[i] += dx[i];          // xk_plus = xk + f(tk, -k, xk, uk, p)  (:191-192)
         if (role == R_BM) {
 #pragma unroll
-            for (int i = 0; i < nx; i++) {
-                T v = 0.0;
-#pragma unroll
-                for (int j = 0; j < nu; j++) v = (ridx == j) ? Bi[i + nx * j] : v;
-                bimp[i] = v;
-            }
+            for (int i = 0; i < nx; i++) bimp[i] = column_entry<nx, nu>(Bi, i, ridx);
         }
     }
 
@@ -188,12 +213,13 @@ __global__ __launch_bounds__(256) void discretize_foh_kernel(DiscArgs a, typenam
     // derivs_foh (:235-286) for this lane: returns f (all lanes) and the lane's column derivative
     auto derivs = [&](T t, const T (&xs)[nx], const T (&cs)[nx], T (&fx)[nx],
                       T (&dc)[nx]) {
-        // linterp on the 2-point grid (helper.jl:107-118), saturating t
-        const T tc = fmax(t0, fmin(t1, t));
-        const T cc = (t1 - tc) / (t1 - t0);
         T u[nu];
+        if constexpr (IMP) {
 #pragma unroll
-        for (int i = 0; i < nu; i++) u[i] = IMP ? (T)0 : cc * u0[i] + ((T)1 - cc) * u1[i];   // IMPULSE: coasting (:321)
+            for (int i = 0; i < nu; i++) u[i] = (T)0;   // IMPULSE: coasting (:321)
+        } else {
+            foh_input(t, t0, t1, u0, u1, u);
+        }
         const T sm = (t1 - t) / (t1 - t0);  // :252
         const T sp = (t - t0) / (t1 - t0);  // :253
         T Am[nx * nx], Bmat[nx * nu], Fc[nx * npFa];
@@ -221,15 +247,8 @@ __global__ __launch_bounds__(256) void discretize_foh_kernel(DiscArgs a, typenam
             if (role == R_PHI) v = cs[i];
             else if (role == R_R) v = rr[i];
             else if (role == R_E) v = (i == ridx) ? 1.0 : 0.0;  // E = I(nx), scp.jl:149
-            else if (role == R_BM || role == R_BP) {
-                T bcol = 0.0;
-#pragma unroll
-                for (int j = 0; j < nu; j++) bcol = (ridx == j) ? Bmat[i + nx * j] : bcol;
-                v = IMP ? 0.0 : (role == R_BM ? sm : sp) * bcol;  // :260-261 (IMPULSE: no B blocks in V)
-            } else if (role == R_F) {
-#pragma unroll
-                for (int j = 0; j < npFa; j++) v = (ridx == j) ? Fc[i + nx * j] : v;
-            }
+            else if (role == R_BM || role == R_BP) v = IMP ? 0.0 : (role == R_BM ? sm : sp) * column_entry<nx, nu>(Bmat, i, ridx);  // :260-261 (IMPULSE: no B blocks in V)
+            else if (role == R_F) v = column_entry<nx, npFa>(Fc, i, ridx);
             w[i] = v;
         }
         // ---- cooperative LU with partial pivoting on [Phi | rhs]  (Phi \ I, :267) ----
@@ -378,8 +397,10 @@ __global__ __launch_bounds__(256) void discretize_foh_kernel(DiscArgs a, typenam
 
 // ------------------------------------------------------------------------------------------------
 // K1v: variational form of the same quantities, for models whose dynamics are linear in (x, u) with
-// coefficient matrices that do not depend on (t, x, u) inside an interval (M::const_jacobian: every registered
-// model so far -- linear dynamics scaled by the time dilation).  Instead of integrating int Phi^-1 [..] and
+// coefficient matrices that do not depend on (t, x, u) inside an interval (M::const_jacobian: linear dynamics scaled
+// by the time dilation) and with M::var_form_max_step > 0 -- the double integrator, the quadrotor and the rocket
+// landing (DiscForms<M>::k1v; the oscillator's A is constant too, but its two forms part ways at every grid in
+// use, models/oscillator.hpp).  Instead of integrating int Phi^-1 [..] and
 // multiplying by Phi(t_{k+1}) at the end (reference formulation, kernel above), each output column
 // Psi = Phi * int Phi^-1 rhs is integrated directly:
 //        Psi' = A Psi + rhs(t),  Psi(t_k) = 0      (Phi' = A Phi, Phi(t_k) = I),
@@ -472,11 +493,8 @@ __global__ __launch_bounds__(256) void discretize_foh_var_kernel(DiscArgs a, typ
 #pragma unroll
         for (int j = 0; j < npFa; j++) pF[j] = (npF > 0) ? pb[M::Fcol(j)] : 0.0;
         auto derivs = [&](double t, const double (&xs)[nx], const double (&cs)[nx], double (&fx)[nx], double (&dc)[nx]) {
-            const double tc = fmax(t0, fmin(t1, t));
-            const double cc = (t1 - tc) / (t1 - t0);
             double u[nu];
-#pragma unroll
-            for (int i = 0; i < nu; i++) u[i] = cc * u0[i] + (1.0 - cc) * u1[i];
+            foh_input(t, t0, t1, u0, u1, u);
             double Am[nx * nx], Bmat[nx * nu], Fc[nx * npFa];
             M::dyn(par, t, k + 1, xs, u, pb, fx, Am, Bmat, Fc);
             double rhs[nx], ax[nx], ac[nx];
@@ -496,12 +514,7 @@ __global__ __launch_bounds__(256) void discretize_foh_var_kernel(DiscArgs a, typ
                 }
             } else {
 #pragma unroll
-                for (int i = 0; i < nx; i++) {
-                    double v = 0.0;
-#pragma unroll
-                    for (int j = 0; j < npFa; j++) v = (ridx == j) ? Fc[i + nx * j] : v;
-                    rhs[i] = v;
-                }
+                for (int i = 0; i < nx; i++) rhs[i] = column_entry<nx, npFa>(Fc, i, ridx);
             }
 #pragma unroll
             for (int i = 0; i < nx; i++) dc[i] = ac[i] + rhs[i];
@@ -543,7 +556,8 @@ __global__ __launch_bounds__(256) void discretize_foh_var_kernel(DiscArgs a, typ
 }
 
 // ------------------------------------------------------------------------------------------------
-// K1x: the variational form for models with STATE-DEPENDENT Jacobians (free-flyer, Starship).  Every output column
+// K1x: the variational form for models with STATE-DEPENDENT Jacobians that declare a step bound for it (DiscForms<M>::k1x: the
+// free-flyer; the Starship declares none and runs K1 at every grid).  Every output column
 // Psi = Phi * int Phi^-1 rhs obeys Psi' = A(t, x(t), u(t)) Psi + rhs(t), so a thread that integrates the state alongside
 // needs no Phi^-1: no LU, no cross-lane traffic -- one thread per (problem, interval, column), one instantiation per ROLE
 // (the role decides which of f, A, B, F the model evaluation has to produce; the rest is dead code in that instantiation).
@@ -580,31 +594,18 @@ __global__ __launch_bounds__(256) void discretize_foh_varx_kernel(DiscArgs a, ty
 #pragma unroll
     for (int j = 0; j < npFa; j++) pF[j] = (npF > 0) ? pb[M::Fcol(j)] : 0.0;
     auto derivs = [&](double t, const double (&xs)[nx], const double (&cs)[nx], double (&fx)[nx], double (&dc)[nx]) {
-        const double tc = fmax(t0, fmin(t1, t));
-        const double cc = (t1 - tc) / (t1 - t0);
         double u[nu];
-#pragma unroll
-        for (int i = 0; i < nu; i++) u[i] = cc * u0[i] + (1.0 - cc) * u1[i];
+        foh_input(t, t0, t1, u0, u1, u);
         double Am[nx * nx], Bmat[nx * nu], Fc[nx * npFa];
         M::dyn(par, t, k + 1, xs, u, pb, fx, Am, Bmat, Fc);       // :256-259 (unused outputs are dead code per ROLE)
         double rhs[nx];
         if constexpr (ROLE == R_BM || ROLE == R_BP) {
             const double sg = ROLE == R_BM ? (t1 - t) / (t1 - t0) : (t - t0) / (t1 - t0);   // :252-253
 #pragma unroll
-            for (int i = 0; i < nx; i++) {
-                double v = 0.0;
-#pragma unroll
-                for (int j = 0; j < nu; j++) v = (ridx == j) ? Bmat[i + nx * j] : v;
-                rhs[i] = sg * v;
-            }
+            for (int i = 0; i < nx; i++) rhs[i] = sg * column_entry<nx, nu>(Bmat, i, ridx);
         } else if constexpr (ROLE == R_F) {
 #pragma unroll
-            for (int i = 0; i < nx; i++) {
-                double v = 0.0;
-#pragma unroll
-                for (int j = 0; j < npFa; j++) v = (ridx == j) ? Fc[i + nx * j] : v;
-                rhs[i] = v;
-            }
+            for (int i = 0; i < nx; i++) rhs[i] = column_entry<nx, npFa>(Fc, i, ridx);
         } else if constexpr (ROLE == R_R) {       // r = f - A x - B u - F p  (:262)
             double ax[nx];
             if constexpr (M::has_amulx) M::Amulx(par, pb, xs, xs, ax);

@@ -20,7 +20,6 @@ struct Freeflyer : ModelDefaults {
     static constexpr int np_node = 6;                 // delta[:, k]: one room-SDF slack per room of the station
     static constexpr int n_obs = 3, n_iss = 6;        // ellipsoidal obstacles / rooms (parameters.jl:95-109)
     static constexpr bool const_jacobian = false;
-    static constexpr double var_form_max_step = 0.0;
     static constexpr bool structured = false;
     // variational form of discretize! (K1x) for physical RK4 steps up to 0.047 s: measured against the reference formulation on
     // strongly perturbed trajectories at N = 200, Nsub = 15 -- B-, B+ 4.3e-11 (t_f = 110 s), 7.1e-11 (130 s = 0.0467 s steps),
@@ -112,7 +111,6 @@ struct Freeflyer : ModelDefaults {
 #pragma unroll
         for (int i = 0; i < 3; i++) { B[(3 + i) + nx * i] = td / P.m; B[(10 + i) + nx * (3 + i)] = td / P.J[i]; }
     }
-    SCP_DEV static void Amul(const Params&, const double*, const double (&)[nx], double (&out)[nx]) { zero(out); }
     // out = A(x, p) v without forming the 13 x 13 matrix (39 structural non-zeros, the same entries as dyn() writes): the
     // variational discretize! kernel (K1x) multiplies A by one column per RK4 stage
     static constexpr bool has_amulx = true;
@@ -137,7 +135,6 @@ struct Freeflyer : ModelDefaults {
         }
         out[9] = -0.5 * td * (w[0] * a[0] + w[1] * a[1] + w[2] * a[2] + qv[0] * b[0] + qv[1] * b[1] + qv[2] * b[2]);
     }
-    SCP_DEV static void Bcol(const Params&, const double*, int, double (&out)[nx]) { zero(out); }
     // integration action (definition.jl:69-82): renormalise the quaternion after every full RK4 step
     template <class T>
     SCP_DEV static void action(T (&x)[nx])
@@ -147,12 +144,7 @@ struct Freeflyer : ModelDefaults {
         for (int i = 6; i < 10; i++) x[i] /= n;
     }
     static constexpr bool has_fp32 = false;
-    static constexpr bool has_impulse = false;
-    SCP_DEV static void impulse(const Params&, double, int, const double (&)[nx], const double (&)[nu], const double*,
-                                double (&dx)[nx], double (&B)[nx * nu])
-    {
-        zero(dx); zero(B);
-    }
+    static constexpr bool has_impulse = false;   // no impulsive-input form of this model (IMPULSE -> SCP_ERR_UNSUPPORTED)
 
     // per-problem data pp = [r0 v0 q0 w0 rf vf qf wf] (npp = 26, below)
 

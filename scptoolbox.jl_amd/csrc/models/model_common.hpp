@@ -14,6 +14,13 @@ SCP_DEV void zero(double (&a)[N])
     for (int i = 0; i < N; i++) a[i] = 0.0;
 }
 
+// Julia LinRange(a,b,n)[j] (0-based j), Base `lerpi`: (1-j/(n-1))*a + (j/(n-1))*b -- every time grid of the kernels and of their host twins
+SCP_DEV double linrange(double a, double b, int n, int j)
+{
+    const double tt = (double)j / (double)(n - 1);
+    return (1.0 - tt) * a + tt * b;
+}
+
 // Traits every model inherits; a model overrides what differs.
 //
 // PARAMETER VECTOR.  p = [global (M::np); node parameters (M::np_node, N) column-major], length np + np_node N -- the
@@ -39,6 +46,10 @@ struct ModelDefaults {
     static constexpr int linf_groups = 0, linf_rows = 0;
     // s(t, k, x, p) does not depend on the input: the model is admissible for GuSTO (gusto.jl:757-792)
     static constexpr bool s_input_free = false;
+    // models with const_jacobian: largest normalised RK4 step 1 / ((N-1)(Nsub-1)) up to which the variational form of discretize! (K1v,
+    // discretize_kernel.hpp) agrees with the reference formulation to 1e-10; 0 = never.  A model that sets it provides the structured
+    // products Amul (out = A v) and Bcol (column j of B), which K1v alone calls
+    static constexpr double var_form_max_step = 0.0;
     // models with state-dependent Jacobians: largest PHYSICAL RK4 step time_dilation(p) * h [s] up to which the variational
     // form of discretize! (K1x, discretize_kernel.hpp) agrees with the reference formulation to 1e-10; 0 = never
     static constexpr double var_form_max_phys_step = 0.0;

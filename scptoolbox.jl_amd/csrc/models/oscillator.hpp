@@ -27,7 +27,7 @@ struct Oscillator : ModelDefaults {
     static constexpr int np_node = 1;                 // l1r_k >= |r_k|
     static constexpr bool node_par_in_running_cost = true;
     static constexpr bool const_jacobian = true;
-    static constexpr double var_form_max_step = 0.0;  // see DISCRETISATION above
+    static constexpr double var_form_max_step = 0.0;  // see DISCRETISATION above: no K1v, hence no Amul / Bcol either
     static constexpr bool has_subproblem = true;
     static constexpr bool structured = false;
     static constexpr bool s_input_free = false;       // s is a function of the input alone
@@ -59,12 +59,6 @@ struct Oscillator : ModelDefaults {
         B[1] = P.tf;                                   // B[v, aa]
         Fc[0] = 0.0; Fc[1] = 0.0;
     }
-    SCP_DEV static void Amul(const Params& P, const double*, const double (&v)[nx], double (&out)[nx])
-    {
-        out[0] = P.tf * v[1];
-        out[1] = -P.tf * P.w0 * P.w0 * v[0] - 2.0 * P.tf * P.zeta * P.w0 * v[1];
-    }
-    SCP_DEV static void Bcol(const Params& P, const double*, int j, double (&out)[nx]) { out[0] = 0.0; out[1] = j == 0 ? P.tf : 0.0; }
     SCP_DEV static void action(double (&)[nx]) {}
     static constexpr bool has_fp32 = false;
     // IMPULSE (definition.jl:170-186, 216-227: the k < 0 branch): dx = [0; aa], B[v, aa] = 1, neither scaled by t_f

@@ -13,7 +13,7 @@ struct RocketLanding : ModelDefaults {
     static constexpr int nx = 7, nu = 4, np = 1, npF = 1;
     // Jacobians A, B, F do not depend on (t, x, u) inside an interval -> variational discretize! kernel (K1v)
     static constexpr bool const_jacobian = true;
-    static constexpr bool has_subproblem = true;   // false: discretize! / propagate / guess only (freeflyer.hpp)
+    static constexpr bool has_subproblem = true;
     static constexpr bool structured = true;   // stage-structured PTR fast path available (stage_problem.hpp, ipm2_*.hpp)
     // largest normalised RK4 step 1/((N-1)(Nsub-1)) for which K1v matches the reference formulation to < 1e-10
     // (Coriolis terms: the two RK4 forms differ by O((tf h)^4) ~ 1e-13 at h = 1e-2, tf = 150 s (measured)); coarser grids use the reference-form kernel K1
@@ -115,11 +115,6 @@ struct RocketLanding : ModelDefaults {
     SCP_DEV static void action(double (&)[nx]) {}
     static constexpr bool has_fp32 = false;    // fp32 variant of K1 (scp_set_discretize_precision): Starship only
     static constexpr bool has_impulse = false;   // no impulsive-input form of this model (IMPULSE -> SCP_ERR_UNSUPPORTED)
-    SCP_DEV static void impulse(const Params&, double, int, const double (&)[nx], const double (&)[nu], const double*,
-                                double (&dx)[nx], double (&B)[nx * nu])
-    {
-        zero(dx); zero(B);
-    }
     // initial guess at node k of N: straight line from (r0, v0, ln m_wet) to (0, 0, ln m_dry), hover input, tf = 75 s
     SCP_DEV static void guess(const Params& P, const double* pp, int N, int k, double (&x)[nx], double (&u)[nu], double* p, double*)
     {

@@ -13,8 +13,7 @@ struct Starship : ModelDefaults {
     static constexpr int id = 3;
     static constexpr int nx = 8, nu = 3, np = 10, npF = 2;   // F: only the columns of t1 and t2 are ever non-zero (:627-634)
     static constexpr bool const_jacobian = false;
-    static constexpr double var_form_max_step = 0.0;
-    static constexpr bool has_subproblem = true;   // false: discretize! / propagate / guess only (freeflyer.hpp)
+    static constexpr bool has_subproblem = true;
     static constexpr bool structured = false;                // no stage-structured fast path (np = 10, ns = 21)
     // Parameter blob (include/scp_mi355x.h, scp_problem_desc.model_par) -- everything the reference keeps in `traj.mdl`
     // (parameters.jl:99-212) is data:
@@ -110,17 +109,9 @@ struct Starship : ModelDefaults {
 #pragma unroll
         for (int i = 0; i < nx; i++) { Fc[i + nx * it] = f[i] / pt[it]; Fc[i + nx * (1 - it)] = nil; }
     }
-    // the variational kernel is never selected for this model (const_jacobian = false); stubs keep the templates complete
-    SCP_DEV static void Amul(const Params&, const double*, const double (&)[nx], double (&out)[nx]) { zero(out); }
-    SCP_DEV static void Bcol(const Params&, const double*, int, double (&out)[nx]) { zero(out); }
     template <class T>
     SCP_DEV static void action(T (&)[nx]) {}
-    static constexpr bool has_impulse = false;
-    SCP_DEV static void impulse(const Params&, double, int, const double (&)[nx], const double (&)[nu], const double*,
-                                double (&dx)[nx], double (&B)[nx * nu])
-    {
-        zero(dx); zero(B);
-    }
+    static constexpr bool has_impulse = false;   // no impulsive-input form of this model (IMPULSE -> SCP_ERR_UNSUPPORTED)
     // Straight-line guess between the boundary states (the reference's bang-bang + LCvx guess, definition.jl:97-445, is
     // host-side pre-processing and can be passed in as a warm start): x from pp to the landing state, hover thrust,
     // t1 = t2 = 10 s, xs = state at the phase switch.

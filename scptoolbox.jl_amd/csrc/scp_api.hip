@@ -381,13 +381,19 @@ int scp::discretize_dev(scp_problem* h, int B, const double* xd, const double* u
                 return (int)SCP_ERR_UNSUPPORTED;
             }
         } else if (h->method == SCP_IMPULSE) {
-            hipLaunchKernelGGL((discretize_foh_kernel<M, true>), dim3(blocks), dim3(256), 0, h->stream, a, P);
-        } else if (M::const_jacobian && !h->disc.reference_form && rk4_step <= M::var_form_max_step) {
+            if constexpr (M::has_impulse) {
+                hipLaunchKernelGGL((discretize_foh_kernel<M, true>), dim3(blocks), dim3(256), 0, h->stream, a, P);
+            } else {
+                return (int)SCP_ERR_UNSUPPORTED;   // (scp_problem_create rejects IMPULSE for these models)
+            }
+        } else if (DiscForms<M>::k1v && !h->disc.reference_form && rk4_step <= M::var_form_max_step) {
             // variational form (K1v): thread per (problem, interval, column), blockIdx.y = column
-            const unsigned gx = (unsigned)((groups + 255) / 256);
-            hipLaunchKernelGGL((discretize_foh_var_kernel<M, false>), dim3(gx, 2 * M::nx + 2 * M::nu), dim3(256), 0, h->stream, a, P);
-            hipLaunchKernelGGL((discretize_foh_var_kernel<M, true>), dim3(gx, M::npF + 1), dim3(256), 0, h->stream, a, P);
-        } else if (!M::const_jacobian && M::var_form_max_phys_step > 0.0) {
+            if constexpr (DiscForms<M>::k1v) {
+                const unsigned gx = (unsigned)((groups + 255) / 256);
+                hipLaunchKernelGGL((discretize_foh_var_kernel<M, false>), dim3(gx, 2 * M::nx + 2 * M::nu), dim3(256), 0, h->stream, a, P);
+                hipLaunchKernelGGL((discretize_foh_var_kernel<M, true>), dim3(gx, M::npF + 1), dim3(256), 0, h->stream, a, P);
+            }
+        } else if constexpr (DiscForms<M>::k1x) {
             // state-dependent Jacobians: per problem the variational form (K1x) where it meets the reference formulation to
             // 1e-10 (physical RK4 step below the model's bound), the reference form (K1) elsewhere
             if (!h->disc.d_mvar) { TRY(dalloc(h, &h->disc.d_mvar, 2 * (size_t)h->cap)); }
@@ -544,8 +550,12 @@ extern "C" int scp_propagate_batch_host(scp_handle h, int B, const double* xd, c
         using M = decltype(m);
         typename M::Params P = M::make_params(h->par.data());
         if (imp) {
-            const long tot = (long)B * (h->N - 1);
-            hipLaunchKernelGGL(propagate_impulse_kernel<M>, dim3((unsigned)((tot + 63) / 64)), dim3(64), 0, h->stream, ai, P);
+            if constexpr (M::has_impulse) {
+                const long tot = (long)B * (h->N - 1);
+                hipLaunchKernelGGL(propagate_impulse_kernel<M>, dim3((unsigned)((tot + 63) / 64)), dim3(64), 0, h->stream, ai, P);
+            } else {
+                return (int)SCP_ERR_UNSUPPORTED;   // (scp_problem_create rejects IMPULSE for these models)
+            }
         } else {
             hipLaunchKernelGGL(propagate_foh_kernel<M>, dim3((B + 63) / 64), dim3(64), 0, h->stream, a, P);
         }

@@ -15,9 +15,10 @@ TOL = 1e-10
 NAMES = ("A", "Bm", "Bp", "F", "r", "E", "defect")
 
 
-def _run(pkg, orc, model, N, Nsub, B, seed, feas_tol=1e-3, noise=0.05):
+def _run(pkg, orc, model, N, Nsub, B, seed, feas_tol=1e-3, noise=0.05, method="foh", res=None):
+    """discretize! of B perturbed guesses on the device and by the C oracle; with `res` the propagation of the same batch too"""
     traj = pkg.TrajectoryProblem(model)
-    pars = pkg.PTR.Parameters(N=N, Nsub=Nsub, iter_max=1, feas_tol=feas_tol)
+    pars = pkg.PTR.Parameters(N=N, Nsub=Nsub, iter_max=1, feas_tol=feas_tol, disc_method=pkg.IMPULSE if method == "impulse" else pkg.FOH)
     pbm = pkg.PTR.create(pars, traj, batch_capacity=B)
     rng = np.random.default_rng(seed)
     xs, us, ps = [], [], []
@@ -30,9 +31,11 @@ def _run(pkg, orc, model, N, Nsub, B, seed, feas_tol=1e-3, noise=0.05):
         ps.append(p * (1 + 0.1 * rng.uniform(-1, 1, size=p.shape)))
     ref = pkg.SubproblemSolutionBatch(np.stack(xs), np.stack(us), np.stack(ps).reshape(B, -1), pbm)
     pkg.discretize_(ref, pbm)
-    o = orc.discretize(model, orc.default_params(model), N, Nsub, ref.xd, ref.ud, ref.p, pbm.scale.iSx, feas_tol)
+    o = orc.discretize(model, orc.default_params(model), N, Nsub, ref.xd, ref.ud, ref.p, pbm.scale.iSx, feas_tol, method=method)
     got = dict(A=ref.dyn.A, Bm=ref.dyn.B[0], Bp=ref.dyn.B[1], F=ref.dyn.F, r=ref.dyn.r, E=ref.dyn.E,
                defect=ref.defect)
+    if res is not None:
+        got["tc"], got["xc"] = pkg.propagate(ref, pbm, res=res)
     pbm.close()
     return ref, got, o
 
@@ -57,6 +60,33 @@ def test_discretize_parity(pkg, orc, model, N, Nsub, B, form, monkeypatch):
         err = float(np.max(np.abs(got[nm] - o[nm]))) / scale if o[nm].size else 0.0
         assert err < TOL, (nm, err)
     assert (ref.feas == o["feas"]).all()
+
+
+@pytest.mark.parametrize("model", ["double_integrator", "quadrotor"])
+@pytest.mark.parametrize("N,Nsub,B", [
+    (2, 2, 1),       # minimum grid, single problem: one interval, one RK4 step
+    (3, 2, 33),      # 66 intervals: ragged against the 8 (DI) and the 4 (quadrotor) lane groups of a K1 block and against
+])                   # the 64 threads of a propagate block
+def test_impulse_forms_on_the_smallest_grids(pkg, orc, model, N, Nsub, B):
+    """The IMPULSE kernels (discretize_foh_kernel<M, true>, propagate_impulse_kernel<M>) where their indexing can go wrong;
+    tests/test_generic_gpu.py has them at one mid-size grid.  Oracle: the C restatement, for the models it knows with an
+    impulse response."""
+    res = 5
+    ref, got, o = _run(pkg, orc, model, N, Nsub, B, seed=12, method="impulse", res=res)
+    for nm in NAMES:
+        scale = max(1.0, float(np.max(np.abs(o[nm])))) if o[nm].size else 1.0
+        err = float(np.max(np.abs(got[nm] - o[nm]))) / scale if o[nm].size else 0.0
+        print(model, N, Nsub, B, nm, err)
+        assert err < TOL, (nm, err)
+    assert np.abs(got["Bp"]).max() == 0.0          # IMPULSE has a single input matrix (DLTV.B, discretization.jl:31)
+    assert (ref.feas == o["feas"]).all()
+    sub = -(-res // (N - 1))
+    assert got["xc"].shape == (B, 1 + (N - 1) * sub, ref.xd.shape[2])
+    for b in range(B):
+        to, xo = orc.propagate_impulse(model, orc.default_params(model), N, ref.xd[b], ref.ud[b], ref.p[b], res=res)
+        assert np.array_equal(to, got["tc"])
+        err = float(np.abs(got["xc"][b] - xo).max()) / max(1.0, float(np.abs(xo).max()))
+        assert err < TOL, (b, err)
 
 
 def test_feasibility_flag_both_ways(pkg, orc):

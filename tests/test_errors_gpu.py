@@ -61,3 +61,21 @@ def test_unsupported_options_are_reported_not_ignored(pkg):
     d.N, d.Nsub, d.batch_capacity, d.disc_method = 8, 4, 1, 1
     h = ctypes.c_void_p()
     assert pkg._lib.lib().scp_problem_create(ctypes.byref(d), ctypes.byref(h)) == 7
+
+
+def test_forms_a_model_lacks_are_refused_at_the_entry_points(pkg):
+    """The kernels of a form exist only for the models that have it; the requests that would need a missing one never reach a
+    launch: scp_problem_create refuses IMPULSE for the three models without an impulse response, and
+    scp_set_discretize_precision refuses fp32 arithmetic for every model but the Starship."""
+    L = pkg._lib.lib()
+    for model_id in (2, 3, 4):       # rocket landing, Starship, free-flyer
+        d = pkg._lib.ScpProblemDesc()
+        d.model_id = model_id
+        d.N, d.Nsub, d.batch_capacity, d.disc_method = 8, 4, 1, 1
+        h = ctypes.c_void_p()
+        assert L.scp_problem_create(ctypes.byref(d), ctypes.byref(h)) == 7 and not h.value      # SCP_ERR_UNSUPPORTED, no handle
+    for name in ("double_integrator", "quadrotor", "rocket_landing", "freeflyer", "oscillator"):
+        pbm = pkg.PTR.create(pkg.PTR.Parameters(N=4, Nsub=3, iter_max=1), pkg.TrajectoryProblem(name), batch_capacity=1)
+        assert L.scp_set_discretize_precision(pbm.handle, 32) == 7, name
+        assert L.scp_set_discretize_precision(pbm.handle, 64) == 0, name
+        pbm.close()
