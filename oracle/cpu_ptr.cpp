@@ -31,9 +31,7 @@
 #include <vector>
 
 #include "../scptoolbox.jl_amd/csrc/stage_problem.hpp"
-#include "../scptoolbox.jl_amd/csrc/models/double_integrator.hpp"
-#include "../scptoolbox.jl_amd/csrc/models/quadrotor.hpp"
-#include "../scptoolbox.jl_amd/csrc/models/rocket_landing.hpp"
+#include "../scptoolbox.jl_amd/csrc/models/registry.hpp"
 
 extern "C" int oracle_discretize(int model_id, const double* par, int N, int Nsub, const double* xd, const double* ud,
                                  const double* p, const double* iSx_diag, double feas_tol, double* A, double* Bm,
@@ -1044,16 +1042,6 @@ static void ptr_one(const double* par, int N, int Nsub, int iters, double wvc, d
     out->feas = feas;
 }
 
-template <class Fn>
-static int with_model(int model_id, Fn&& fn)
-{
-    switch (model_id) {
-        case 0: return fn(DoubleIntegrator{});
-        case 1: return fn(Quadrotor{});
-        case 2: return fn(RocketLanding{});
-        default: return 2;
-    }
-}
 }  // namespace
 
 // Batched PTR solve on the host: arrays in the C-ABI layout of include/scp_mi355x.h (trailing batch dimension), guesses in
@@ -1068,7 +1056,7 @@ extern "C" int cpu_ptr_solve_batch(int model_id, const double* par, int N, int N
 {
     if (threads > 0) omp_set_num_threads(threads);
     int done = 0;
-    int rc = with_model(model_id, [&](auto m) -> int {
+    int rc = with_structured_model(model_id, [&](auto m) -> int {
         using M = decltype(m);
         constexpr int nx = M::nx, nu = M::nu, np = M::np, npp = M::npp;
         const double t0 = omp_get_wtime();
@@ -1085,7 +1073,7 @@ extern "C" int cpu_ptr_solve_batch(int model_id, const double* par, int N, int N
         return 0;
     });
     if (n_done) *n_done = done;
-    return rc;
+    return rc == SCP_ERR_UNSUPPORTED ? (int)SCP_ERR_UNKNOWN_MODEL : rc;   // the twin knows the models of the structured path and no others
 }
 
 extern "C" int cpu_ptr_max_threads() { return omp_get_num_procs(); }

@@ -1,35 +1,18 @@
-// The continuous-time audit's own translation unit: the four instantiations of audit_foh_kernel, the six of
-// audit_interval_kernel with their fold, the four of audit_dispersed_kernel with its fold and the four of audit_tracking_kernel
-// with its fold (audit_kernel.hpp), their launches for the handle-level entry points of scp_api.hip, and the pure-host twins
-// scp_model_audit_host, scp_model_audit_intervals_host, scp_model_audit_dispersed_host and scp_model_audit_tracking_host.
+// The continuous-time audit's own translation unit: per auditable model (models/registry.hpp) the instantiations of audit_foh_kernel,
+// of audit_interval_kernel (FOH, and IMPULSE where the model has it) with their fold, of audit_dispersed_kernel with its fold and of
+// audit_tracking_kernel with its fold (audit_kernel.hpp), their launches for the handle-level entry points of audit_entry.hip, and the
+// pure-host twins scp_model_audit_host, scp_model_audit_intervals_host, scp_model_audit_dispersed_host and
+// scp_model_audit_tracking_host.
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
 #include "../../include/scp_mi355x.h"
+#include "audit_host.hpp"
 #include "audit_kernel.hpp"
-#include "models/double_integrator.hpp"
-#include "models/quadrotor.hpp"
-#include "models/rocket_landing.hpp"
-#include "models/starship.hpp"
+#include "models/registry.hpp"
 
 namespace scp {
-
-// the models the audit is defined for: FOH, no node parameters (the X rows of the free-flyer and of the oscillator read the
-// slacks of their own node)
-template <class Fn>
-static int with_audit_model(int model_id, Fn&& fn)
-{
-    switch (model_id) {
-        case SCP_MODEL_DOUBLE_INTEGRATOR: return fn(DoubleIntegrator{});
-        case SCP_MODEL_QUADROTOR: return fn(Quadrotor{});
-        case SCP_MODEL_ROCKET_LANDING: return fn(RocketLanding{});
-        case SCP_MODEL_STARSHIP: return fn(Starship{});
-        case SCP_MODEL_FREEFLYER: return (int)SCP_ERR_UNSUPPORTED;
-        case SCP_MODEL_OSCILLATOR: return (int)SCP_ERR_UNSUPPORTED;
-        default: return (int)SCP_ERR_UNKNOWN_MODEL;
-    }
-}
 
 __global__ void audit_mask_kernel(const int* status, int* mask, int B)
 {
@@ -40,21 +23,21 @@ __global__ void audit_mask_kernel(const int* status, int* mask, int B)
 int audit_mask_from_status(const int* status, int* mask, int B, hipStream_t stream)
 {
     hipLaunchKernelGGL(audit_mask_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, status, mask, B);
-    return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+    return launch_rc();
 }
 
 int audit_launch(int model_id, const double* model_par, const AuditArgs& a, hipStream_t stream)
 {
-    return with_audit_model(model_id, [&](auto m) -> int {
+    return with_auditable_model(model_id, [&](auto m) -> int {
         using M = decltype(m);
         hipLaunchKernelGGL(audit_foh_kernel<M>, dim3((a.B + 63) / 64), dim3(64), 0, stream, a, M::make_params(model_par));
-        return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+        return launch_rc();
     });
 }
 
 int audit_intervals_launch(int model_id, const double* model_par, int disc_method, const AuditIntervalArgs& a, hipStream_t stream)
 {
-    return with_audit_model(model_id, [&](auto m) -> int {
+    return with_auditable_model(model_id, [&](auto m) -> int {
         using M = decltype(m);
         const typename M::Params par = M::make_params(model_par);
         const dim3 grid((unsigned)(((long)a.B * (a.N - 1) + 63) / 64)), block(64);
@@ -64,9 +47,9 @@ int audit_intervals_launch(int model_id, const double* model_par, int disc_metho
         } else {
             hipLaunchKernelGGL((audit_interval_kernel<M, false>), grid, block, 0, stream, a, par);
         }
-        if (hipGetLastError() != hipSuccess) return (int)SCP_ERR_HIP;
+        if (const int rc = launch_rc()) return rc;
         hipLaunchKernelGGL(audit_interval_fold_kernel<M>, dim3((a.B + 63) / 64), block, 0, stream, a, par);
-        return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+        return launch_rc();
     });
 }
 
@@ -76,11 +59,7 @@ __global__ __launch_bounds__(64) void audit_dispersed_fold_kernel(AuditDispersed
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.B) return;
     double* out = a.audit + (long)b * SCP_AUDIT_WIDTH;
-    if (a.mask != nullptr && a.mask[b] == 0) {
-#pragma unroll
-        for (int i = 0; i < SCP_AUDIT_WIDTH; i++) out[i] = NAN;
-        return;
-    }
+    if (a.mask != nullptr && a.mask[b] == 0) { nan_record<SCP_AUDIT_WIDTH>(out); return; }
     audit_dispersed_fold(a.D, a.flights + (long)b * a.D * SCP_AUDIT_WIDTH, out);
 }
 
@@ -89,14 +68,14 @@ template <class Args, class Params>
 static int audit_flights_launch(void (*flight)(Args, Params), void (*fold)(Args), const Args& a, const Params& par, hipStream_t stream)
 {
     hipLaunchKernelGGL(flight, dim3((unsigned)(((long)a.B * a.D + 63) / 64)), dim3(64), 0, stream, a, par);
-    if (hipGetLastError() != hipSuccess) return (int)SCP_ERR_HIP;
+    if (const int rc = launch_rc()) return rc;
     hipLaunchKernelGGL(fold, dim3((a.B + 63) / 64), dim3(64), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+    return launch_rc();
 }
 
 int audit_dispersed_launch(int model_id, const double* model_par, const AuditDispersedArgs& a, hipStream_t stream)
 {
-    return with_audit_model(model_id, [&](auto m) -> int {
+    return with_auditable_model(model_id, [&](auto m) -> int {
         return audit_flights_launch(audit_dispersed_kernel<decltype(m)>, audit_dispersed_fold_kernel, a, decltype(m)::make_params(model_par), stream);
     });
 }
@@ -107,17 +86,13 @@ __global__ __launch_bounds__(64) void audit_tracking_fold_kernel(AuditTrackingAr
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.B) return;
     double* out = a.audit + (long)b * SCP_AUDIT_WIDTH;
-    if (a.mask != nullptr && a.mask[b] == 0) {
-#pragma unroll
-        for (int i = 0; i < SCP_AUDIT_WIDTH; i++) out[i] = NAN;
-        return;
-    }
+    if (a.mask != nullptr && a.mask[b] == 0) { nan_record<SCP_AUDIT_WIDTH>(out); return; }
     audit_dispersed_fold(a.D, a.flights + (long)b * a.D * SCP_AUDIT_WIDTH, out, 3.0);
 }
 
 int audit_tracking_launch(int model_id, const double* model_par, const AuditTrackingArgs& a, hipStream_t stream)
 {
-    return with_audit_model(model_id, [&](auto m) -> int {
+    return with_auditable_model(model_id, [&](auto m) -> int {
         return audit_flights_launch(audit_tracking_kernel<decltype(m)>, audit_tracking_fold_kernel, a, decltype(m)::make_params(model_par), stream);
     });
 }
@@ -128,7 +103,7 @@ static int audit_flights_host(int model_id, const double* model_par, const doubl
                               const double* p, const double* pp, const double* Sx, const double* Su, const double* K, int res_or_steps, double viol_tol,
                               int D, const double* dx0, const double* ugain, const double* ubias, double marker, double* summary, double* flights)
 {
-    return with_audit_model(model_id, [&](auto m) -> int {
+    return with_auditable_model(model_id, [&](auto m) -> int {
         using M = decltype(m);
         if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
         const typename M::Params par = M::make_params(par_true ? par_true : model_par);
@@ -150,7 +125,7 @@ extern "C" int scp_model_audit_host(int model_id, const double* model_par, int N
                                     double* audit)
 {
     if (!model_par || N < 2 || !xd || !ud || !Sx || !audit || res < 2) return SCP_ERR_BAD_ARGUMENT;
-    return scp::with_audit_model(model_id, [&](auto m) -> int {
+    return scp::with_auditable_model(model_id, [&](auto m) -> int {
         using M = decltype(m);
         if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
         scp::audit_flight_one<M, scp::AuditFlight::nominal>(M::make_params(model_par), N, res, viol_tol, xd, ud, p, pp, Sx, audit);
@@ -164,7 +139,7 @@ extern "C" int scp_model_audit_intervals_host(int model_id, const double* model_
 {
     if (!model_par || N < 2 || !xd || !ud || !Sx || !audit || res < 2) return SCP_ERR_BAD_ARGUMENT;
     if (disc_method != SCP_FOH && disc_method != SCP_IMPULSE) return SCP_ERR_BAD_ARGUMENT;
-    return scp::with_audit_model(model_id, [&](auto m) -> int {
+    return scp::with_auditable_model(model_id, [&](auto m) -> int {
         using M = decltype(m);
         if (disc_method == SCP_IMPULSE && !M::has_impulse) return (int)SCP_ERR_UNSUPPORTED;
         if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;

@@ -464,7 +464,7 @@ struct Sigmas { const double *sig0, *sigu, *sigw; };
 static int cov_begin(scp_problem* h, const Sigmas& g, double nsig, const double* summary)
 {
     TRY(audit_begin(h, 2, summary));
-    if (!cov_sigmas_ok(h->info.nx, h->info.nu, g.sig0, g.sigu, g.sigw, nsig)) {
+    if (!(nsig > 0.0) || !__builtin_isfinite(nsig) || !audit_sigmas_ok(h->info.nx, h->info.nu, g.sig0, g.sigu, g.sigw)) {
         h->err = "audit: sig0 >= 0, sigu >= 0, sigw >= 0, all finite, and a finite nsig > 0 are required";
         return SCP_ERR_BAD_ARGUMENT;
     }
@@ -522,7 +522,7 @@ static int mc_begin(scp_problem* h, int steps, int D, const Sigmas& g, const dou
 {
     TRY(audit_tracking_begin(h, steps, D, 0u, summary));
     if (D < 2 || !stat) { h->err = "audit: D >= 2 flights and the stat array are required"; return SCP_ERR_BAD_ARGUMENT; }
-    if (!mc_sigmas_ok(h->info.nx, h->info.nu, g.sig0, g.sigu, g.sigw)) {
+    if (!audit_sigmas_ok(h->info.nx, h->info.nu, g.sig0, g.sigu, g.sigw)) {
         h->err = "audit: sig0 >= 0, sigu >= 0, sigw >= 0, all finite, are required";
         return SCP_ERR_BAD_ARGUMENT;
     }

@@ -644,6 +644,25 @@ SCP_DEV void audit_dispersed_fold(int D, const double* recs, double* out, double
     out[10] = n_viol; out[11] = n_bad; out[12] = dbc; out[13] = marker; out[14] = (double)D; out[15] = m > 0 ? cmax : NAN;
 }
 
+// the record of a skipped problem (mask[b] == 0): W NaNs
+template <int W>
+SCP_DEV void nan_record(double* out)
+{
+#pragma unroll
+    for (int i = 0; i < W; i++) out[i] = NAN;
+}
+
+// the disturbance model of the covariance and Monte-Carlo audits: sig0[nx], sigu[nu], sigw[nx] all present, finite and >= 0
+inline bool audit_sigmas_ok(int nx, int nu, const double* sig0, const double* sigu, const double* sigw)
+{
+    if (!sig0 || !sigu || !sigw) return false;
+    for (int i = 0; i < nx; i++)
+        if (!__builtin_isfinite(sig0[i]) || sig0[i] < 0.0 || !__builtin_isfinite(sigw[i]) || sigw[i] < 0.0) return false;
+    for (int i = 0; i < nu; i++)
+        if (!__builtin_isfinite(sigu[i]) || sigu[i] < 0.0) return false;
+    return true;
+}
+
 // one thread per (problem, flight), gid = b D + (d - 1), blocks of one wavefront: the mapping of audit_interval_kernel.
 // Neighbouring lanes fly the same problem, so their ud loads hit the same addresses and the trip count is uniform.
 template <class M>

@@ -53,8 +53,6 @@ struct CovArgs {
 
 // cov_api.hip: cov_rows_kernel<M> then cov_chain_kernel<nx, nu> on `stream` (SCP_ERR_UNSUPPORTED for models with node parameters)
 int cov_launch(int model_id, const double* model_par, const CovArgs& a, hipStream_t stream);
-// sig0[nx], sigu[nu], sigw[nx] >= 0, all present and finite; nsig > 0 and finite
-bool cov_sigmas_ok(int nx, int nu, const double* sig0, const double* sigu, const double* sigw, double nsig);
 
 // ------------------------------------------------------------------------------------------------
 // The rows of ONE node k (1-based) of ONE problem: xd[nx,N], ud[nu,N], p[np], pp[npp], Kg[nu,nx,N-1] -> rows_k[nx+1,nrow] and, at

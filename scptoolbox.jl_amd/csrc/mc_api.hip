@@ -1,34 +1,16 @@
-// The Monte-Carlo audit's own translation unit: the four instantiations of mc_flight_kernel (one per auditable model), the fold of
-// the wavefront partials and the per-problem fold (mc_kernel.hpp), their launch for the handle-level entry points of scp_api.hip,
-// and the pure-host twins scp_model_audit_montecarlo_host and scp_mc_draws_host.
+// The Monte-Carlo audit's own translation unit: the instantiations of mc_flight_kernel (one per auditable model, models/registry.hpp),
+// the fold of the wavefront partials and the per-problem fold (mc_kernel.hpp), their launch for the handle-level entry points of
+// audit_entry.hip, and the pure-host twins scp_model_audit_montecarlo_host and scp_mc_draws_host.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <vector>
 
 #include "../../include/scp_mi355x.h"
+#include "audit_host.hpp"
 #include "mc_kernel.hpp"
-#include "models/double_integrator.hpp"
-#include "models/quadrotor.hpp"
-#include "models/rocket_landing.hpp"
-#include "models/starship.hpp"
+#include "models/registry.hpp"
 
 namespace scp {
-
-// the models the audits are defined for (audit_api.hip): FOH, no node parameters
-template <class Fn>
-static int with_mc_model(int model_id, Fn&& fn)
-{
-    switch (model_id) {
-        case SCP_MODEL_DOUBLE_INTEGRATOR: return fn(DoubleIntegrator{});
-        case SCP_MODEL_QUADROTOR: return fn(Quadrotor{});
-        case SCP_MODEL_ROCKET_LANDING: return fn(RocketLanding{});
-        case SCP_MODEL_STARSHIP: return fn(Starship{});
-        case SCP_MODEL_FREEFLYER: return (int)SCP_ERR_UNSUPPORTED;
-        case SCP_MODEL_OSCILLATOR: return (int)SCP_ERR_UNSUPPORTED;
-        default: return (int)SCP_ERR_UNKNOWN_MODEL;
-    }
-}
 
 // one thread per (problem, node): the W partials in wavefront order -> the node's record of moments
 __global__ __launch_bounds__(64) void mc_fold_kernel(McArgs a, int nx, int nu)
@@ -58,10 +40,8 @@ __global__ __launch_bounds__(64) void mc_stat_kernel(McArgs a, int nx, int nu)
     double* out = a.audit + (long)b * SCP_AUDIT_WIDTH;
     double* stat = a.stat + (long)b * SCP_MC_STAT_WIDTH;
     if (a.mask != nullptr && a.mask[b] == 0) {
-#pragma unroll
-        for (int i = 0; i < SCP_AUDIT_WIDTH; i++) out[i] = NAN;
-#pragma unroll
-        for (int i = 0; i < SCP_MC_STAT_WIDTH; i++) stat[i] = NAN;
+        nan_record<SCP_AUDIT_WIDTH>(out);
+        nan_record<SCP_MC_STAT_WIDTH>(stat);
         return;
     }
     mc_stat_one(nx, nu, a.N, a.moments + (long)b * a.N * mc_nv(nx, nu), a.Sx, stat);
@@ -70,25 +50,15 @@ __global__ __launch_bounds__(64) void mc_stat_kernel(McArgs a, int nx, int nu)
 
 int mc_launch(int model_id, const double* model_par, const McArgs& a, hipStream_t stream)
 {
-    return with_mc_model(model_id, [&](auto m) -> int {
+    return with_auditable_model(model_id, [&](auto m) -> int {
         using M = decltype(m);
         hipLaunchKernelGGL(mc_flight_kernel<M>, dim3((unsigned)((long)a.B * a.W)), dim3(64), 0, stream, a, M::make_params(model_par));
-        if (hipGetLastError() != hipSuccess) return (int)SCP_ERR_HIP;
+        if (const int rc = launch_rc()) return rc;
         hipLaunchKernelGGL(mc_fold_kernel, dim3((unsigned)(((long)a.B * a.N + 63) / 64)), dim3(64), 0, stream, a, M::nx, M::nu);
-        if (hipGetLastError() != hipSuccess) return (int)SCP_ERR_HIP;
+        if (const int rc = launch_rc()) return rc;
         hipLaunchKernelGGL(mc_stat_kernel, dim3((a.B + 63) / 64), dim3(64), 0, stream, a, M::nx, M::nu);
-        return hipGetLastError() == hipSuccess ? (int)SCP_OK : (int)SCP_ERR_HIP;
+        return launch_rc();
     });
-}
-
-bool mc_sigmas_ok(int nx, int nu, const double* sig0, const double* sigu, const double* sigw)
-{
-    if (!sig0 || !sigu || !sigw) return false;
-    for (int i = 0; i < nx; i++)
-        if (!std::isfinite(sig0[i]) || sig0[i] < 0.0 || !std::isfinite(sigw[i]) || sigw[i] < 0.0) return false;
-    for (int i = 0; i < nu; i++)
-        if (!std::isfinite(sigu[i]) || sigu[i] < 0.0) return false;
-    return true;
 }
 
 // the `mc` of audit_flight_one in the host twin: the node values of one flight into its lane of the wavefront's table
@@ -116,11 +86,11 @@ extern "C" int scp_model_audit_montecarlo_host(int model_id, const double* model
                                                const double* sigw, double* summary, double* stat, double* moments, double* flights)
 {
     if (!model_par || N < 2 || !xd || !ud || !Sx || !Su || !K || !summary || !stat || steps < 1 || D < 2) return SCP_ERR_BAD_ARGUMENT;
-    return scp::with_mc_model(model_id, [&](auto m) -> int {
+    return scp::with_auditable_model(model_id, [&](auto m) -> int {
         using M = decltype(m);
         constexpr int nx = M::nx, nu = M::nu, nv = 1 + 2 * nx + nu;
         if ((M::np > 0 && !p) || (M::npp > 0 && !pp)) return (int)SCP_ERR_BAD_ARGUMENT;
-        if (!scp::mc_sigmas_ok(nx, nu, sig0, sigu, sigw)) return (int)SCP_ERR_BAD_ARGUMENT;
+        if (!scp::audit_sigmas_ok(nx, nu, sig0, sigu, sigw)) return (int)SCP_ERR_BAD_ARGUMENT;
         const typename M::Params par = M::make_params(model_par);
         std::vector<double> own, own_mom, table((size_t)N * nv * 64), sums((size_t)N * nv, 0.0);
         if (!flights) { own.resize((size_t)SCP_AUDIT_WIDTH * D); flights = own.data(); }

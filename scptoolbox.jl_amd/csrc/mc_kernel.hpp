@@ -60,8 +60,6 @@ struct McArgs {
 
 // mc_api.hip: mc_flight_kernel<M>, mc_fold_kernel and mc_stat_kernel on `stream`
 int mc_launch(int model_id, const double* model_par, const McArgs& a, hipStream_t stream);
-// mc_api.hip: sig0[nx], sigu[nu], sigw[nx] all present, finite and >= 0
-bool mc_sigmas_ok(int nx, int nu, const double* sig0, const double* sigu, const double* sigw);
 
 SCP_DEV constexpr int mc_nv(int nx, int nu) { return 1 + 2 * nx + nu; }
 

@@ -17,12 +17,7 @@
 #include <vector>
 
 #include "../../include/scp_mi355x.h"
-#include "models/double_integrator.hpp"
-#include "models/quadrotor.hpp"
-#include "models/rocket_landing.hpp"
-#include "models/starship.hpp"
-#include "models/freeflyer.hpp"
-#include "models/oscillator.hpp"
+#include "models/registry.hpp"
 
 struct DynBuf {  // one DLTV + defect on the device
     double *A = nullptr, *Bm = nullptr, *Bp = nullptr, *F = nullptr, *r = nullptr, *E = nullptr, *defect = nullptr;
@@ -178,31 +173,6 @@ struct Traj { double *xd, *ud, *p; };   // one trajectory triple on the device
 
 #pragma GCC visibility push(hidden)
 namespace scp {
-
-// dispatch a generic lambda on the model type
-template <class Fn>
-static int with_model(int model_id, Fn&& fn)
-{
-    switch (model_id) {
-        case SCP_MODEL_DOUBLE_INTEGRATOR: return fn(DoubleIntegrator{});
-        case SCP_MODEL_QUADROTOR: return fn(Quadrotor{});
-        case SCP_MODEL_ROCKET_LANDING: return fn(RocketLanding{});
-        case SCP_MODEL_STARSHIP: return fn(Starship{});
-        case SCP_MODEL_FREEFLYER: return fn(Freeflyer{});
-        case SCP_MODEL_OSCILLATOR: return fn(Oscillator{});
-        default: return SCP_ERR_UNKNOWN_MODEL;
-    }
-}
-// models with the stage-structured PTR fast path (stage_problem.hpp + ipm2_*.hpp: one arrow column, <= 16 penalised rows
-// per node); the others (M::structured == false) run their subproblems through the generic conic path
-template <class Fn>
-static int with_structured_model(int model_id, Fn&& fn)
-{
-    return with_model(model_id, [&](auto m) -> int {
-        if constexpr (decltype(m)::structured) return fn(m);
-        else return (int)SCP_ERR_UNSUPPORTED;
-    });
-}
 
 template <class T>
 static int dalloc(scp_problem* h, T** p, size_t count)

@@ -1,53 +1,22 @@
 // Stand-alone sanitizer check of the host twin of the dispersed-flight audit (scp_model_audit_dispersed_host,
 // csrc/audit_api.hip): the bodies the device kernels run, on heap arrays of EXACTLY the documented sizes, for the rocket landing
 // and the quadrotor, N in {2, 9}, D in {1, 3}, with and without the flight records and the truth model.  Not a pytest and not
-// loaded into Python.  Build and run from the repository root (host code only; no GPU is needed or used):
-//
-//   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//         tools/audit_dispersed_host_check.cpp scptoolbox.jl_amd/csrc/audit_api.hip -o build/audit_dispersed_host_check \
-//         && build/audit_dispersed_host_check
+// loaded into Python.  Built and run by `make -C tools host-checks` (see tools/Makefile, HOST_CHECK_UNITS).
 //
 // Exit status 0 and one line per call when every call returned SCP_OK with finite, flag-free records whose summary is the same
 // with and without the flight records.
-#include <cmath>
-#include <cstdio>
-#include <vector>
-
-#include "../include/scp_mi355x.h"
-
-struct Case {
-    const char* name;
-    int id, nx, nu, np, npp;
-    std::vector<double> par, par_true, x0, xf, u, p, pp, Sx;
-};
+#include "host_check.hpp"
 
 int main()
 {
-    const double d2r = 3.14159265358979323846 / 180.0;
-    std::vector<Case> cases;
-    // the truth models: heavier gravity, a thirstier engine and less thrust for the rocket; heavier gravity for the quadrotor
-    cases.push_back({"rocket_landing", SCP_MODEL_ROCKET_LANDING, 7, 4, 1, 6,
-                     {0, 0, -3.7114, 6.1e-5, 0, 3.5e-5, 5.1e-4, 1505, 1905, 4972, 13258, 86 * d2r, 40 * d2r, 138.9, 40, 120, 1},
-                     {0, 0, -4.0, 6.1e-5, 0, 3.5e-5, 5.6e-4, 1505, 1905, 4972, 12000, 86 * d2r, 40 * d2r, 138.9, 40, 120, 1},
-                     {2000, 0, 1500, 80, 30, -75, std::log(1905.0)}, {0, 0, 0, 0, 0, 0, std::log(1505.0)}, {0.1, 0.1, 3.7, 3.9}, {75},
-                     {2000, 0, 1500, 80, 30, -75}, {5000, 5000, 2500, 278, 278, 278, 0.24}});
-    cases.push_back({"quadrotor", SCP_MODEL_QUADROTOR, 6, 4, 1, 12,
-                     {9.81, 0.6, 23.2, 60 * d2r, 0.0, 2.5, 0.0, 2, 2, 0, 1, 2, 0, 1.5, 1.5, 0, 2, 5, 0},
-                     {10.3, 0.6, 23.2, 60 * d2r, 0.0, 2.5, 0.0, 2, 2, 0, 1, 2, 0, 1.5, 1.5, 0, 2, 5, 0},
-                     {0, 0, 0, 0, 0, 0}, {2.5, 6, 0, 0, 0, 0}, {0.1, -0.2, 9.81, 9.9}, {1.25}, {0, 0, 0, 0, 0, 0, 2.5, 6, 0, 0, 0, 0},
-                     {1, 1, 1, 1, 1, 1}});
-    int bad = 0;
-    for (const Case& c : cases) {
+    for (int id : {SCP_MODEL_ROCKET_LANDING, SCP_MODEL_QUADROTOR}) {
+        const Model& c = models()[id];
         for (int N : {2, 9}) {
             for (int D : {1, 3}) {
                 for (int truth = 0; truth < 2; truth++) {
                     const int res = 6 * (N - 1) + 1;
-                    std::vector<double> xd((size_t)c.nx * N), ud((size_t)c.nu * N);
-                    for (int k = 0; k < N; k++) {
-                        const double t = (double)k / (N - 1);
-                        for (int i = 0; i < c.nx; i++) xd[(size_t)k * c.nx + i] = (1 - t) * c.x0[i] + t * c.xf[i];
-                        for (int i = 0; i < c.nu; i++) ud[(size_t)k * c.nu + i] = c.u[i] * (1.0 + 0.05 * std::sin(3.0 * k + i));
-                    }
+                    std::vector<double> xd, ud;
+                    straight_line(c, N, xd, ud);
                     std::vector<double> dx0((size_t)c.nx * D), gain((size_t)c.nu * D), bias((size_t)c.nu * D);
                     for (int d = 0; d < D; d++) {
                         for (int i = 0; i < c.nx; i++) dx0[(size_t)d * c.nx + i] = 0.01 * d * c.Sx[i] * std::sin(1.0 + i + d);
@@ -79,7 +48,7 @@ int main()
     }
     // NULL dispersion arrays, and the refusals, which touch no array
     {
-        const Case& c = cases[1];
+        const Model& c = models()[SCP_MODEL_QUADROTOR];
         const int N = 2;
         std::vector<double> xd(c.x0), ud(c.u), sum(SCP_AUDIT_WIDTH, -7.0);
         xd.insert(xd.end(), c.xf.begin(), c.xf.end());
@@ -87,10 +56,8 @@ int main()
         if (scp_model_audit_dispersed_host(c.id, c.par.data(), nullptr, N, xd.data(), ud.data(), c.p.data(), c.pp.data(), c.Sx.data(), 5, 0.0, 2,
                                            nullptr, nullptr, nullptr, sum.data(), nullptr) != SCP_OK || sum[11] != 0.0 || sum[14] != 2.0) bad++;
     }
-    double one[SCP_AUDIT_WIDTH] = {0};
     if (scp_model_audit_dispersed_host(SCP_MODEL_FREEFLYER, one, nullptr, 5, one, one, one, one, one, 4, 0.0, 1, one, one, one, one, one) != SCP_ERR_UNSUPPORTED) bad++;
     if (scp_model_audit_dispersed_host(SCP_MODEL_QUADROTOR, one, nullptr, 5, one, one, one, one, one, 4, 0.0, 0, one, one, one, one, one) != SCP_ERR_BAD_ARGUMENT) bad++;
     if (scp_model_audit_dispersed_host(SCP_MODEL_QUADROTOR, one, nullptr, 5, one, one, one, one, one, 1, 0.0, 1, one, one, one, one, one) != SCP_ERR_BAD_ARGUMENT) bad++;
-    std::printf("%s\n", bad ? "FAILED" : "ok");
-    return bad ? 1 : 0;
+    return verdict();
 }

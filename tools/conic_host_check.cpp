@@ -5,12 +5,8 @@
 // AddressSanitizer reports a carve that runs past the total (in effect the last array) and any overrun of the input and output
 // arrays; an array that is too short in the middle spills into its neighbour inside the allocation and shows only as a wrong
 // status or cost.  On programs this small the "nd" pass ends with the level counts of the "seq" pass (printed below), so it
-// adds the other entry of the order selection, not another schedule.  Not a pytest and not loaded into Python.  Build and run from the repository root (host code only, no GPU is needed or used; without -fopenmp, because the
-// OpenMP runtime's own allocation trips the leak check):
-//
-//   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -x hip -Wno-unknown-pragmas \
-//         -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//         tools/conic_host_check.cpp oracle/conic_host.cpp -o build/conic_host_check -lpthread && build/conic_host_check
+// adds the other entry of the order selection, not another schedule.  Not a pytest and not loaded into Python.  Built and run by
+// `make -C tools host-checks` (see tools/Makefile, HOST_CHECK_UNITS; host code only, no GPU is needed or used).
 //
 // Exit status 0 and "ok" when every problem ended OPTIMAL within 1e-7 of its closed-form cost (the bound
 // tests/test_conic_geometry_gpu.py holds this solver to on the softplus family) and the runs with shared arrays gave the bits

@@ -2,53 +2,16 @@
 // the four dimension pairs, N in {2, 9}, with a finite problem, a failing one (a pivot of exactly 0) and a non-finite one; and
 // scp_model_audit_tracking_host (csrc/audit_api.hip) for the rocket landing and the quadrotor, N in {2, 9}, D in {1, 3},
 // steps in {1, 4}, with and without the flight records and the truth model, flown with the gains the first twin made.  Heap
-// arrays of EXACTLY the documented sizes.  Not a pytest and not loaded into Python.  Build and run from the repository root (host
-// code only; no GPU is needed or used):
-//
-//   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//         tools/lqr_tracking_host_check.cpp scptoolbox.jl_amd/csrc/audit_api.hip scptoolbox.jl_amd/csrc/lqr_api.hip \
-//         -o build/lqr_tracking_host_check && build/lqr_tracking_host_check
+// arrays of EXACTLY the documented sizes.  Not a pytest and not loaded into Python.  Built and run by `make -C tools host-checks` (see tools/Makefile, HOST_CHECK_UNITS).
 //
 // Exit status 0 and one line per call when every call returned what it should.
-#include <cmath>
-#include <cstdio>
-#include <vector>
-
-#include "../include/scp_mi355x.h"
-
-struct Case {
-    const char* name;
-    int id, nx, nu, np, npp;
-    std::vector<double> par, par_true, x0, xf, u, p, pp, Sx, Su;
-};
-
-// a discretisation that looks like one: A = I + h (a few couplings), B-, B+ = h / 2 (a few entries); [.,.,N-1] column-major
-static void make_dyn(int nx, int nu, int N, std::vector<double>& A, std::vector<double>& Bm, std::vector<double>& Bp)
-{
-    const double h = 1.0 / (N - 1);
-    A.assign((size_t)nx * nx * (N - 1), 0.0);
-    Bm.assign((size_t)nx * nu * (N - 1), 0.0);
-    Bp.assign((size_t)nx * nu * (N - 1), 0.0);
-    for (int k = 0; k < N - 1; k++) {
-        double* a = A.data() + (size_t)k * nx * nx;
-        for (int i = 0; i < nx; i++) a[i + nx * i] = 1.0;
-        for (int i = 0; i + nx / 2 < nx; i++) a[i + nx * (i + nx / 2)] = h * (1.0 + 0.1 * k);      // position rows read the velocities
-        for (int c = 0; c < nu; c++) {
-            const int i = nx / 2 + c % (nx - nx / 2);
-            Bm[(size_t)k * nx * nu + i + nx * c] = 0.5 * h * (1.0 + 0.05 * c);
-            Bp[(size_t)k * nx * nu + i + nx * c] = 0.5 * h * (1.0 - 0.05 * c);
-            Bm[(size_t)k * nx * nu + c % nx + nx * c] += 0.1 * h * h;
-        }
-    }
-}
+#include "host_check.hpp"
 
 int main()
 {
-    int bad = 0;
     // ---- scp_lqr_gains_host ----
-    const int dims[4][2] = {{2, 1}, {6, 4}, {7, 4}, {8, 3}};
-    for (const auto& d : dims) {
-        const int nx = d[0], nu = d[1];
+    for (const Model& m : models()) {
+        const int nx = m.nx, nu = m.nu;
         for (int N : {2, 9}) {
             std::vector<double> A, Bm, Bp, qx(nx, 1.0), ru(nu, 0.5), qf(nx, 10.0);
             make_dyn(nx, nu, N, A, Bm, Bp);
@@ -81,9 +44,6 @@ int main()
         }
     }
     {
-        double one[64] = {1.0};
-        for (double& v : one) v = 1.0;
-        double neg[8] = {-1.0, 1, 1, 1, 1, 1, 1, 1};
         if (scp_lqr_gains_host(13, 6, 5, one, one, one, one, one, one, one, one) != SCP_ERR_UNSUPPORTED) bad++;
         if (scp_lqr_gains_host(2, 1, 2, one, one, one, neg, one, one, one, one) != SCP_ERR_BAD_ARGUMENT) bad++;
         if (scp_lqr_gains_host(2, 1, 2, one, one, one, one, neg, one, one, one) != SCP_ERR_BAD_ARGUMENT) bad++;
@@ -92,29 +52,14 @@ int main()
     }
 
     // ---- scp_model_audit_tracking_host ----
-    const double d2r = 3.14159265358979323846 / 180.0;
-    std::vector<Case> cases;
-    cases.push_back({"rocket_landing", SCP_MODEL_ROCKET_LANDING, 7, 4, 1, 6,
-                     {0, 0, -3.7114, 6.1e-5, 0, 3.5e-5, 5.1e-4, 1505, 1905, 4972, 13258, 86 * d2r, 40 * d2r, 138.9, 40, 120, 1},
-                     {0, 0, -4.0, 6.1e-5, 0, 3.5e-5, 5.6e-4, 1505, 1905, 4972, 12000, 86 * d2r, 40 * d2r, 138.9, 40, 120, 1},
-                     {2000, 0, 1500, 80, 30, -75, std::log(1905.0)}, {0, 0, 0, 0, 0, 0, std::log(1505.0)}, {0.1, 0.1, 3.7, 3.9}, {75},
-                     {2000, 0, 1500, 80, 30, -75}, {5000, 5000, 2500, 278, 278, 278, 0.24}, {14, 14, 7, 7}});
-    cases.push_back({"quadrotor", SCP_MODEL_QUADROTOR, 6, 4, 1, 12,
-                     {9.81, 0.6, 23.2, 60 * d2r, 0.0, 2.5, 0.0, 2, 2, 0, 1, 2, 0, 1.5, 1.5, 0, 2, 5, 0},
-                     {10.3, 0.6, 23.2, 60 * d2r, 0.0, 2.5, 0.0, 2, 2, 0, 1, 2, 0, 1.5, 1.5, 0, 2, 5, 0},
-                     {0, 0, 0, 0, 0, 0}, {2.5, 6, 0, 0, 0, 0}, {0.1, -0.2, 9.81, 9.9}, {1.25}, {0, 0, 0, 0, 0, 0, 2.5, 6, 0, 0, 0, 0},
-                     {1, 1, 1, 1, 1, 1}, {46, 46, 46, 23}});
-    for (const Case& c : cases) {
+    for (int id : {SCP_MODEL_ROCKET_LANDING, SCP_MODEL_QUADROTOR}) {
+        const Model& c = models()[id];
         for (int N : {2, 9}) {
             for (int D : {1, 3}) {
                 for (int steps : {1, 4}) {
                     for (int truth = 0; truth < 2; truth++) {
-                        std::vector<double> xd((size_t)c.nx * N), ud((size_t)c.nu * N);
-                        for (int k = 0; k < N; k++) {
-                            const double t = (double)k / (N - 1);
-                            for (int i = 0; i < c.nx; i++) xd[(size_t)k * c.nx + i] = (1 - t) * c.x0[i] + t * c.xf[i];
-                            for (int i = 0; i < c.nu; i++) ud[(size_t)k * c.nu + i] = c.u[i] * (1.0 + 0.05 * std::sin(3.0 * k + i));
-                        }
+                        std::vector<double> xd, ud;
+                        straight_line(c, N, xd, ud);
                         std::vector<double> dx0((size_t)c.nx * D), gain((size_t)c.nu * D), bias((size_t)c.nu * D);
                         for (int d = 0; d < D; d++) {
                             for (int i = 0; i < c.nx; i++) dx0[(size_t)d * c.nx + i] = 0.01 * (d + 1) * c.Sx[i] * std::sin(1.0 + i + d);
@@ -123,14 +68,9 @@ int main()
                                 bias[(size_t)d * c.nu + i] = 0.01 * d * std::sin(3.0 + i);
                             }
                         }
-                        // gains by Bryson's rule on the synthetic discretisation: small, finite, of the documented size
-                        std::vector<double> A, Bm, Bp, qx(c.nx), ru(c.nu), qf(c.nx);
+                        std::vector<double> A, Bm, Bp, K;
                         make_dyn(c.nx, c.nu, N, A, Bm, Bp);
-                        for (int i = 0; i < c.nx; i++) { qx[i] = 1.0 / (c.Sx[i] * c.Sx[i]); qf[i] = 10.0 * qx[i]; }
-                        for (int i = 0; i < c.nu; i++) ru[i] = 1.0 / (c.Su[i] * c.Su[i]);
-                        std::vector<double> K((size_t)c.nu * c.nx * (N - 1)), info(SCP_LQR_INFO_WIDTH);
-                        const int rg = scp_lqr_gains_host(c.nx, c.nu, N, A.data(), Bm.data(), Bp.data(), qx.data(), ru.data(), qf.data(), K.data(),
-                                                          info.data());
+                        const bool gk = gains(c.nx, c.nu, N, A, Bm, Bp, c.Sx, c.Su, K);
                         std::vector<double> par(c.par), pt(c.par_true), p(c.p), pp(c.pp), Sx(c.Sx), Su(c.Su);
                         std::vector<double> sum(SCP_AUDIT_WIDTH, -7.0), only(SCP_AUDIT_WIDTH, -8.0), rec((size_t)SCP_AUDIT_WIDTH * D, -9.0);
                         const double* ptrue = truth ? pt.data() : nullptr;
@@ -140,7 +80,7 @@ int main()
                         const int rc2 = scp_model_audit_tracking_host(c.id, par.data(), ptrue, N, xd.data(), ud.data(), p.data(), pp.data(),
                                                                       Sx.data(), Su.data(), K.data(), steps, 0.0, D, dx0.data(), gain.data(),
                                                                       bias.data(), only.data(), nullptr);
-                        bool fin = rg == SCP_OK && info[0] == 0.0 && rc == SCP_OK && rc2 == SCP_OK && sum[11] == 0.0 && sum[13] == 3.0 && sum[14] == (double)D;
+                        bool fin = gk && rc == SCP_OK && rc2 == SCP_OK && sum[11] == 0.0 && sum[13] == 3.0 && sum[14] == (double)D;
                         for (int i = 6; i < SCP_AUDIT_WIDTH; i++) fin = fin && std::isfinite(sum[i]) && sum[i] == only[i];
                         for (int d = 0; d < D; d++) {
                             const double* r = rec.data() + (size_t)d * SCP_AUDIT_WIDTH;
@@ -157,7 +97,7 @@ int main()
     }
     // NULL dispersion arrays, and the refusals, which touch no array
     {
-        const Case& c = cases[1];
+        const Model& c = models()[SCP_MODEL_QUADROTOR];
         const int N = 2;
         std::vector<double> xd(c.x0), ud(c.u), sum(SCP_AUDIT_WIDTH, -7.0), K((size_t)c.nu * c.nx, 0.0);
         xd.insert(xd.end(), c.xf.begin(), c.xf.end());
@@ -166,11 +106,9 @@ int main()
                                           K.data(), 3, 0.0, 2, nullptr, nullptr, nullptr, sum.data(), nullptr) != SCP_OK || sum[11] != 0.0 ||
             sum[14] != 2.0 || sum[13] != 3.0) bad++;
     }
-    double one[SCP_AUDIT_WIDTH] = {0};
     if (scp_model_audit_tracking_host(SCP_MODEL_FREEFLYER, one, nullptr, 5, one, one, one, one, one, one, one, 4, 0.0, 1, one, one, one, one, one) != SCP_ERR_UNSUPPORTED) bad++;
     if (scp_model_audit_tracking_host(SCP_MODEL_QUADROTOR, one, nullptr, 5, one, one, one, one, one, one, one, 4, 0.0, 0, one, one, one, one, one) != SCP_ERR_BAD_ARGUMENT) bad++;
     if (scp_model_audit_tracking_host(SCP_MODEL_QUADROTOR, one, nullptr, 5, one, one, one, one, one, one, one, 0, 0.0, 1, one, one, one, one, one) != SCP_ERR_BAD_ARGUMENT) bad++;
     if (scp_model_audit_tracking_host(SCP_MODEL_QUADROTOR, one, nullptr, 5, one, one, one, one, one, one, nullptr, 4, 0.0, 1, one, one, one, one, one) != SCP_ERR_BAD_ARGUMENT) bad++;
-    std::printf("%s\n", bad ? "FAILED" : "ok");
-    return bad ? 1 : 0;
+    return verdict();
 }

@@ -2,74 +2,24 @@
 // landing and the quadrotor, N in {2, 9}, D in {2, 64, 65} (one padded wavefront, a full one, a second one with a single flight),
 // with and without the optional outputs, and scp_mc_draws_host for odd and even n (both csrc/mc_api.hip).  The gains come from
 // scp_lqr_gains_host (csrc/lqr_api.hip).  Heap arrays of EXACTLY the documented sizes.  Not a pytest and not loaded into Python.
-// Build and run from the repository root (host code only; no GPU is needed or used):
-//
-//   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//         tools/montecarlo_host_check.cpp scptoolbox.jl_amd/csrc/mc_api.hip scptoolbox.jl_amd/csrc/lqr_api.hip \
-//         -o build/montecarlo_host_check && build/montecarlo_host_check
+// Built and run by `make -C tools host-checks` (see tools/Makefile, HOST_CHECK_UNITS).
 //
 // Exit status 0 and one line per call when every call returned what it should.
-#include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <vector>
 
-#include "../include/scp_mi355x.h"
-
-struct Case {
-    const char* name;
-    int id, nx, nu;
-    std::vector<double> par, x0, xf, u, p, pp, Sx, Su;
-};
-
-// a discretisation that looks like one: A = I + h (a few couplings), B-, B+ = h / 2 (a few entries); [.,.,N-1] column-major
-static void make_dyn(int nx, int nu, int N, std::vector<double>& A, std::vector<double>& Bm, std::vector<double>& Bp)
-{
-    const double h = 1.0 / (N - 1);
-    A.assign((size_t)nx * nx * (N - 1), 0.0);
-    Bm.assign((size_t)nx * nu * (N - 1), 0.0);
-    Bp.assign((size_t)nx * nu * (N - 1), 0.0);
-    for (int k = 0; k < N - 1; k++) {
-        double* a = A.data() + (size_t)k * nx * nx;
-        for (int i = 0; i < nx; i++) a[i + nx * i] = 1.0;
-        for (int i = 0; i + nx / 2 < nx; i++) a[i + nx * (i + nx / 2)] = h * (1.0 + 0.1 * k);
-        for (int c = 0; c < nu; c++) {
-            const int i = nx / 2 + c % (nx - nx / 2);
-            Bm[(size_t)k * nx * nu + i + nx * c] = 0.5 * h * (1.0 + 0.05 * c);
-            Bp[(size_t)k * nx * nu + i + nx * c] = 0.5 * h * (1.0 - 0.05 * c);
-        }
-    }
-}
+#include "host_check.hpp"
 
 int main()
 {
-    int bad = 0;
-    const double d2r = 3.14159265358979323846 / 180.0;
-    std::vector<Case> cases;
-    cases.push_back({"rocket_landing", SCP_MODEL_ROCKET_LANDING, 7, 4,
-                     {0, 0, -3.7114, 6.1e-5, 0, 3.5e-5, 5.1e-4, 1505, 1905, 4972, 13258, 86 * d2r, 40 * d2r, 138.9, 40, 120, 1},
-                     {2000, 0, 1500, 80, 30, -75, std::log(1905.0)}, {0, 0, 0, 0, 0, 0, std::log(1505.0)}, {0.1, 0.1, 3.7, 3.9}, {75},
-                     {2000, 0, 1500, 80, 30, -75}, {5000, 5000, 2500, 278, 278, 278, 0.24}, {14, 14, 7, 7}});
-    cases.push_back({"quadrotor", SCP_MODEL_QUADROTOR, 6, 4,
-                     {9.81, 0.6, 23.2, 60 * d2r, 0.0, 2.5, 0.0, 2, 2, 0, 1, 2, 0, 1.5, 1.5, 0, 2, 5, 0},
-                     {0, 0, 0, 0, 0, 0}, {2.5, 6, 0, 0, 0, 0}, {0.1, -0.2, 9.81, 9.9}, {1.25}, {0, 0, 0, 0, 0, 0, 2.5, 6, 0, 0, 0, 0},
-                     {1, 1, 1, 1, 1, 1}, {46, 46, 46, 23}});
-    for (const Case& c : cases) {
+    for (int id : {SCP_MODEL_ROCKET_LANDING, SCP_MODEL_QUADROTOR}) {
+        const Model& c = models()[id];
         const int nv = 1 + 2 * c.nx + c.nu;
         for (int N : {2, 9}) {
-            std::vector<double> xd((size_t)c.nx * N), ud((size_t)c.nu * N);
-            for (int k = 0; k < N; k++) {
-                const double t = (double)k / (N - 1);
-                for (int i = 0; i < c.nx; i++) xd[(size_t)k * c.nx + i] = (1 - t) * c.x0[i] + t * c.xf[i];
-                for (int i = 0; i < c.nu; i++) ud[(size_t)k * c.nu + i] = c.u[i] * (1.0 + 0.05 * std::sin(3.0 * k + i));
-            }
-            std::vector<double> A, Bm, Bp, K((size_t)c.nu * c.nx * (N - 1), -5.0);
-            make_dyn(c.nx, c.nu, N, A, Bm, Bp);
-            std::vector<double> qx(c.nx), ru(c.nu), qf(c.nx), info(SCP_LQR_INFO_WIDTH);
-            for (int i = 0; i < c.nx; i++) { qx[i] = 1.0 / (c.Sx[i] * c.Sx[i]); qf[i] = 10.0 * qx[i]; }
-            for (int i = 0; i < c.nu; i++) ru[i] = 1.0 / (c.Su[i] * c.Su[i]);
-            const bool gk = scp_lqr_gains_host(c.nx, c.nu, N, A.data(), Bm.data(), Bp.data(), qx.data(), ru.data(), qf.data(), K.data(),
-                                               info.data()) == SCP_OK && info[0] == 0.0;
+            std::vector<double> xd, ud;
+            straight_line(c, N, xd, ud);
+            std::vector<double> A, Bm, Bp, K;
+            make_dyn(c.nx, c.nu, N, A, Bm, Bp, false);
+            const bool gk = gains(c.nx, c.nu, N, A, Bm, Bp, c.Sx, c.Su, K);
             std::vector<double> par(c.par), p(c.p), pp(c.pp), Sx(c.Sx), Su(c.Su), sig0(c.nx), sigu(c.nu), sigw(c.nx);
             for (int i = 0; i < c.nx; i++) { sig0[i] = 0.01 * Sx[i]; sigw[i] = 0.002 * Sx[i]; }
             for (int i = 0; i < c.nu; i++) sigu[i] = 0.01 * Su[i];
@@ -135,9 +85,6 @@ int main()
     // the refusals, which touch no array
     {
         const int before = bad;
-        double one[64];
-        for (double& v : one) v = 1.0;
-        double neg[8] = {-1.0, 1, 1, 1, 1, 1, 1, 1};
 #define MC(id, K, steps, D, s0, su, sw, sum, st) \
     scp_model_audit_montecarlo_host(id, one, 5, one, one, one, one, one, one, K, steps, 0.0, D, 0, s0, su, sw, sum, st, nullptr, nullptr)
         if (MC(SCP_MODEL_FREEFLYER, one, 1, 2, one, one, one, one, one) != SCP_ERR_UNSUPPORTED) bad++;
@@ -156,6 +103,5 @@ int main()
         if (scp_mc_draws_host(0, 0, 0, 1, 2, nullptr, nullptr) != SCP_ERR_BAD_ARGUMENT) bad++;
         std::printf("refusals: %d wrong\n", bad - before);
     }
-    std::printf("%s\n", bad ? "FAILED" : "ok");
-    return bad ? 1 : 0;
+    return verdict();
 }

@@ -1,11 +1,8 @@
 // Stand-alone sanitizer check of the host compilation of the oscillator model (csrc/models/oscillator.hpp): the functions the
 // device kernels call, on heap arrays of EXACTLY the sizes the kernels give them, at the mild and at the extreme sharpness
 // kappa1 of the deadband homotopy (where exp overflows to Inf and the reference's order of operations must still give finite
-// values).  Not a pytest and not loaded into Python.  Build and run from the repository root (host code only; no GPU is needed
-// or used):
-//
-//   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//         tools/oscillator_host_check.cpp -o build/oscillator_host_check && build/oscillator_host_check
+// values).  Not a pytest and not loaded into Python.  Built and run by
+// `make -C tools host-checks` (see tools/Makefile, HOST_CHECK_UNITS).
 //
 // Exit status 0 and "ok" when every value was finite and the analytic Jacobian of s agrees with central differences.
 #include <cmath>
